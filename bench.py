@@ -8,7 +8,10 @@ Net_MDA with MSA + SDA losses (BASELINE.json configs[1]: N=1024, k=20, batch 32 
 A step = 2 semantic + 2 node forwards (4 encoder passes over 2B clouds), 3 soft-MMD losses
 with SDA weights, one backward, 3 Adam updates (train_dg_single_gpu.py:246-335).  Inputs are
 synthetic (U(-1,1)^3 -> normal_pc, labels randint(0,10)) and resident in HBM before the
-timed region; weights are random-init.  Prints ONE JSON line on rank 0.
+timed region; weights are random-init.  Prints ONE JSON line on rank 0.  --steps is the number
+of timed steps, `ms_per_step` the wall time of one of them; --dump-outputs DIR writes what the
+last timed step computed as .npy files (inputs and initial weights are seeded: the same
+arguments give the same inputs on every run).
 
 `roofline` describes the dominant hand-written kernel of the step, timed live with events
 on the stream it is launched on; `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py,
@@ -371,6 +374,34 @@ def other_workload(model_name, B, N, fp16, dev, steps=10, warmup=3, profile_step
         torch.cuda.empty_cache()
 
 
+DUMP_STATE_BYTES = 48 * 10 ** 6       # model state budget of --dump-outputs (the whole directory stays under 64 MB)
+
+
+def dump_outputs(path, losses, model, budget=DUMP_STATE_BYTES):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy -- the three losses SUGStep.step
+    returns (loss_cls.npy, loss_geo.npy, loss_sem.npy; a loss the step does not compute is not written) and the model state
+    the step updated in place (state.<state_dict key>.npy: weights after the three Adam updates, BatchNorm buffers).  Float
+    tensors are written as float32, integer buffers as float64.  When the state exceeds `budget` bytes in float32, every
+    tensor of more than 4096 elements is replaced by a fixed sample of its flattened elements (indices drawn from a
+    generator seeded with 0, sorted; the same share of every tensor), so two builds of the project compare element for
+    element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(('loss_cls', 'loss_geo', 'loss_sem'), losses):
+        if t is not None:
+            np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
+    state = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    total = sum(4 * v.numel() for v in state.values())
+    share = min(1.0, budget / total)
+    for k, v in state.items():
+        v = v.double() if not v.is_floating_point() else v.float()
+        if share < 1.0 and v.numel() > 4096:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(v.numel(), generator=g)[:max(4096, int(share * v.numel()))].sort()[0]
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, 'state.%s.npy' % k), v.numpy())
+
+
 def param_counts(model):
     """(parameter elements of the model, parameter elements summed over the three Adam optimizers of a step)."""
     n_g = sum(p.numel() for p in model.g.parameters())
@@ -511,7 +542,12 @@ def main():
                          'then says so in config.workload (not the headline configuration)')
     ap.add_argument('--no-pair', action='store_true',
                     help='separate encoder passes for the source and the target batch (identical results)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one returned (losses) and the model state it updated '
+                         'as DIR/<name>.npy, under 64 MB in all (e.g. DIR = bench_outputs); same arguments, same inputs')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -662,6 +698,9 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     loss_vals = [None if l is None else float(l) for l in losses]
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the graph's loss buffers and the weights change with every further step
+        dump_outputs(args.dump_outputs, losses, model)
     prof, ops.CTX.profile = ({} if graph_mode else ops.CTX.profile), None
     eager_ms = None
     exact_ms = None

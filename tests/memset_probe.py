@@ -1,6 +1,6 @@
 """Child process of test_training_step_issues_no_device_memsets: one eager training step under torch.profiler, prints
 {"kernels": n, "memsets": [names]}.  A child because the profiler's teardown (kineto / roctracer, stop_trace) now and then
-takes the whole process down with a segmentation fault on this stack; the test retries, the test run survives.
+took the whole process down with a segmentation fault on this stack; a crash fails the test, the test run survives.
 usage: python tests/memset_probe.py MODEL [fp16]"""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -28,17 +28,41 @@ def test_two_training_steps_match_reference():
     tr = SUGStep(net, lr=1e-3, weight_decay=5e-5, methods=methods)        # defaults: paired domains, sug_amd.optim.Adam
     data, data_t = G['data'].cuda(), G['data_t'].cuda()
     lab, lab_t = G['label'].cuda(), G['label_t'].cuda()
+    from sug_amd import ops
     torch.manual_seed(seed)
-    got = []
-    for _ in range(2):
-        lc, lg, ls = tr.step(data, lab, data_t, lab_t)
+    got, lists, real_knn = [], [], ops.knn
+
+    def spy(f, k):
+        idx = real_knn(f, k)
+        lists.append(idx.cpu().long())
+        return idx
+    B = data.shape[0]
+    forced = []
+    for i in range(2):
+        del lists[:]
+        ops.knn = spy                                    # the neighbour graphs of each step (paired pass: [2B, N, k] each)
+        try:
+            lc, lg, ls = tr.step(data, lab, data_t, lab_t)
+        finally:
+            ops.knn = real_knn
         got.append([lc.item(), lg.item(), ls.item()])
+        assert len(lists) == 6 and lists[0].shape[0] == 2 * B, len(lists)
+        forced.append(list(lists))
     want = G['losses'].tolist()
+    with torch.no_grad():                                # free-running step 1 of the oracle
+        torch.manual_seed(seed)
+        free = [float(v) for v in O.sug_losses(O.as_params(O.fill_params({k: tuple(v.shape) for k, v in net.state_dict().items()}, seed)),
+                                               'DGCNN', G['data'], G['label'], G['data_t'], G['label_t'],
+                                               methods['GEO_MMD'][0], methods['SEM_MMD'][0])]
 
     # The oracle run on THIS machine's CPU (same algorithm as the reference, proven equal to it
     # where the golden was produced).  Free-running feature-space kNN makes the reference's own
-    # losses CPU-dependent at the 1e-3 level (sgemm rounding flips near-tied neighbours), so the
-    # tight comparison is against the oracle here and the golden gets the looser bound.
+    # losses CPU-dependent at the 1e-3 level (sgemm rounding flips near-tied neighbours; which ones
+    # depends on the CPU and its thread count), so the tight comparison of step 1 is against the
+    # oracle on the HIP path's neighbour graphs, free-running step 1 gets the bound that
+    # test_second_step_spread_over_8_seeds gives its worst seed, and the golden the looser one.
+    # The oracle's two steps (losses, Adam updates, checksums) run on the HIP path's graphs of each step,
+    # all six lists of a step (_dgcnn_losses_on_graphs).
     p = O.as_params(O.fill_params({k: tuple(v.shape) for k, v in Net_MDA('DGCNN').state_dict().items()}, seed))
     names = list(p.keys())
     og = torch.optim.Adam([p[k] for k in names if k.startswith('g.') and p[k].requires_grad and 'pred_offset' not in k], lr=1e-3, weight_decay=5e-5)
@@ -46,19 +70,21 @@ def test_two_training_steps_match_reference():
     od = torch.optim.Adam([p[k] for k in names if k.startswith(('g.', 'attention')) and p[k].requires_grad], lr=1e-3, weight_decay=5e-5)
     torch.manual_seed(seed)
     ora = []
-    for _ in range(2):
-        lc, lg, ls = O.sug_losses(p, 'DGCNN', G['data'], G['label'], G['data_t'], G['label_t'],
-                                  methods['GEO_MMD'][0], methods['SEM_MMD'][0])
+    for i in range(2):
+        lc, lg, ls = _dgcnn_losses_on_graphs(p, G, methods, forced[i], B)
         (lc + lg + ls).backward()
         od.step(); og.step(); oc.step()
         for o in (og, oc, od):
             o.zero_grad()
         ora.append([lc.item(), lg.item(), ls.item()])
     print('losses gpu', got)
-    print('losses oracle(here)', ora)
+    print('losses oracle(here, on the HIP graphs)', ora)
     print('losses golden(reference, build container)', want)
+    print('free-running step 1 of the oracle', free)
     for a, b in zip(got[0], ora[0]):
         assert abs(a - b) <= 1e-4 * max(1.0, abs(b)), (got, ora)
+    for a, b in zip(got[0], free):
+        assert abs(a - b) <= 5e-3 * max(1.0, abs(b)), (got[0], free)
     # after one Adam update of every parameter: Adam turns rounding-level gradients into +-lr
     # moves and arg-max / kNN near-ties flip, so trajectories separate quickly -- the reference
     # itself gives 1.7815 (build container CPU) vs 1.7900 (this CPU) for this loss
@@ -87,6 +113,27 @@ def test_two_training_steps_match_reference():
             allow = 2e-3 * v.numel() + 2e-3 * pa
         assert abs(v.sum().item() - ps) <= allow, (k, v.sum().item(), ps, allow)
     print('worst checksum deviation / allowance vs oracle = %.3f' % worst)
+
+
+def _dgcnn_losses_on_graphs(p, G, methods, lists, B):
+    """oracle.sug_losses of the DGCNN step on the HIP path's neighbour graphs in all four passes: the paired semantic pass
+    made four kNN calls ([2B,N,k] lists 0..3), the node pass -- kNN + conv1 / conv2 prefix shared -- two more for conv3 and
+    conv4 (lists 4, 5: another FPS start, other features)."""
+    import torch.nn.functional as F
+    half = lambda l, d: l[d * B:(d + 1) * B]
+    sem_ko = lambda d: [half(l, d) for l in lists[:4]]
+    node_ko = lambda d: [half(lists[0], d), half(lists[1], d), half(lists[4], d), half(lists[5], d)]
+    geo, sem = methods['GEO_MMD'][0], methods['SEM_MMD'][0]
+    data, lab, data_t, lab_t = G['data'], G['label'], G['data_t'], G['label_t']
+    ps1, ps2, fs1, fs2 = O.net_mda(p, 'DGCNN', data, True, None, semantic_adaption=True, knn_override=sem_ko(0))
+    pt1, pt2, ft1, ft2 = O.net_mda(p, 'DGCNN', data_t, True, None, semantic_adaption=True, knn_override=sem_ko(1))
+    loss_cls = 0.5 * F.cross_entropy(ps1, lab) + 0.5 * F.cross_entropy(ps2, lab)
+    node_s = O.net_mda(p, 'DGCNN', data, True, None, node_adaptation_s=True, knn_override=node_ko(0))
+    node_t = O.net_mda(p, 'DGCNN', data_t, True, None, node_adaptation_t=True, knn_override=node_ko(1))
+    loss_geo = geo['GEO_SCALE'] * O.mmd_cal(lab, node_s, lab_t, node_t, geo, data, data_t)
+    l1 = sem['SEM_SCALE'] * O.mmd_cal(lab, fs1, lab_t, ft1, sem, ps1, pt1)
+    l2 = sem['SEM_SCALE'] * O.mmd_cal(lab, fs2, lab_t, ft2, sem, ps2, pt2)
+    return loss_cls, loss_geo, 0.5 * l1 + 0.5 * l2
 
 
 _STEP_METHODS = {'GEO_MMD': [{'NAME': 'SOFT_MMD', 'LABEL_SCALE': 50, 'GEO_SCALE': 1}],
@@ -393,23 +440,18 @@ def test_fp16_mode_weight_copies_follow_the_optimizer():
 def test_training_step_issues_no_device_memsets(model_name):
     """A replayed step graph must not contain memset nodes on this stack (they were not reliably
     ordered under replay -- garbage MMD values, NaN weights).  One step under the profiler: no memset on the device.
-    The profiled step runs in a child process (tests/memset_probe.py): the profiler's own teardown crashes the process now
-    and then on this stack (segmentation fault inside stop_trace), which must not take the test run down."""
+    The profiled step runs in a child process (tests/memset_probe.py): the profiler's own teardown crashed the process now
+    and then on this stack (segmentation fault inside stop_trace), which must not take the test run down.  The probe runs
+    once: a crashed probe is a failure to look into, never retried."""
     import json
     import subprocess
     import sys
     probe = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'memset_probe.py')
     cmd = [sys.executable, probe] + model_name.split('_')
-    res = None
-    for attempt in range(6):
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-        lines = [l for l in r.stdout.decode().splitlines() if l.startswith('PROBE ')]
-        if lines:
-            res = json.loads(lines[-1][6:])
-            break
-        assert r.returncode < 0, 'probe failed (rc %d): %s' % (r.returncode, r.stderr.decode()[-800:])     # killed by a signal: retry
-    if res is None:
-        pytest.skip('torch.profiler crashed the probe process six times in a row')
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith('PROBE ')]
+    assert lines, 'probe failed (rc %d): %s' % (r.returncode, r.stderr.decode()[-800:])
+    res = json.loads(lines[-1][6:])
     assert res['kernels'] > 0, 'the profiler saw no kernels'
     assert not res['memsets'], res['memsets']
 

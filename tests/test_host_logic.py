@@ -66,3 +66,29 @@ def test_call_graph_manager_is_not_copied_or_pickled_with_the_model():
     assert twin.__dict__.get('_call_graph_mgr') is None
     assert call_graphs.manager_for(twin) is not mgr
     assert pickle.loads(pickle.dumps(mgr)) is None
+
+
+def test_bench_dump_outputs_stays_under_64_mb_and_repeats(tmp_path):
+    """bench.py --dump-outputs: the losses and the updated model state as float32 / float64 .npy files, under 64 MB in all
+    even for the largest model state (the Point Transformer's is 77 MB in float32: sampled), the same files on a rerun."""
+    import os
+    import numpy as np
+    import bench
+    from sug_amd.model.Model import Net_MDA
+    torch.manual_seed(666)
+    net = Net_MDA('PTran')
+    losses = (torch.tensor(2.5), torch.tensor(0.125), None)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), losses, net)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b'))
+    assert 'loss_cls.npy' in names and 'loss_geo.npy' in names and 'loss_sem.npy' not in names
+    assert len(names) == 2 + len(net.state_dict())
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) < 64 * 10 ** 6
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype in (np.float32, np.float64), (n, x.dtype)
+        assert np.array_equal(x, y), n
+    assert float(np.load(tmp_path / 'a' / 'loss_cls.npy')) == 2.5
+    # a tensor of at most 4096 elements is written whole
+    assert np.array_equal(np.load(tmp_path / 'a' / 'state.g.fc1.0.bias.npy'), net.state_dict()['g.fc1.0.bias'].numpy())
