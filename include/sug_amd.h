@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate was added: a purely additive entry point, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -745,6 +745,35 @@ int sug_ce_pair_bwd(const float* logits1, const float* logits2, int64_t ld, cons
 int sug_loss_combine_fwd(const float* loss_cls, const float* v_geo, const float* v_sem1, const float* v_sem2, float wg, float ws,
                          float* out3, void* stream);
 int sug_loss_combine_bwd(const float* g, float wg, float ws, float* out4, void* stream);
+
+/* ---- evaluation metrics -----------------------------------------------------------------------------------
+ * One batch of eval_worker (utils/eval_utils.py:37-61) on the device, one launch, no host synchronisation (capturable).
+ * output = (logits1 + logits2) / 2 in fp32 (logits1 alone when logits2 is null), written to out [B, C] (dense) when out is
+ * given; pred[r] (int64, optional) = the index torch.max(output, 1) returns (first maximum; a row holding NaN: its first
+ * NaN).  The batch loss is the device scalar loss_in[0] (ce_mode 0: the caller's criterion) or nn.CrossEntropyLoss of
+ * output computed here (ce_mode 1: mean over the rows whose label != ignore_index, 2: sum; label_smoothing as torch;
+ * per-row terms in fp32, summed in fp64 in a fixed order, rounded to fp32).  The state block (int64 / fp64 words, zeroed
+ * by the caller before the first batch, SUG_EVAL_STATE_WORDS(cap) words) accumulates, in a fixed order by one thread:
+ * data_total += B, correct_total += correct rows, loss_total += (double)loss * B, the per-class totals of rows and correct
+ * rows, with cls_eval for every class c present in the batch class_acc[c] += {(double)correct_c / (double)rows_c, 1.0},
+ * batch_acc[batch_count++] = (double)correct / (double)B.  A label outside [0, C) sets bit 0 of the error word (the
+ * reference raises IndexError), a batch beyond `cap` bit 1.  logits* [B, C] fp32 with row stride ld, label int64 [B].
+ * B <= SUG_EVAL_MAX_ROWS, C <= SUG_EVAL_MAX_CLASSES. */
+#define SUG_EVAL_MAX_ROWS 4096
+#define SUG_EVAL_MAX_CLASSES 64
+#define SUG_EVAL_BATCH_COUNT 0        /* int64 */
+#define SUG_EVAL_DATA_TOTAL 1         /* int64 */
+#define SUG_EVAL_CORRECT_TOTAL 2      /* int64 */
+#define SUG_EVAL_ERROR 3              /* int64 */
+#define SUG_EVAL_LOSS_TOTAL 4         /* fp64 */
+#define SUG_EVAL_CLASS_ACC 8          /* fp64 [64][2]: sum of ratios, batches present */
+#define SUG_EVAL_CLASS_ROWS 136       /* int64 [64] */
+#define SUG_EVAL_CLASS_CORRECT 200    /* int64 [64] */
+#define SUG_EVAL_BATCH_ACC 264        /* fp64 [cap] */
+#define SUG_EVAL_STATE_WORDS(cap) (SUG_EVAL_BATCH_ACC + (cap))
+int sug_eval_accumulate(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int B, int C,
+                        const float* loss_in, int ce_mode, int64_t ignore_index, float label_smoothing, float* out,
+                        int64_t* pred, int cls_eval, void* state, int cap, void* stream);
 
 #ifdef __cplusplus
 }

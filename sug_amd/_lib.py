@@ -132,6 +132,7 @@ SIGNATURES = {
     'sug_ce_pair_bwd': [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp],
     'sug_loss_combine_fwd': [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp],
     'sug_loss_combine_bwd': [_vp, _f32, _f32, _vp, _vp],
+    'sug_eval_accumulate': [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _i32, _vp, _i32, _vp],
 }
 
 STATS_BLOCKS = 1024        # SUG_STATS_BLOCKS

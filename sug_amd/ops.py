@@ -2048,6 +2048,66 @@ def loss_combine(loss_cls, v_geo, v_sem1, v_sem2, wg, ws):
     return _LossCombine.apply(loss_cls, v_geo, v_sem1, v_sem2, wg, ws)
 
 
+# ----------------------------------------------------------------------------- evaluation metrics (sug_eval_accumulate)
+EVAL_MAX_ROWS, EVAL_MAX_CLASSES = 4096, 64              # SUG_EVAL_MAX_ROWS, SUG_EVAL_MAX_CLASSES
+EVAL_BATCH_COUNT, EVAL_DATA_TOTAL, EVAL_CORRECT_TOTAL, EVAL_ERROR, EVAL_LOSS_TOTAL = 0, 1, 2, 3, 4
+EVAL_CLASS_ACC, EVAL_CLASS_ROWS, EVAL_CLASS_CORRECT, EVAL_BATCH_ACC = 8, 136, 200, 264
+
+
+def eval_state(cap, device):
+    """A zeroed state block for `cap` batches (SUG_EVAL_STATE_WORDS(cap) int64 / fp64 words, held as int64)."""
+    return torch.zeros(EVAL_BATCH_ACC + int(cap), dtype=torch.int64, device=device)
+
+
+def eval_state_fields(state):
+    """The accumulators of a state block (on the host), as a dict of numpy values."""
+    s = state.cpu()
+    d = s.view(torch.float64).numpy()
+    i = s.numpy()
+    n = int(i[EVAL_BATCH_COUNT])
+    cap = s.numel() - EVAL_BATCH_ACC
+    return {'batch_count': n, 'data_total': int(i[EVAL_DATA_TOTAL]), 'correct_total': int(i[EVAL_CORRECT_TOTAL]),
+            'error': int(i[EVAL_ERROR]), 'loss_total': float(d[EVAL_LOSS_TOTAL]),
+            'class_acc': d[EVAL_CLASS_ACC:EVAL_CLASS_ACC + 2 * EVAL_MAX_CLASSES].reshape(EVAL_MAX_CLASSES, 2).copy(),
+            'class_rows': i[EVAL_CLASS_ROWS:EVAL_CLASS_ROWS + EVAL_MAX_CLASSES].copy(),
+            'class_correct': i[EVAL_CLASS_CORRECT:EVAL_CLASS_CORRECT + EVAL_MAX_CLASSES].copy(),
+            'batch_acc': d[EVAL_BATCH_ACC:EVAL_BATCH_ACC + min(n, cap)].copy()}
+
+
+def eval_accumulate_supported(logits, label):
+    return logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 \
+        and 1 <= logits.shape[0] <= EVAL_MAX_ROWS and 1 <= logits.shape[1] <= EVAL_MAX_CLASSES \
+        and label.is_cuda and label.dtype == torch.int64 and label.dim() == 1 and label.shape[0] == logits.shape[0]
+
+
+def eval_accumulate(state, logits1, label, logits2=None, loss=None, ce=None, out=None, pred=None, cls_eval=True):
+    """One evaluation batch into `state` (sug_eval_accumulate): output = (logits1 + logits2) / 2 (or logits1), its argmax,
+    and either the fused cross entropy `ce` = (reduction 'mean' | 'sum', ignore_index, label_smoothing) or the caller's loss
+    scalar `loss`.  out [B, C] / pred [B] int64: optional outputs.  No host synchronisation."""
+    _need_gpu(logits1, logits2, label, loss, out, pred, state)
+    B, C = logits1.shape
+    if logits2 is not None and (logits2.shape != logits1.shape or logits2.stride() != logits1.stride()):
+        raise RuntimeError('eval_accumulate: the two heads need the same shape and strides')
+    if out is not None and not (out.shape == (B, C) and out.is_contiguous() and out.dtype == torch.float32):
+        raise RuntimeError('eval_accumulate: out must be a dense fp32 [B, C] tensor')
+    if pred is not None and not (pred.shape == (B,) and pred.is_contiguous() and pred.dtype == torch.int64):
+        raise RuntimeError('eval_accumulate: pred must be a dense int64 [B] tensor')
+    if label.dtype != torch.int64 or not label.is_contiguous() or label.shape != (B,):
+        raise RuntimeError('eval_accumulate: label must be a dense int64 [B] tensor')
+    if ce is not None:
+        mode, ignore_index, smoothing = {'mean': 1, 'sum': 2}[ce[0]], int(ce[1]), float(ce[2])
+        lin = None
+    else:
+        if loss is None:
+            raise RuntimeError('eval_accumulate: give the batch loss or a fused cross entropy')
+        mode, ignore_index, smoothing = 0, -100, 0.0
+        lin = loss.detach().reshape(1).to(torch.float32)
+    cap = state.numel() - EVAL_BATCH_ACC
+    check(lib().sug_eval_accumulate(_p(logits1), _p(logits2), logits1.stride(0), _p(label), B, C, _p(lin), mode, ignore_index,
+                                    smoothing, _p(out), _p(pred), int(bool(cls_eval)), _p(state), cap, _st()),
+          'sug_eval_accumulate')
+
+
 class _SplitHalves(torch.autograd.Function):
     """The two domain halves of a paired [2B, ...] tensor as views.  Backward: when the two gradients are adjacent row
     blocks of one buffer (what mmd_assemble's and the paired kernels' backwards hand back) the pair's gradient is that
