@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate was added: a purely additive entry point, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate and the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd) were added: purely additive entry points, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -774,6 +774,52 @@ int sug_loss_combine_bwd(const float* g, float wg, float ws, float* out4, void* 
 int sug_eval_accumulate(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int B, int C,
                         const float* loss_in, int ce_mode, int64_t ignore_index, float label_smoothing, float* out,
                         int64_t* pred, int cls_eval, void* state, int cap, void* stream);
+
+
+/* ---- KPConv backbone (model/KPConv_model.py, model/KPConv_blocks.py; rigid kernel points, linear influence, sum) ----
+ * Clouds are packed: level points [sum N_b, 3] with device offsets off[B+1] (int32).  A neighbour table [Nq, H] holds
+ * global support indices, a missing slot the shadow index Ns.  No float atomics: every sum has one fixed order.
+ *
+ * sug_grid_subsample: per cloud, the voxels floor(p / dl) (fp32 true division) in order of their first point, each the
+ * fp32 point-order sum of its points divided once by the count.  out_pad [B, cap, 3] and cnt [B] are scratch / counts,
+ * out [<= sum N_b, 3] the packed result with offsets out_off [B+1].  cap >= every input cloud's length,
+ * cap <= SUG_KPCONV_MAX_CLOUD. */
+#define SUG_KPCONV_MAX_CLOUD 4096
+int sug_grid_subsample(const float* pts, const int32_t* off, int B, int cap, float dl, float* out_pad, int32_t* cnt,
+                       float* out, int32_t* out_off, void* stream);
+/* out [Nq, limit]: per query the first `limit` supports of its cloud, in support order, with d^2 < radius^2
+ * (d^2 = (s-q)_x^2 + (s-q)_y^2 + (s-q)_z^2 in fp32, left to right); the rest Ns.  limit <= 64. */
+int sug_radius_neighbors(const float* q, const int32_t* qoff, int Nq, const float* s, const int32_t* soff, int Ns, int B,
+                         float radius, int limit, int32_t* out, void* stream);
+/* Reverse lists of a neighbour table: the entries e = q*H + h naming support s, ascending, are
+ * rev_ent[rev_be[2s] .. rev_be[2s+1]); rev_ent [Nq*H] (cloud b's lists lie in [qoff[b]*H, qoff[b+1]*H)), rev_be [Ns, 2].
+ * Shadow slots appear in no list.  cap >= every cloud's support count, <= SUG_KPCONV_MAX_CLOUD. */
+int sug_radius_reverse(const int32_t* nbr, const int32_t* qoff, const int32_t* soff, int B, int H, int Ns, int cap,
+                       int32_t* rev_be, int32_t* rev_ent, void* stream);
+/* wf [Nq, K*Cin] = (sum_h w[q,k,h] x[s_h, :]) / cnt[q] with w = max(0, 1 - |(s_h - q) - kp_k| / extent) (shadow: 0) and
+ * cnt = max(1, #{h : sum_c x[s_h, c] > 0}); the layer output is wf . W viewed as [K*Cin, Cout].  Also written for the
+ * backward: w [Nq, H, K], cnt [Nq] (fp32).  H <= 64, K <= 16. */
+int sug_kpconv_fwd(const float* q, const float* s, const int32_t* nbr, int Nq, int H, int Ns, const float* kp, int K,
+                   float extent, const float* x, int Cin, float* wf, float* w, float* cnt, void* stream);
+/* dx [Ns, Cin] = sum over the reverse entries (q, h) of s, ascending, of (sum_k w[q,h,k] dwf[q,k,:]) / cnt[q] */
+int sug_kpconv_bwd(const int32_t* rev_be, const int32_t* rev_ent, int H, int K, const float* w, const float* cnt,
+                   const float* dwf, int Ns, int Cin, float* dx, void* stream);
+/* Per-cloud InstanceNorm1d (biased variance, no affine) over the rows of each cloud, x / y [N, C]; mode 0: plain,
+ * 1: LeakyReLU(0.1) after it, 2: LeakyReLU(0.1)(norm + sc).  mean / rstd [B, C] are kept for the backward, which
+ * writes dx and, in mode 2, dsc (the gradient of sc). */
+int sug_seg_instnorm_fwd(const float* x, const int32_t* off, int B, int C, float eps, int mode, const float* sc, float* y,
+                         float* mean, float* rstd, void* stream);
+int sug_seg_instnorm_bwd(const float* g, const float* y, const float* x, const float* mean, const float* rstd,
+                         const int32_t* off, int B, int C, int mode, float* dx, float* dsc, void* stream);
+/* y [Nq, C] = max over the H slots of x[slot] (a shadow slot reads 0), arg = the first slot h holding it; the backward
+ * routes g[q, c] to the support of slot arg[q, c] through the reverse lists (a shadow winner: nowhere). */
+int sug_seg_max_pool_fwd(const float* x, const int32_t* nbr, int Nq, int H, int Ns, int C, float* y, int32_t* arg,
+                         void* stream);
+int sug_seg_max_pool_bwd(const float* g, const int32_t* arg, const int32_t* rev_be, const int32_t* rev_ent, int H, int Ns,
+                         int C, float* dx, void* stream);
+/* y [B, C] = per-cloud mean of x [N, C]; dx [N, C] = g[b] / N_b */
+int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C, float* y, void* stream);
+int sug_seg_mean_bwd(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,17 @@ SIGNATURES = {
     'sug_loss_combine_fwd': [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp],
     'sug_loss_combine_bwd': [_vp, _f32, _f32, _vp, _vp],
     'sug_eval_accumulate': [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _i32, _vp, _i32, _vp],
+    'sug_grid_subsample': [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp],
+    'sug_radius_neighbors': [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp],
+    'sug_radius_reverse': [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    'sug_kpconv_fwd': [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp],
+    'sug_kpconv_bwd': [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    'sug_seg_instnorm_fwd': [_vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    'sug_seg_instnorm_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    'sug_seg_max_pool_fwd': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    'sug_seg_max_pool_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    'sug_seg_mean_fwd': [_vp, _vp, _i32, _i32, _vp, _vp],
+    'sug_seg_mean_bwd': [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
 }
 
 STATS_BLOCKS = 1024        # SUG_STATS_BLOCKS

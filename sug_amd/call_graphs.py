@@ -419,8 +419,9 @@ class CallGraphs:
 
 
 def manager_for(model):
-    """The model's call-graph manager (created on first use), or None when call graphs are switched off."""
-    if not ENABLED:
+    """The model's call-graph manager (created on first use), or None when call graphs are switched off or the encoder's
+    sizes depend on the data (KPConv_g: graph_capturable = False), so that the call runs eagerly."""
+    if not ENABLED or not getattr(getattr(model, 'g', None), 'graph_capturable', True):
         return None
     mgr = model.__dict__.get('_call_graph_mgr')
     if mgr is None:

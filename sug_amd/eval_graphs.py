@@ -61,6 +61,8 @@ def fallback_reason(model, x):
     """Why a call cannot go through a runner (None: it can)."""
     if not isinstance(model, _known_types()):
         return 'module %s' % type(model).__name__
+    if not getattr(getattr(model, 'g', None), 'graph_capturable', True):
+        return 'KPConv: level sizes depend on the data'
     if any(m.training for m in model.modules()):
         return 'train mode'
     if not (ops.CTX.bn_groups == 1 and ops.CTX.start_queue is None and ops.CTX.geometry_plan is None and

@@ -1,0 +1,235 @@
+"""KPConv encoder, preprocessing and classifier (mirror of the reference's model/KPConv_model.py).
+
+PreprocessorGPU builds the whole pyramid on the device -- grid subsampling (sug_grid_subsample), radius neighbours,
+pools and upsamples (sug_radius_neighbors) and the reverse lists the backward passes scatter through
+(sug_radius_reverse) -- with ONE host synchronisation per forward: the copy of all level lengths, which the packed
+sizes need.  The two third-party operations of the reference (MinkowskiEngine's quantisation, pytorch3d's ball_query)
+are restated under documented assumptions:
+  * radius query: per query, the first `limit` supports of its cloud in index order with d^2 < r^2, d^2 in fp32 as
+    (s - q) per axis, summed x, y, z; r^2 = fp32(r) * fp32(r); missing slots hold the shadow index (total supports);
+  * grid subsample: key = floor(fp32(p) / fp32(dl)) per axis (true division), voxels per cloud in order of their first
+    point (MinkowskiEngine's own order is a hash order), the voxel point = fp32 sum in point order / count.
+"""
+from typing import List
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .KPConv_blocks import block_decider, global_average, UnaryBlock
+
+
+class _Config(dict):
+    """Attribute access over a dict (the reference's EasyDict)."""
+    __getattr__ = dict.__getitem__
+
+    def __setattr__(self, k, v):
+        self[k] = v
+
+
+KPConvConfig = _Config()
+KPConvConfig["num_class"] = 10
+KPConvConfig["first_subsampling_dl"] = 0.02
+KPConvConfig["conv_radius"] = 2.5
+KPConvConfig["deform_radius"] = 6.0
+KPConvConfig["d_bottle"] = 256
+KPConvConfig["in_feats_dim"] = 1
+KPConvConfig["KP_extent"] = 1.2
+KPConvConfig["KP_influence"] = "linear"
+KPConvConfig["overlap_radius"] = 0.04
+KPConvConfig["use_batch_norm"] = True
+KPConvConfig["batch_norm_momentum"] = 0.02
+KPConvConfig["modulated"] = False
+KPConvConfig["num_kernel_points"] = 15
+KPConvConfig["first_feats_dim"] = 64
+KPConvConfig["fixed_kernel_points"] = "center"
+KPConvConfig["neighborhood_limits"] = [50, 50, 50, 50, 50]
+KPConvConfig["aggregation_mode"] = "sum"
+KPConvConfig["in_points_dim"] = 3
+KPConvConfig["num_layers"] = 5
+KPConvConfig["architecture"] = ['simple', 'resnetb', 'resnetb_strided', 'resnetb', 'resnetb', 'resnetb_strided', 'resnetb',
+                                'resnetb', 'resnetb_strided', 'resnetb', 'resnetb', 'resnetb_strided', 'resnetb', 'resnetb']
+KPConvConfig["deform_fitting_power"] = 1.0
+
+
+def _layer_plan(config):
+    """[(radius, pooled at the end)] per level, as the reference's preprocessing loop walks the architecture."""
+    for block in config.architecture:
+        if 'upsample' in block or 'deform' in block:
+            raise NotImplementedError('KPConv preprocessing: %r blocks are not built (no decoder, rigid kernels only)'
+                                      % block)
+    plan, r, blocks = [], config.first_subsampling_dl * config.conv_radius, []
+    arch = config.architecture
+    for i, block in enumerate(arch):
+        if 'global' in block:
+            break
+        if not ('pool' in block or 'strided' in block):
+            blocks.append(block)
+            if i < len(arch) - 1:
+                continue
+        plan.append((r, 'pool' in block or 'strided' in block))
+        r *= 2
+        blocks = []
+    return plan
+
+
+class PreprocessorGPU(nn.Module):
+    """Computes the metadata used for KPConv on the device (deterministic: voxels in first-point order)."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+
+    def forward(self, pts: List[torch.Tensor]):
+        """pts: list of point clouds XYZ [Ni, 3] (fp32, HIP device)."""
+        return self.forward_packed(torch.cat([p.float() for p in pts], 0).contiguous(), [int(p.shape[0]) for p in pts])
+
+    def forward_packed(self, points, lengths):
+        """points [sum Ni, 3] packed on the device, lengths: host ints."""
+        ops._need_gpu(points)
+        config = self.cfg
+        plan = _layer_plan(config)
+        limits = config.neighborhood_limits
+        dev = points.device
+        B = len(lengths)
+        cap = max(lengths)
+        if cap > 4096:
+            raise NotImplementedError('KPConv preprocessing: clouds of at most 4096 points (got %d)' % cap)
+        off0 = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int32).to(dev, non_blocking=True)
+        bufs, offs = [points], [off0]
+        for li, (r, pooled) in enumerate(plan):
+            if not pooled:
+                break
+            dl = 2 * r / config.conv_radius
+            p, o = ops.kp_grid_subsample(bufs[-1], offs[-1], B, cap, dl)
+            bufs.append(p)
+            offs.append(o)
+        # the one synchronisation of the forward: every level's offsets
+        off_host = torch.stack(offs).cpu().numpy().astype(np.int64)
+        lens = [np.diff(o) for o in off_host]
+        pts = [b[:int(o[-1])] for b, o in zip(bufs, off_host)]
+        neighbors, pools, upsamples, rev_n, rev_p = [], [], [], [], []
+        for li, (r, pooled) in enumerate(plan):
+            Ns, capl = pts[li].shape[0], int(lens[li].max())
+            nb = ops.radius_neighbors(pts[li], offs[li], pts[li], offs[li], r, limits[li])
+            neighbors.append(nb)
+            rev_n.append(ops.radius_reverse(nb, offs[li], offs[li], Ns, capl))
+            if pooled:
+                pl = ops.radius_neighbors(pts[li + 1], offs[li + 1], pts[li], offs[li], r, limits[li])
+                pools.append(pl)
+                rev_p.append(ops.radius_reverse(pl, offs[li + 1], offs[li], Ns, capl))
+                upsamples.append(ops.radius_neighbors(pts[li], offs[li], pts[li + 1], offs[li + 1], 2 * r, limits[li]))
+            else:
+                empty = torch.zeros((0, 1), dtype=torch.int32, device=dev)
+                pools.append(empty)
+                upsamples.append(empty)
+                rev_p.append(None)
+        stack = torch.tensor(np.stack(lens), dtype=torch.int64).to(dev, non_blocking=True)
+        return {
+            'points': pts,
+            'neighbors': neighbors,
+            'pools': pools,
+            'upsamples': upsamples,
+            'stack_lengths': list(stack.unbind(0)),
+            # this build's additions: device offsets, reverse lists, host lengths
+            'offsets': offs,
+            'rev_neighbors': rev_n,
+            'rev_pools': rev_p,
+            'lengths': [list(map(int, x)) for x in lens],
+        }
+
+
+class KPFEncoder(nn.Module):
+    def __init__(self, config, increase_channel_when_downsample=True):
+        super().__init__()
+        octave = 0
+        r = config.first_subsampling_dl * config.conv_radius
+        in_dim = config.in_feats_dim
+        out_dim = config.first_feats_dim
+        self.encoder_blocks = nn.ModuleList()
+        self.encoder_skip_dims = []
+        self.encoder_skips = []
+        for block_i, block in enumerate(config.architecture):
+            if ('equivariant' in block) and (not out_dim % 3 == 0):
+                raise ValueError('Equivariant block but features dimension is not a factor of 3')
+            if np.any([tmp in block for tmp in ['pool', 'strided', 'upsample', 'global']]):
+                self.encoder_skips.append(block_i)
+                self.encoder_skip_dims.append(in_dim)
+            if 'upsample' in block:
+                break
+            self.encoder_blocks.append(block_decider(block, r, in_dim, out_dim, octave, config))
+            in_dim = out_dim // 2 if 'simple' in block else out_dim
+            if 'pool' in block or 'strided' in block:
+                octave += 1
+                r *= 2
+                if increase_channel_when_downsample:
+                    out_dim *= 2
+        if 'upsample' not in block:
+            self.encoder_skips.append(block_i)
+            self.encoder_skip_dims.append(in_dim)
+        self.layer_idx = octave
+
+    def forward(self, x, batch):
+        """(x, skip_x, mid_fea): mid_fea = the output of block 2, detached (as the reference)."""
+        skip_x = []
+        mid_fea = None
+        for block_i, block_op in enumerate(self.encoder_blocks):
+            if block_i in self.encoder_skips:
+                skip_x.append(x)
+            x = block_op(x, batch)
+            if block_i == 2:
+                mid_fea = x.detach()
+        return x, skip_x, mid_fea
+
+
+class GlobalAverageBlock(nn.Module):
+
+    def __init__(self):
+        super(GlobalAverageBlock, self).__init__()
+
+    def forward(self, x, len):
+        """len: the last level's device offsets [B+1] (int32) in this build (the reference: stack lengths)."""
+        return global_average(x, len)
+
+
+def _split_clouds(x):
+    """[B,3,N,1] clouds -> (packed points [B*N, 3], host lengths)."""
+    B, N = x.shape[0], x.shape[2]
+    pts = x.squeeze(-1).permute(0, 2, 1)[:, :, :3].reshape(B * N, 3).contiguous()
+    return pts, [N] * B
+
+
+class KPFCls(nn.Module):
+    """model/KPConv_model.py:60-90.  B = 1 works here (the reference builds an empty cloud list for it)."""
+
+    def __init__(self, config=None, increase_channel_when_downsample=True):
+        super().__init__()
+        self.config = KPConvConfig if config is None else config
+        self.preprocessor = PreprocessorGPU(self.config)
+        self.encoder = KPFEncoder(self.config)
+        self.global_avg_pooling = GlobalAverageBlock()
+        self.fc = nn.Sequential(nn.Linear(1024, 256), nn.ReLU(), nn.Linear(256, 64), nn.ReLU(),
+                                nn.Linear(64, self.config.num_class))
+        self.deform_fitting_power = self.config.deform_fitting_power
+
+    def forward(self, x):
+        pts, lengths = _split_clouds(x)
+        kpconv_meta = self.preprocessor.forward_packed(pts, lengths)
+        feats0 = kpconv_meta["points"][0][:, 0:1]
+        feats = self.encoder(feats0, kpconv_meta)
+        feats_avg = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1])
+        return self.fc(feats_avg)
+
+
+def p2p_fitting_regularizer(net, deform_fitting_power=1):
+    """model/KPConv_model.py:282-315: the deformable kernels' fitting and repulsion terms -- 0 for rigid kernels, the
+    only ones built."""
+    for m in net:
+        if hasattr(m, "KPConv") and m.KPConv.deformable:
+            raise NotImplementedError('p2p_fitting_regularizer: deformable KPConv is not built')
+    return 0
+
+
+__all__ = ['KPConvConfig', 'PreprocessorGPU', 'KPFEncoder', 'GlobalAverageBlock', 'KPFCls', 'p2p_fitting_regularizer',
+           'UnaryBlock']

@@ -5,7 +5,8 @@ sub-module names (`g`, `c1`, `c2`, `attention_s`, `attention_t`) and every param
 match the reference, so `train_dg_single_gpu.py`-style drivers and reference checkpoints
 work unchanged.  Inside, the encoders run on point-major rows [B,N,C] and call the HIP
 kernels (sug_amd.ops); inputs and outputs keep the reference layout ([B,3,N,1] in,
-[B,1024] / [B,64,64,1] out).  KPConv / PointNet++-MSG are out of scope.
+[B,1024] / [B,64,64,1] out).  KPConv: the rigid / linear / sum path (KPConv_g, KPConv_c).
+PointNet++-MSG is out of scope.
 """
 import weakref
 
@@ -528,6 +529,57 @@ class Pointnet_c(nn.Module):
         return x
 
 
+class KPConv_g(nn.Module):
+    """model/Model.py:349-386: the KPConv encoder -- device-side preprocessing, 14 blocks on 5 levels, the per-cloud mean
+    of the last level [B, 1024] and the node features [B, 64, 64] (64 rows per cloud of block 2's output, detached as in
+    the reference).  The level sizes depend on the data, so this encoder runs eagerly (no per-call graph replay)."""
+    graph_capturable = False
+
+    def __init__(self, config=None):
+        super(KPConv_g, self).__init__()
+        from .KPConv_model import KPFEncoder, PreprocessorGPU, GlobalAverageBlock, KPConvConfig
+        from .KPConv_blocks import sample_tensor_slices
+        self.config = KPConvConfig if config is None else config
+        self.sample_tensor_slices = sample_tensor_slices
+        self.preprocessor = PreprocessorGPU(self.config)
+        self.encoder = KPFEncoder(self.config)
+        self.global_avg_pooling = GlobalAverageBlock()
+        self.deform_fitting_power = self.config.deform_fitting_power
+
+    def forward(self, x, node=False, feat_grad=True):
+        """x [B,3,N,1].  B = 1 is accepted (the reference's `if x.shape[0] > 1` leaves it an empty cloud list)."""
+        from .KPConv_model import _split_clouds
+        pts, lengths = _split_clouds(x)
+        kpconv_meta = self.preprocessor.forward_packed(pts, lengths)
+        feats0 = kpconv_meta["points"][0][:, 0:1]
+        feats = self.encoder(feats0, kpconv_meta)
+        nodes = self.sample_tensor_slices(feats[2], kpconv_meta["lengths"][1])
+        feats = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1])
+        if node:
+            return feats, nodes, None
+        return feats, nodes
+
+
+class KPConv_c(nn.Module):
+    """model/Model.py:389-409: Linear 1024->256, ReLU, 256->64, ReLU, 64->num_class; the semantic feature is the
+    pre-ReLU mlp1 output."""
+
+    def __init__(self, num_class=10, dgcnn_flag=False, PTran_flag=False):
+        super(KPConv_c, self).__init__()
+        self.mlp1 = nn.Linear(1024, 256)
+        self.mlp2 = nn.Linear(256, 64)
+        self.mlp3 = nn.Linear(64, num_class)
+        self.act = nn.ReLU()
+
+    def forward(self, x, adapt=False):
+        x = self.mlp1(x)
+        mid_feature = x
+        x = self.mlp3(self.act(self.mlp2(self.act(x))))
+        if adapt:
+            return x, mid_feature
+        return x
+
+
 def _check_input(x):
     """The GPU-only contract at the model boundary: the encoders are HIP kernels behind a C ABI,
     there is no CPU or 16-bit-input path -- fail here with a clear message instead of deep inside an op."""
@@ -540,7 +592,7 @@ def _check_input(x):
 
 
 class Net_MDA(nn.Module):
-    """model/Model.py:452-520.  model_name in {'Pointnet', 'Pointnet2', 'DGCNN', 'PTran'}."""
+    """model/Model.py:452-520.  model_name in {'Pointnet', 'Pointnet2', 'DGCNN', 'PTran', 'KPConv'}."""
 
     def __init__(self, model_name='Pointnet'):
         super(Net_MDA, self).__init__()
@@ -556,12 +608,19 @@ class Net_MDA(nn.Module):
         elif model_name == 'PTran':
             self.g = PTran_g()
             self.PTran_flag = True
+        elif model_name == 'KPConv':
+            from .KPConv_model import KPConvConfig
+            self.g = KPConv_g(config=KPConvConfig)
         else:
             raise NotImplementedError("Unsupported model name")
         self.attention_s = CALayer(64 * 64)
         self.attention_t = CALayer(64 * 64)
-        self.c1 = Pointnet_c(dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
-        self.c2 = Pointnet_c(dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
+        if model_name == 'KPConv':
+            self.c1 = KPConv_c()
+            self.c2 = KPConv_c()
+        else:
+            self.c1 = Pointnet_c(dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
+            self.c2 = Pointnet_c(dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
 
     # `forward(..., semantic_adaption=True, node_adaptation_s=True)` (or node_adaptation_t) is the opt-in
     # single-pass dual-output call: ONE encoder evaluation feeds the two heads AND the attention layer.  The reference
@@ -690,7 +749,7 @@ class Net_MDA(nn.Module):
     def _heads(self, x):
         """[(logits, mid feature)] of c1 and c2 on the pooled feature x: one launch per layer for both heads
         (ops.heads_fused, sug_head_linear_*) where the shapes allow, the module path otherwise."""
-        if ops.heads_fused_supported((self.c1, self.c2), x):
+        if isinstance(self.c1, Pointnet_c) and ops.heads_fused_supported((self.c1, self.c2), x):
             return ops.heads_fused((self.c1, self.c2), x)
         return ops.run_parallel([lambda: self.c1(x, adapt=True), lambda: self.c2(x, adapt=True)])
 

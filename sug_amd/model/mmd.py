@@ -17,7 +17,9 @@ sigma_list = [0.01, 0.1, 1, 10, 100]
 
 def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=None, KPC=False, sample_weights=None):
     """model/mmd.py:25-41.  `sample_weights` (not in the reference signature): SDA weights the caller
-    already has (the batch-sharded step computes them once from the gathered batch)."""
+    already has (the batch-sharded step computes them once from the gathered batch).  KPC=True (the KPConv
+    backbone's call) uses the same Chamfer weights as KPC=False: the reference's KPC branch (model/mmd.py:122-124)
+    only calls the unpinned third-party Chamfer op another way."""
     sample_weights_flag = args.get("GEO_WEIGHTS", None) or args.get("SEM_WEIGHTS", None)
     if sample_weights is None and data_s is not None and sample_weights_flag:
         sample_weights = cal_sample_weights(data_s, data_t, args, label_s=label_s, label_t=label_t)

@@ -2696,6 +2696,178 @@ def chamfer_weights(a, b, method):
 
 
 # ----------------------------------------------------------------------------- the old module-level names of the context fields
+# ----------------------------------------------------------------------------- KPConv backbone
+# Packed clouds (rows of all clouds of a level back to back) with int32 device offsets off [B+1]; neighbour tables
+# [Nq, H] int32 whose missing slots hold the shadow index Ns (sug_amd/csrc/kpconv.hip).
+def kp_grid_subsample(pts, off, B, cap, dl):
+    """Grid subsample of packed clouds pts [N,3] (offsets off, every cloud <= cap points) -> (packed voxel points
+    [N,3] of which the first sum-of-counts rows are valid, their offsets [B+1]); nothing is synchronised."""
+    _need_gpu(pts, off)
+    pts = pts.detach().contiguous()
+    pad = torch.empty(B, cap, 3, dtype=torch.float32, device=pts.device)
+    cnt = torch.empty(B, dtype=torch.int32, device=pts.device)
+    out = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=pts.device)
+    out_off = torch.empty(B + 1, dtype=torch.int32, device=pts.device)
+    check(lib().sug_grid_subsample(_p(pts), _p(off), B, cap, float(dl), _p(pad), _p(cnt), _p(out), _p(out_off), _st()),
+          'sug_grid_subsample')
+    return out, out_off
+
+
+def radius_neighbors(q, qoff, s, soff, radius, limit):
+    """[Nq, limit] int32: per query the first `limit` supports of its cloud (support order) with d^2 < r^2, shadow Ns."""
+    _need_gpu(q, qoff, s, soff)
+    q, s = q.detach().contiguous(), s.detach().contiguous()
+    out = torch.empty(q.shape[0], limit, dtype=torch.int32, device=q.device)
+    check(lib().sug_radius_neighbors(_p(q), _p(qoff), q.shape[0], _p(s), _p(soff), s.shape[0], qoff.numel() - 1,
+                                     float(radius), limit, _p(out), _st()), 'sug_radius_neighbors')
+    return out
+
+
+def radius_reverse(nbr, qoff, soff, Ns, cap):
+    """Sorted reverse lists of a neighbour table: (rev_be [Ns,2], rev_ent [Nq*H])."""
+    _need_gpu(nbr, qoff, soff)
+    Nq, H = nbr.shape
+    be = torch.empty(Ns, 2, dtype=torch.int32, device=nbr.device)
+    ent = torch.empty(max(1, Nq * H), dtype=torch.int32, device=nbr.device)
+    check(lib().sug_radius_reverse(_p(nbr), _p(qoff), _p(soff), qoff.numel() - 1, H, Ns, cap, _p(be), _p(ent), _st()),
+          'sug_radius_reverse')
+    return be, ent
+
+
+class _KPConvAgg(torch.autograd.Function):
+    """wf [Nq, K*Cin]: the influence-weighted neighbour features of every kernel point, divided by the positive-row count
+    (sug_kpconv_fwd); backward dx through the support's reverse lists (sug_kpconv_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, q, s, nbr, kp, extent, rev):
+        _need_gpu(x, q, s, nbr, kp)
+        x = x.contiguous()
+        Nq, H = nbr.shape
+        K, Cin = kp.shape[0], x.shape[1]
+        wf = torch.empty(Nq, K * Cin, dtype=torch.float32, device=x.device)
+        w = torch.empty(Nq, H, K, dtype=torch.float32, device=x.device)
+        cnt = torch.empty(Nq, dtype=torch.float32, device=x.device)
+        check(_timed('kpconv_fwd', {'Nq': Nq, 'Cin': Cin},
+                     lambda: lib().sug_kpconv_fwd(_p(q), _p(s), _p(nbr), Nq, H, s.shape[0], _p(kp.detach().contiguous()),
+                                                  K, float(extent), _p(x), Cin, _p(wf), _p(w), _p(cnt), _st())),
+              'sug_kpconv_fwd')
+        ctx.save_for_backward(w, cnt)
+        ctx.rev, ctx.dims = rev, (H, K, s.shape[0], Cin)
+        return wf
+
+    @staticmethod
+    def backward(ctx, g):
+        w, cnt = ctx.saved_tensors
+        H, K, Ns, Cin = ctx.dims
+        g = g.contiguous()
+        dx = torch.empty(Ns, Cin, dtype=torch.float32, device=g.device)
+        be, ent = ctx.rev
+        check(_timed('kpconv_bwd', {'Ns': Ns, 'Cin': Cin},
+                     lambda: lib().sug_kpconv_bwd(_p(be), _p(ent), H, K, _p(w), _p(cnt), _p(g), Ns, Cin, _p(dx), _st())),
+              'sug_kpconv_bwd')
+        return dx, None, None, None, None, None, None
+
+
+def kpconv(x, q, s, nbr, rev, kernel_points, weights, extent):
+    """KPConv (rigid, linear influence, sum): [Nq, Cout] = (wf / count) . W with W [K, Cin, Cout] viewed as [K*Cin, Cout];
+    rev = radius_reverse(nbr, ...)."""
+    _need_gpu(x, q, s, nbr, kernel_points, weights)
+    K, Cin, Cout = weights.shape
+    wf = _KPConvAgg.apply(x, q, s, nbr, kernel_points, extent, rev)
+    return linear_rows(wf, weights.view(K * Cin, Cout).t())
+
+
+class _SegInstNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, off, mode, sc):
+        _need_gpu(x, off, sc)
+        x = x.contiguous()
+        B, C = off.numel() - 1, x.shape[1]
+        y = torch.empty_like(x)
+        mean = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        scc = sc.contiguous() if sc is not None else None
+        check(lib().sug_seg_instnorm_fwd(_p(x), _p(off), B, C, 1e-5, mode, _p(scc), _p(y), _p(mean), _p(rstd), _st()),
+              'sug_seg_instnorm_fwd')
+        ctx.save_for_backward(x, y, mean, rstd, off)
+        ctx.mode = mode
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, mean, rstd, off = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        dsc = torch.empty_like(x) if ctx.mode == 2 else None
+        check(lib().sug_seg_instnorm_bwd(_p(g), _p(y), _p(x), _p(mean), _p(rstd), _p(off), off.numel() - 1, x.shape[1],
+                                         ctx.mode, _p(dx), _p(dsc), _st()), 'sug_seg_instnorm_bwd')
+        return dx, None, None, dsc
+
+
+def seg_instnorm(x, off, act=False, shortcut=None):
+    """Per-cloud InstanceNorm1d of rows x [N, C] (clouds at offsets off), then LeakyReLU(0.1) if act; with a shortcut
+    [N, C]: LeakyReLU(0.1)(norm(x) + shortcut)."""
+    mode = 2 if shortcut is not None else (1 if act else 0)
+    return _SegInstNorm.apply(x, off, mode, shortcut)
+
+
+class _SegMaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, nbr, rev):
+        _need_gpu(x, nbr)
+        x = x.contiguous()
+        Nq, H = nbr.shape
+        Ns, C = x.shape
+        y = torch.empty(Nq, C, dtype=torch.float32, device=x.device)
+        arg = torch.empty(Nq, C, dtype=torch.int32, device=x.device)
+        check(lib().sug_seg_max_pool_fwd(_p(x), _p(nbr), Nq, H, Ns, C, _p(y), _p(arg), _st()), 'sug_seg_max_pool_fwd')
+        ctx.save_for_backward(arg)
+        ctx.rev, ctx.dims = rev, (H, Ns, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        H, Ns, C = ctx.dims
+        g = g.contiguous()
+        dx = torch.empty(Ns, C, dtype=torch.float32, device=g.device)
+        be, ent = ctx.rev
+        check(lib().sug_seg_max_pool_bwd(_p(g), _p(arg), _p(be), _p(ent), H, Ns, C, _p(dx), _st()), 'sug_seg_max_pool_bwd')
+        return dx, None, None
+
+
+def seg_max_pool(x, nbr, rev):
+    """[Nq, C]: max over each query's slots of x rows, a shadow slot reading 0 (model/KPConv_blocks.py max_pool)."""
+    return _SegMaxPool.apply(x, nbr, rev)
+
+
+class _SegMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, off):
+        _need_gpu(x, off)
+        x = x.contiguous()
+        B, C = off.numel() - 1, x.shape[1]
+        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        check(lib().sug_seg_mean_fwd(_p(x), _p(off), B, C, _p(y), _st()), 'sug_seg_mean_fwd')
+        ctx.save_for_backward(off)
+        ctx.N = x.shape[0]
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (off,) = ctx.saved_tensors
+        g = g.contiguous()
+        B, C = g.shape
+        dx = torch.empty(ctx.N, C, dtype=torch.float32, device=g.device)
+        check(lib().sug_seg_mean_bwd(_p(g), _p(off), B, ctx.N, C, _p(dx), _st()), 'sug_seg_mean_bwd')
+        return dx, None
+
+
+def seg_mean(x, off):
+    """[B, C]: per-cloud mean of the rows x [N, C] (model/KPConv_model.py global_average)."""
+    return _SegMean.apply(x, off)
+
+
 def _ctx_property(field):
     return property(lambda self: getattr(CTX, field), lambda self, v: setattr(CTX, field, v))
 

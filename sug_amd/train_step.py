@@ -198,6 +198,10 @@ class SUGStep:
     def __init__(self, model, lr=1e-3, weight_decay=5e-5, lr_scaler=1.0, methods=None, criterion=None,
                  global_mmd=True, fused_adam=None, share_prefix=True, use_graph=False, pair_domains=True,
                  force_segmented=False, single_pass=False):
+        if not getattr(getattr(model, 'g', None), 'graph_capturable', True):
+            raise NotImplementedError('SUGStep: the KPConv backbone is not supported (its level sizes depend on the data); '
+                                      'train it with the eager four-call form -- model(...) per loss term, as '
+                                      'train_dg_single_gpu.py does -- which Net_MDA(\'KPConv\') supports')
         self.model = model
         # ONE encoder evaluation per domain feeds the heads and the attention layers, instead of the
         # semantic + node pass of train_dg_single_gpu.py:260-264, :309-310.  Same losses and gradients as the two-pass step
