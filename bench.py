@@ -13,9 +13,14 @@ of timed steps, `ms_per_step` the wall time of one of them; --dump-outputs DIR w
 last timed step computed as .npy files (inputs and initial weights are seeded: the same
 arguments give the same inputs on every run).
 
-`roofline` describes the dominant hand-written kernel of the step, timed live with events
-on the stream it is launched on; `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py,
-the restatement of the reference's algorithm) on a bounded sample of the same workload.
+A plain run does only that: set up, warm up, time the steps, dump, print.  Everything else
+the benchmark measures runs after the timed steps with --full only: `roofline` describes the
+dominant hand-written kernel of the step, timed live with events on the stream it is launched
+on; `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py, the restatement of the reference's
+algorithm) on a bounded sample of the same workload; eager, unchanged-caller and single-pass
+step times, the other BASELINE configurations, the one-rank RCCL rehearsal and per-collective
+times fill in `config`.  Without --full those fields are null (`roofline` and `kernels` hold
+what the timed steps themselves recorded: nothing in graph mode).
 """
 import argparse
 import gc
@@ -206,7 +211,7 @@ def segmented_rehearsal(args):
     (link time comes on top on a real node)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--segmented', '--model', args.model, '--batch', str(args.batch),
-           '--npoints', str(args.npoints), '--warmup', '5', '--steps', '40', '--no-cpu-baseline', '--no-other-workloads',
+           '--npoints', str(args.npoints), '--warmup', '5', '--steps', '40', '--full', '--no-cpu-baseline', '--no-other-workloads',
            '--caller-steps', '0', '--profile-steps', '3']
     for flag, on in (('--fp16', args.fp16), ('--no-tuned-gemms', args.no_tuned_gemms)):
         if on:
@@ -523,7 +528,14 @@ def main():
                     help='start the ranks, form the process group, all-reduce one CPU/GPU scalar, print a JSON line on rank 0 '
                          'and exit BEFORE any model / kernel call (launch + rendezvous + relay check; works without a GPU '
                          'with SUG_BENCH_BACKEND=gloo)')
-    ap.add_argument('--plain', action='store_true', help='only warm-up + timed steps (for rocprofv3 kernel traces): no extra passes')
+    lean = ap.add_mutually_exclusive_group()
+    lean.add_argument('--full', action='store_true',
+                      help='after the timed steps, everything else the benchmark measures: kernel timings and roofline, eager, '
+                           'unchanged-caller and single-pass steps, the other workloads, the one-rank RCCL rehearsal, '
+                           'per-collective times and the CPU baselines (--no-cpu-baseline, --no-other-workloads and the '
+                           '--*-steps options trim it)')
+    lean.add_argument('--plain', action='store_true',
+                      help='only warm-up + timed steps (for rocprofv3 kernel traces): what a run without --full does')
     ap.add_argument('--timestamps-child', default=None, metavar='OUT.json',
                     help='(internal) warm up, replay --profile-steps captured steps under torch.profiler, write the device '
                          'kernel durations to OUT.json and exit: bench.py runs this pass in a CHILD process because roctracer '
@@ -706,7 +718,7 @@ def main():
     exact_ms = None
     graph_kernel_ms = graph_launches = None
     child_events = None
-    if graph_mode and not args.plain:
+    if graph_mode and args.full:
         # kernel durations INSIDE the measured launch mode: the device kernels' own timestamps (torch.profiler = roctracer,
         # what `rocprofv3 --kernel-trace` reads) over a few more replays of the captured step
         # -- in a CHILD process (rank 0 only, a one-rank replica of the same step): roctracer under hipGraph replay crashed
@@ -724,7 +736,7 @@ def main():
             graph_kernel_ms = sum(sum(v) for v in exact_ms.values()) / nrep
             graph_launches = sum(len(v) for v in exact_ms.values()) / nrep
     collectives = None
-    if (world > 1 or args.segmented) and graph_mode and getattr(trainer, 'segmented', False):
+    if args.full and (world > 1 or args.segmented) and graph_mode and getattr(trainer, 'segmented', False):
         # per-collective milliseconds (events on the compute stream around the eager RCCL calls between the graph replays)
         # over a few more steps, outside the timed region; bucket 1 additionally alone (synchronous, nothing beside it)
         trainer.collective_events = {}
@@ -752,11 +764,12 @@ def main():
                                 'each eager collective; bucket1_exposed = wait for bucket 1 after the encoder backward it '
                                 'runs under; bucket1_alone = the same message all-reduced with nothing beside it'
                                 % max(args.profile_steps, 1))
-    if args.plain or ((world > 1 or args.segmented) and graph_mode):
-        # multi-rank: nothing but the timed region in this process; the per-kernel timings of the hand-written families
-        # come from rank 0's one-rank child (the kernels are the same: the per-GPU share is what every rank runs)
+    if not args.full or ((world > 1 or args.segmented) and graph_mode):
+        # no --full: no step after the timed region.  Multi-rank: nothing but the timed region in this process; the per-kernel
+        # timings of the hand-written families come from rank 0's one-rank child (the kernels are the same: the per-GPU share
+        # is what every rank runs)
         extra_prof = {}
-        if not args.plain and graph_mode and rank == 0 and child_events:
+        if args.full and graph_mode and rank == 0 and child_events:
             extra_prof = {k: [(ms, None, {kk: vv for kk, vv in shp.items()}) for ms, shp in v] for k, v in child_events.items()}
     elif graph_mode:
         # eager steps of the same trainer: per-kernel event timings of every hand-written family + eager ms/step
@@ -796,7 +809,7 @@ def main():
     # calls per step, nothing shared between them (the headline uses the exact restructurings of
     # paired domains + shared prefix).
     caller_ms = None
-    if args.caller_steps > 0 and not args.plain and world == 1 and not args.segmented and (trainer.pair_domains or trainer.share_prefix):
+    if args.caller_steps > 0 and args.full and world == 1 and not args.segmented and (trainer.pair_domains or trainer.share_prefix):
         keep = (trainer.pair_domains, trainer.share_prefix)
         trainer.pair_domains = trainer.share_prefix = False
         if hasattr(model.g, 'share_prefix'):
@@ -823,7 +836,7 @@ def main():
     # attention layers.  Reported BESIDE the headline, never as it: it differs from the reference's step in one documented
     # way (one FPS start draw per sampling stage instead of two).
     single_ms = None
-    if args.caller_steps > 0 and not args.plain and world == 1 and not args.segmented and graph_mode and not args.single_pass:
+    if args.caller_steps > 0 and args.full and world == 1 and not args.segmented and graph_mode and not args.single_pass:
         tr1 = SUGStep(model, lr=1e-3, weight_decay=5e-5, share_prefix=not args.no_share_prefix, use_graph=True,
                       pair_domains=not args.no_pair, methods=BENCH_METHODS, single_pass=True)
         for _ in range(4):
@@ -885,11 +898,12 @@ def main():
             else:
                 roofline['traffic_note'] = 'no PMC passes on file for this kernel version (profiles/pmc_traffic_%s.json)' % kernel_source_hash(dom)
         if roofline is not None:
-            try:
-                roofline['hbm_copy_gbps_measured'] = round(measured_copy_gbps(dev), 1)
-                roofline['hbm_note'] = 'device-to-device copy of 1 GiB on this box (read + write) beside the %.0f GB/s vendor peak the fractions use' % HBM_PEAK_GBS
-            except RuntimeError:
-                pass
+            if args.full:                                   # a measurement of its own
+                try:
+                    roofline['hbm_copy_gbps_measured'] = round(measured_copy_gbps(dev), 1)
+                    roofline['hbm_note'] = 'device-to-device copy of 1 GiB on this box (read + write) beside the %.0f GB/s vendor peak the fractions use' % HBM_PEAK_GBS
+                except RuntimeError:
+                    pass
             import bench_work
             roofline['step'] = bench_work.step_roofline(args.model, B, N, 1e3 * dt / args.steps, single_pass=args.single_pass,
                                                         fp16=args.fp16 and args.model == 'PTran', n_params=n_params,
@@ -899,7 +913,7 @@ def main():
                     args.model, B, N, single_ms, single_pass=True, n_params=n_params, adam_elems=adam_elems).items()
                     if k in ('gflop', 'gbytes', 'ms', 'achieved_tflops', 'achieved_gbps', 'frac_mfma', 'frac_hbm')}
         others = None
-        if world == 1 and not args.plain and not args.segmented and not args.no_other_workloads and args.model == 'DGCNN':
+        if world == 1 and args.full and not args.segmented and not args.no_other_workloads and args.model == 'DGCNN':
             # the other BASELINE configurations, driver-timed in the same line (configs 1, 3, 5 and N = 2048)
             trainer = model = None
             gc.collect()
@@ -911,11 +925,11 @@ def main():
                 except RuntimeError as e:
                     others.append({'workload': '%s N=%d batch=%d' % (nm, n_, b_), 'error': str(e).splitlines()[0][:200]})
         seg1 = None
-        if world == 1 and not args.plain and not args.segmented and not args.no_other_workloads and args.model == 'DGCNN' \
+        if world == 1 and args.full and not args.segmented and not args.no_other_workloads and args.model == 'DGCNN' \
                 and not args.single_pass:
             seg1 = segmented_rehearsal(args)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_record(args.model, args.cpu_batch, N, args.cpu_steps)
             if others:
                 # the CPU oracle beside every single-GPU configuration, on bounded samples of the same

@@ -6,7 +6,8 @@
   * mmd.mmd_cal(..., GEO_WEIGHTS='mean2one', data_s, data_t) against oracle.mmd_cal (train_dg_single_gpu.py:314,
     model/mmd.py:107-131, :178-202);
   * the steps of BASELINE configs 3 and 5 at their per-GPU sizes (PointNet++ 64 x 2048; Point Transformer 16 x 2048 in its
-    fp16 mode): finite, reproducible, and for config 5 the deviation of the fp16 mode from fp32 reported and bounded.
+    fp16 mode): finite, reproducible, and for config 5 the deviation of the fp16 mode from fp32 reported and bounded;
+  * a plain `bench.py` run (no --full): the headline line and nothing measured after the timed steps.
 """
 import pytest
 import torch
@@ -284,3 +285,30 @@ def test_configs_3_and_5_full_size_graph_tuned_match_oracle(model_name, single_p
     for step in got:
         for a, b in zip(step, want):
             assert abs(a - b) <= 1e-4 * max(1.0, abs(b)), (model_name, single_pass, got, want)
+
+
+def test_plain_bench_run_reports_the_headline_and_measures_nothing_else():
+    """`bench.py` without --full: one JSON line with the headline fields, and nothing measured after the timed steps -- no
+    kernel timings or roofline, no eager / unchanged-caller / single-pass steps, no other workloads, no one-rank RCCL
+    rehearsal, no CPU baseline (all of that is --full's)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    r = subprocess.run([sys.executable, os.path.abspath(bench.__file__), '--gpus', '1', '--steps', '3', '--warmup', '3'],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d['metric'] == 'point-clouds/sec (train step, N=1024)' and d['unit'] == 'point-clouds/sec'
+    assert d['higher_is_better'] is True and d['dtype'] == 'f32' and d['steps'] == 3 and d['warmup'] == 3
+    assert d['value'] > 0 and abs(d['value'] - 64 / (d['ms_per_step'] * 1e-3)) <= 1e-9 * d['value']
+    assert d['config']['launch'] == 'hipGraph replay of the whole step'
+    assert d['roofline'] is None and d['kernels'] == {} and d['cpu_baseline'] is None
+    cfg = d['config']
+    for k in ('eager_ms_per_step', 'graph_kernel_ms_per_step', 'unchanged_caller_ms_per_step', 'single_pass_ms_per_step',
+              'other_workloads', 'segmented_one_rank_rccl', 'collectives'):
+        assert cfg[k] is None, (k, cfg[k])
+    assert all(v is not None for v in d['losses']), d['losses']

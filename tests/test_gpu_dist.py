@@ -223,7 +223,7 @@ def test_two_rank_step_rccl():
 
 
 def test_bench_two_ranks_end_to_end_gloo_on_one_gpu():
-    """`python bench.py --gpus 2` the way the driver starts a multi-GPU run, with gloo standing in for RCCL and both ranks on
+    """`python bench.py --gpus 2 --full` as a multi-GPU run is started, with gloo standing in for RCCL and both ranks on
     the one device of this box: bench.launch_ranks -> torch.distributed.run -> two ranks -> five graph segments around the
     four collectives -> per-collective milliseconds -> rank 0's one-rank child process for the kernel timings -> ONE JSON
     line on stdout with roofline, kernels and config.collectives filled in.  (The step time itself means nothing here: two
@@ -233,7 +233,7 @@ def test_bench_two_ranks_end_to_end_gloo_on_one_gpu():
     env = dict(os.environ, SUG_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '3', '--batch', '4',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--full', '--warmup', '3', '--batch', '4',
                         '--no-cpu-baseline', '--no-other-workloads', '--caller-steps', '0', '--eager-steps', '1', '--profile-steps', '1'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -289,7 +289,7 @@ def test_four_rank_segmented_graph_gloo_on_one_gpu():
 
 
 def test_bench_three_ranks_end_to_end_gloo_on_one_gpu():
-    """`bench.py --gpus 3 --batch 2` on one device over gloo: a world size that is not a power of two (M = 6 rows per domain in
+    """`bench.py --gpus 3 --batch 2 --full` on one device over gloo: a world size that is not a power of two (M = 6 rows per domain in
     the global MMD, / 3 in the gradient buckets) through the launcher, the five graph segments and rank 0's kernel-timestamp
     child.  (This test process + 3 ranks + the child = 5 processes on the card; the box allows 6 -- the first 8-rank run is
     the driver's.)"""
@@ -299,7 +299,7 @@ def test_bench_three_ranks_end_to_end_gloo_on_one_gpu():
     env = dict(os.environ, SUG_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--steps', '2', '--warmup', '3', '--batch', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--steps', '2', '--full', '--warmup', '3', '--batch', '2',
                         '--no-cpu-baseline', '--no-other-workloads', '--caller-steps', '0', '--eager-steps', '1', '--profile-steps', '1'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1100)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
