@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate and the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd) were added: purely additive entry points, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd) and sug_ptcls_head_supported / _fwd / _bwd were added: purely additive entry points, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -820,6 +820,24 @@ int sug_seg_max_pool_bwd(const float* g, const int32_t* arg, const int32_t* rev_
 /* y [B, C] = per-cloud mean of x [N, C]; dx [N, C] = g[b] / N_b */
 int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C, float* y, void* stream);
 int sug_seg_mean_bwd(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream);
+
+/* ---- Point Transformer classifier head (PointTransformerCls.fc2 on points.mean(1), model/Ptran_model.py:104-117) ----
+ * logits [B, NC] = L3(relu(L2(relu(L1(mean_P(points)))))), points [B, P, K] dense, Li(x) = x . Wi^T + bi with W1 [N1, K],
+ * W2 [N2, N1], W3 [NC, N2] (nn.Linear layout).  fp32, every sum in one fixed order, no atomics: bit-reproducible.
+ * Supported (sug_ptcls_head_supported): 1 <= B <= 128, 1 <= P <= 64, K % 64 == 0 and K <= 1024, N1 % 64 == 0 and
+ * N1 <= 1024, N2 == 64, 2 <= NC <= 64.  points, W1, W2, W3, mean and h1 16-byte aligned.
+ * sug_ptcls_head_fwd (2 launches): mean [B, K] = sum over P in point order / P, h1 [B, N1], h2 [B, N2] (post-ReLU),
+ * logits.  sug_ptcls_head_bwd (2 launches): from dlogits [B, NC] and the forward's mean / h1 / h2: dz1 [B, N1] and
+ * dz2 [B, N2] (caller's scratch: pre-activation gradients), dpoints [B, P, K] = dmean / P for every point, and the
+ * weight / bias gradients (overwritten, not accumulated). */
+int sug_ptcls_head_supported(int B, int P, int K, int N1, int N2, int NC);
+int sug_ptcls_head_fwd(const float* points, int B, int P, int K, const float* W1, const float* b1, int N1, const float* W2,
+                       const float* b2, int N2, const float* W3, const float* b3, int NC, float* mean, float* h1, float* h2,
+                       float* logits, void* stream);
+int sug_ptcls_head_bwd(const float* dlogits, const float* mean, const float* h1, const float* h2, int B, int P, int K,
+                       const float* W1, int N1, const float* W2, int N2, const float* W3, int NC, float* dz1, float* dz2,
+                       float* dpoints, float* dW1, float* db1, float* dW2, float* db2, float* dW3, float* db3,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,10 @@ SIGNATURES = {
     'sug_seg_max_pool_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     'sug_seg_mean_fwd': [_vp, _vp, _i32, _i32, _vp, _vp],
     'sug_seg_mean_bwd': [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    'sug_ptcls_head_supported': [_i32, _i32, _i32, _i32, _i32, _i32],
+    'sug_ptcls_head_fwd': [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    'sug_ptcls_head_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _vp, _vp, _vp],
 }
 
 STATS_BLOCKS = 1024        # SUG_STATS_BLOCKS

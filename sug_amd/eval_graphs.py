@@ -43,7 +43,8 @@ FALLBACKS = collections.Counter()           # reason -> eager calls on the calle
 def _known_types():
     from .model.Model import Net_MDA
     from .model.model_pointnet import Pointnet_cls, Pointnet2_cls, DGCNN
-    return (Net_MDA, Pointnet_cls, Pointnet2_cls, DGCNN)
+    from .model.Ptran_model import PointTransformerCls
+    return (Net_MDA, Pointnet_cls, Pointnet2_cls, DGCNN, PointTransformerCls)
 
 
 def signature(model):
@@ -118,7 +119,8 @@ class EvalRunner:
 
     def __init__(self, model):
         if not isinstance(model, _known_types()):
-            raise TypeError('EvalRunner: %s is not Net_MDA / Pointnet_cls / Pointnet2_cls / DGCNN' % type(model).__name__)
+            raise TypeError('EvalRunner: %s is not Net_MDA / Pointnet_cls / Pointnet2_cls / DGCNN / PointTransformerCls'
+                            % type(model).__name__)
         self.sig = signature(model)
         self.net = self._private_copy(model)
         sd = self.net.state_dict(keep_vars=True)

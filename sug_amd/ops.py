@@ -1026,6 +1026,65 @@ def heads_fused(heads, x):
     return [(out[2 * i], out[2 * i + 1]) for i in range(len(heads))]
 
 
+# ---- Point Transformer classifier head (PointTransformerCls: fc2 on points.mean(1)) in 2 + 2 launches ---------------
+PTCLS_HEAD_FUSED = _os.environ.get('SUG_PTCLS_HEAD_FUSED', '1') != '0'   # A/B knob: 0 = the composed library head
+
+
+def ptcls_head_supported(points, fc2):
+    """Can PointTransformerCls.fc2 (Linear, ReLU, Linear, ReLU, Linear) on points [B, P, K] run through sug_ptcls_head_*?
+    Otherwise the model composes the head from library ops (points.mean(1), three nn.Linear)."""
+    if not (PTCLS_HEAD_FUSED and points.is_cuda and points.dtype == torch.float32 and points.dim() == 3 and len(fc2) == 5):
+        return False
+    l1, l2, l3 = fc2[0], fc2[2], fc2[4]
+    for t in (l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias):
+        if t is None or not t.is_cuda or t.dtype != torch.float32:
+            return False
+    B, P, K = points.shape
+    if l1.in_features != K or l2.in_features != l1.out_features or l3.in_features != l2.out_features:
+        return False
+    return bool(lib().sug_ptcls_head_supported(B, P, K, l1.out_features, l2.out_features, l3.out_features))
+
+
+class _PtclsHead(torch.autograd.Function):
+    """logits = L3(relu(L2(relu(L1(points.mean(1)))))) (sug_ptcls_head_fwd: 2 launches); the backward gives the gradients
+    of points and of all six parameters (sug_ptcls_head_bwd: 2 launches).  Saved: the mean rows and both post-ReLU
+    activations."""
+
+    @staticmethod
+    def forward(ctx, points, w1, b1, w2, b2, w3, b3):
+        _need_gpu(points, w1, b1, w2, b2, w3, b3)
+        p = points.detach().contiguous()
+        W = [t.detach().contiguous() for t in (w1, b1, w2, b2, w3, b3)]
+        B, P, K = p.shape
+        N1, N2, NC = W[0].shape[0], W[2].shape[0], W[4].shape[0]
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=p.device)
+        mean, h1, h2, logits = new(B, K), new(B, N1), new(B, N2), new(B, NC)
+        check(lib().sug_ptcls_head_fwd(_p(p), B, P, K, _p(W[0]), _p(W[1]), N1, _p(W[2]), _p(W[3]), N2, _p(W[4]), _p(W[5]), NC,
+                                       _p(mean), _p(h1), _p(h2), _p(logits), _st()), 'sug_ptcls_head_fwd')
+        ctx.save_for_backward(mean, h1, h2, W[0], W[2], W[4])
+        ctx.P = P
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        mean, h1, h2, w1, w2, w3 = ctx.saved_tensors
+        B, K = mean.shape
+        P, N1, N2, NC = ctx.P, w1.shape[0], w2.shape[0], w3.shape[0]
+        g = g.contiguous()
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=g.device)
+        dz1, dz2, dpts = new(B, N1), new(B, N2), new(B, P, K)
+        dw1, db1, dw2, db2, dw3, db3 = new(N1, K), new(N1), new(N2, N1), new(N2), new(NC, N2), new(NC)
+        check(lib().sug_ptcls_head_bwd(_p(g), _p(mean), _p(h1), _p(h2), B, P, K, _p(w1), N1, _p(w2), N2, _p(w3), NC,
+                                       _p(dz1), _p(dz2), _p(dpts), _p(dw1), _p(db1), _p(dw2), _p(db2), _p(dw3), _p(db3), _st()),
+              'sug_ptcls_head_bwd')
+        return dpts, dw1, db1, dw2, db2, dw3, db3
+
+
+def ptcls_head(points, w1, b1, w2, b2, w3, b3):
+    """PointTransformerCls's head on the last level's features points [B, P, K] -> logits [B, NC] (see _PtclsHead)."""
+    return _PtclsHead.apply(points, w1, b1, w2, b2, w3, b3)
+
+
 # num_batches_tracked increments: one tiny launch per BatchNorm call unless deferred; inside a
 # `deferred_bn_counts()` block they are collected and applied with one foreach add at the end.
 
