@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd) and sug_ptcls_head_supported / _fwd / _bwd were added: purely additive entry points, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) were added: purely additive entry points, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -106,6 +106,35 @@ int sug_knn_query_direct(const float* xyz, const float* query, int B, int N, int
  * expanded-form value (the 1e-10 clamp is the caller's). */
 int sug_three_nn(const float* query, const float* cand, int B, int N, int S,
                  int32_t* idx3, float* dist3, void* stream);
+
+/* The same selection on the direct-form distance ((q-c)_x^2 + (q-c)_y^2) + (q-c)_z^2 of model/PTran_utils.py:36
+ * (PTran_utils.PointNetFeaturePropagation, Ptran_model.TransitionUp).  Both forms take 3 <= S <= 2048. */
+int sug_three_nn_direct(const float* query, const float* cand, int B, int N, int S,
+                        int32_t* idx3, float* dist3, void* stream);
+
+/* ---- ball query for several radii in one pass ------------------------------
+ * query_ball_point of PointNetSetAbstractionMsg.forward (model/pointnet2_utils.py:246-248) for R radii, 1 <= R <= 4:
+ * every query / point distance is computed once, in sug_ball_query's operation order, and feeds the R lists
+ * out[r] [B,S,nsample[r]] by that entry point's rules; the lists equal R sug_ball_query calls bit for bit.
+ * r2, nsample and out are HOST arrays of R entries (out: device pointers). */
+int sug_ball_query_multi(const float* xyz, const float* query, int B, int N, int S, int R, const float* r2,
+                         const int32_t* nsample, int32_t* const* out, void* stream);
+
+/* ---- feature propagation: 3-NN inverse-distance interpolation ---------------
+ * PointNetFeaturePropagation.forward, model/pointnet2_utils.py:305-308 and model/PTran_utils.py:296-299:
+ *   r_t = 1 / (d3[b,n,t] + 1e-8), w_t = r_t / ((r_0 + r_1) + r_2), out[b,n,0:D) = (w_0 src[i_0] + w_1 src[i_1]) + w_2 src[i_2]
+ * with i_t = idx3[b,n,t] a row of src [B,S,D] (row stride lds).  d3 is used as it is: no clamp, a negative value (the
+ * expanded form's rounding residue of a point's distance to itself) divides as in the reference.  out has row stride ldo
+ * and may be a column slice of a wider [B,N,ldo] buffer (the torch.cat of :312 then costs no pass of its own).  w3
+ * [B,N,3] receives the weights for the backward.  Nothing of shape [B,N,3,D] is formed.
+ * Backward: dsrc[b,s,0:D) (row stride ldd) = sum over the entries e = 3n + t with idx3[b,n,t] == s, ascending in e, of
+ * w3[b,n,t] * g[b,n,0:D) (g: row stride ldg, may be a column slice): sorted reverse lists, no float atomics, every row
+ * of dsrc written, bit-identical from run to run.  Scratch: rev_off [B,S+1], rev_ent [B,3N] ints.  No gradient is
+ * formed for the coordinates.  3 <= S; 3N entries per cloud must fit the LDS-resident reverse-list build (N <= 8192). */
+int sug_fp_interp_fwd(const float* src, int64_t lds, const int32_t* idx3, const float* d3, int B, int N, int S, int D,
+                      float* out, int64_t ldo, float* w3, void* stream);
+int sug_fp_interp_bwd(const float* g, int64_t ldg, const int32_t* idx3, const float* w3, int B, int N, int S, int D,
+                      int32_t* rev_off, int32_t* rev_ent, float* dsrc, int64_t ldd, void* stream);
 
 /* dst[r][0..C) = src[r][0..C), r < rows, row strides lds / ldd in floats (C, lds, ldd multiples of 4; 16-byte aligned):
  * a dense tensor into a column slice of a wider row buffer (the torch.cat of DGCNN.forward, model/Model.py:111) or back. */

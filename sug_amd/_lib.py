@@ -25,6 +25,10 @@ SIGNATURES = {
     'sug_knn_query': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     'sug_knn_query_direct': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     'sug_three_nn': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    'sug_three_nn_direct': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    'sug_ball_query_multi': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    'sug_fp_interp_fwd': [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
+    'sug_fp_interp_bwd': [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
     'sug_gather_rows': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     'sug_scatter_add_rows': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     'sug_scatter_rows_ordered_supported': [_i32, _i32, _i32],

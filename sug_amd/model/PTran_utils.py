@@ -5,6 +5,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from . import pointnet2_utils as _pn2
 
 
 def square_distance(src, dst):
@@ -83,3 +84,9 @@ class PointNetSetAbstraction(nn.Module):
         for conv, bn in zip(self.mlp_convs, self.mlp_bns):             # g [B,S,ns,C] rows
             g = ops.bn_act_rows(ops.linear_rows(g, conv.weight.view(conv.weight.shape[0], -1), conv.bias), bn, 0.0)
         return new_xyz, torch.max(g, dim=2)[0]
+
+
+class PointNetFeaturePropagation(_pn2.PointNetFeaturePropagation):
+    """PTran_utils.py:261-311: pointnet2_utils.PointNetFeaturePropagation with the 3-NN selection and the interpolation
+    weights on the direct-form distance sum((a - b)^2) (:36, sug_three_nn_direct).  Channel-first in and out as there."""
+    DIRECT = True

@@ -4,12 +4,14 @@ imports PointTransformerCls from there).
 `Backbone` is PTran_g's encoder without the conv1d node branch (the same fc1 lift, transformer blocks, FPS / kNN
 transition-downs and HIP kernels); `PointTransformerCls` puts `fc2(points.mean(1))` on it, through the fused head
 (ops.ptcls_head) where the shapes allow and the composed library ops otherwise.  Module and parameter names follow the
-reference, so its state_dict loads with strict=True.  The segmentation decoder (TransitionUp) is not built.
+reference, so its state_dict loads with strict=True.  `TransitionUp` is the decoder's up-sampling step (two per-point
+Linear + BatchNorm + ReLU branches and the 3-NN interpolation of feature propagation).
 """
 import torch.nn as nn
 
 from .. import ops
 from .Model import PTran_g, TransitionDown, _check_input
+from .PTran_utils import PointNetFeaturePropagation
 from .Ptran_transformer import TransformerBlock
 
 # the reference's defaults (Ptran_model.py:98-104)
@@ -41,6 +43,34 @@ def _settings(cfg):
     if n_c < 1:
         raise ValueError('PointTransformerCls: cfg.num_class = %d' % n_c)
     return npoints, 4, 16, n_c, 3, 512
+
+
+class _SwapAxes(nn.Module):
+    """Holds nothing: keeps the reference's Sequential positions (Ptran_model.py:20-25), so the keys are fc?.0.* / fc?.2.*."""
+
+    def forward(self, x):
+        return x.transpose(1, 2)
+
+
+class TransitionUp(nn.Module):
+    """Ptran_model.py:18-48: feats1 = relu(bn(fc1(points1))) on the coarse level, interpolated onto the dense level's
+    points (direct-form 3-NN, ops.fp_interp), plus feats2 = relu(bn(fc2(points2))).  Rows in and out."""
+
+    def __init__(self, dim1, dim2, dim_out):
+        super().__init__()
+        self.fc1 = nn.Sequential(nn.Linear(dim1, dim_out), _SwapAxes(), nn.BatchNorm1d(dim_out), _SwapAxes(), nn.ReLU())
+        self.fc2 = nn.Sequential(nn.Linear(dim2, dim_out), _SwapAxes(), nn.BatchNorm1d(dim_out), _SwapAxes(), nn.ReLU())
+        self.fp = PointNetFeaturePropagation(-1, [])
+
+    @staticmethod
+    def _branch(fc, x):
+        return ops.bn_act_rows(ops.linear_rows(x, fc[0].weight, fc[0].bias), fc[2], 0.0)
+
+    def forward(self, xyz1, points1, xyz2, points2):
+        """xyz1 [B,n1,3], points1 [B,n1,dim1] (coarse), xyz2 [B,n2,3], points2 [B,n2,dim2] (dense) -> [B,n2,dim_out]."""
+        feats1 = self._branch(self.fc1, points1)
+        feats2 = self._branch(self.fc2, points2)
+        return self.fp.rows(xyz2, xyz1, None, feats1) + feats2
 
 
 class Backbone(nn.Module):
@@ -101,4 +131,4 @@ def classify(fc2, points):
     return fc2(points.mean(1))
 
 
-__all__ = ['TransitionDown', 'Backbone', 'PointTransformerCls']
+__all__ = ['TransitionDown', 'TransitionUp', 'Backbone', 'PointTransformerCls']

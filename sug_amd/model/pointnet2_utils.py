@@ -1,5 +1,5 @@
-"""Point-set operators in the [B,N,C] layout and the PointNet++ set-abstraction module
-(mirror of the reference's model/pointnet2_utils.py:19-207), over the HIP kernels."""
+"""Point-set operators in the [B,N,C] layout and the PointNet++ modules -- set abstraction, multi-scale grouping and
+feature propagation (mirror of the reference's model/pointnet2_utils.py:19-320), over the HIP kernels."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -169,3 +169,112 @@ class PointNetSetAbstraction(nn.Module):
         r = self.rows(xyz.permute(0, 2, 1).contiguous(),
                       None if points is None else points.permute(0, 2, 1).contiguous(), adapt)
         return tuple(t.permute(0, 2, 1) for t in r)
+
+
+def _msg_scale_rows(convs, bns, xyz, points, new_xyz, idx):
+    """One scale of multi-scale grouping (model/pointnet2_utils.py:249-262) on rows: the (1x1 conv, BN, ReLU) stack over the
+    groups of `idx` [B,S,K] and the max over each group -> [B,S,D'].  Channel order of a group is [features, xyz - centre]
+    (:253): the coordinate columns of the first layer are its LAST three.  What PointNetSetAbstraction.rows does per layer:
+    the first one on the neighbour lists where its width and the list size allow (no grouped [B,S,K,3+D] tensor), the last one fused
+    with the max where the widths allow, the general rows kernels otherwise."""
+    B, S, K = idx.shape
+    conv = convs[0]
+    w = conv.weight.view(conv.weight.shape[0], -1)
+    last = len(convs) - 1
+    first = 0
+    if last > 0 and ops.sa_first_layer_supported(w.shape[0]) and ops.reverse_lists_fit(B, xyz.shape[1], S * K):
+        # y = Wf.f_j + b + Wx.(x_j - c_s), the coordinate part from the difference the reference forms (sug_sa_first_geo_*): at
+        # the small radii of the first scales P[j] - Q[s] cancels, and BatchNorm divides the residue by a small deviation.
+        # Px and Q only route the gradients of Wx and b (their values are not read by the kernel)
+        wx = w[:, -3:].contiguous()
+        Px = ops.linear_rows(xyz, wx)
+        Pf = None if points is None else ops.linear_rows(points, w[:, :-3].contiguous())
+        Q = ops.sub_row_bias(ops.linear_rows(new_xyz, wx), conv.bias)
+        g = ops.sa_first_layer_geo(Pf, Px, Q, idx, xyz, new_xyz, wx, conv.bias, bns[0])
+        first = 1
+    else:
+        g = ops.gather_rows(xyz, idx) - new_xyz.view(B, S, 1, 3)
+        if points is not None:
+            g = torch.cat([ops.gather_rows(points, idx), g], dim=-1)
+    for i in range(first, last + 1):                                  # g: [B,S,K,C] rows
+        conv = convs[i]
+        w = conv.weight.view(conv.weight.shape[0], -1)
+        if i == last - 1 and ops.SA_MID_FUSED and bns[i].training == bns[last].training and \
+                ops.pointmlp_max_supported(w.shape[0], convs[last].out_channels, K):
+            # middle layer's BatchNorm + ReLU inside the fused last-layer + max kernel
+            cl = convs[last]
+            out, _ = ops.bn_act_pointmlp_max(ops.linear_rows(g, w, conv.bias), bns[i], 0.0, cl.weight.view(cl.weight.shape[0], -1),
+                                             cl.bias, bns[last], 0.0, K)
+            return out.view(B, S, -1)
+        if i == last and ops.pointmlp_max_supported(g.shape[-1], w.shape[0], K):
+            return ops.pointmlp_max(g, w, conv.bias, bns[i], 0.0, K).view(B, S, -1)
+        g = ops.bn_act_rows(ops.linear_rows(g, w, conv.bias), bns[i], 0.0)
+    return torch.max(g, dim=2)[0]
+
+
+class PointNetSetAbstractionMsg(nn.Module):
+    """model/pointnet2_utils.py:210-267: FPS once, then per radius ball query -> group -> 1x1 conv/BN/ReLU stack -> max over
+    the group, the scales' features concatenated.  The lists of all radii come from one pass over the distances
+    (ops.ball_query_multi).  Parameters are named as in the reference (conv_blocks.i.j, bn_blocks.i.j)."""
+
+    def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
+        super(PointNetSetAbstractionMsg, self).__init__()
+        self.npoint, self.radius_list, self.nsample_list = npoint, radius_list, nsample_list
+        self.conv_blocks, self.bn_blocks = nn.ModuleList(), nn.ModuleList()
+        for widths in mlp_list:                                        # one (conv, BN) stack per radius; input [features, xyz - centre]
+            stack = [in_channel + 3] + list(widths)
+            self.conv_blocks.append(nn.ModuleList(nn.Conv2d(a, b, 1) for a, b in zip(stack[:-1], stack[1:])))
+            self.bn_blocks.append(nn.ModuleList(nn.BatchNorm2d(b) for b in stack[1:]))
+
+    def group_indices(self, xyz):
+        """xyz [B,N,3] -> new_xyz [B,S,3], fps_idx [B,S] int32, [idx_i [B,S,K_i] int32]: ONE start draw from the CPU
+        generator (:244), the lists of up to four radii per launch."""
+        B, N, _ = xyz.shape
+        fps_idx = ops.fps(xyz, self.npoint, ops.draw_start(B, N))
+        new_xyz = ops.gather_rows(xyz, fps_idx)
+        lists = []
+        for r0 in range(0, len(self.radius_list), 4):
+            lists += ops.ball_query_multi(xyz, new_xyz, list(self.radius_list[r0:r0 + 4]), list(self.nsample_list[r0:r0 + 4]))
+        return new_xyz, fps_idx, lists
+
+    def rows(self, xyz, points):
+        """xyz [B,N,3], points [B,N,D] or None -> new_xyz [B,S,3], feats [B,S,sum D'_i]."""
+        new_xyz, _, lists = self.group_indices(xyz.detach())
+        parts = [_msg_scale_rows(self.conv_blocks[i], self.bn_blocks[i], xyz, points, new_xyz, idx) for i, idx in enumerate(lists)]
+        if len(parts) == 1:
+            return new_xyz, parts[0]
+        B, S = parts[0].shape[:2]
+        buf = torch.empty(B, S, sum(p.shape[-1] for p in parts), dtype=torch.float32, device=xyz.device)
+        return new_xyz, ops.assemble_rows(buf, parts)               # each scale lands in its column slice
+
+    def forward(self, xyz, points):
+        """Reference layout: xyz [B,3,N], points [B,D,N] or None -> new_xyz [B,3,S], new_points_concat [B,sum D'_i,S]."""
+        r = self.rows(xyz.permute(0, 2, 1).contiguous(), None if points is None else points.permute(0, 2, 1).contiguous())
+        return tuple(t.permute(0, 2, 1) for t in r)
+
+
+class PointNetFeaturePropagation(nn.Module):
+    """model/pointnet2_utils.py:270-320: 3-NN inverse-distance interpolation of the coarse level's features onto the dense
+    level (ops.fp_interp: expanded-form distances, `1 / (d + 1e-8)` weights), concatenated behind points1, then the
+    (1x1 conv, BN, ReLU) stack on rows.  Parameters are named as in the reference (mlp_convs.i, mlp_bns.i).  The coordinates
+    are data: no gradient flows to them."""
+    DIRECT = False                    # distance form of the 3-NN selection (PTran_utils: the direct form)
+
+    def __init__(self, in_channel, mlp):
+        super(PointNetFeaturePropagation, self).__init__()
+        stack = [in_channel] + list(mlp)
+        self.mlp_convs = nn.ModuleList(nn.Conv1d(a, b, 1) for a, b in zip(stack[:-1], stack[1:]))
+        self.mlp_bns = nn.ModuleList(nn.BatchNorm1d(b) for b in stack[1:])
+
+    def rows(self, xyz1, xyz2, points1, points2):
+        """xyz1 [B,N,3], xyz2 [B,S,3], points1 [B,N,D1] or None, points2 [B,S,D2] -> [B,N,D']."""
+        g = ops.fp_interp(xyz1, xyz2, points1, points2, direct=self.DIRECT)
+        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+            g = ops.bn_act_rows(ops.linear_rows(g, conv.weight.view(conv.weight.shape[0], -1), conv.bias), bn, 0.0)
+        return g
+
+    def forward(self, xyz1, xyz2, points1, points2):
+        """Reference layout: xyz1 [B,C,N], xyz2 [B,C,S], points1 [B,D1,N] or None, points2 [B,D2,S] -> [B,D',N]."""
+        return self.rows(xyz1.permute(0, 2, 1).contiguous(), xyz2.permute(0, 2, 1).contiguous(),
+                         None if points1 is None else points1.permute(0, 2, 1).contiguous(),
+                         points2.permute(0, 2, 1).contiguous()).permute(0, 2, 1)

@@ -277,15 +277,96 @@ def knn_query(xyz, query, k, want_dist=False, direct=False):
     return (idx, dist) if want_dist else idx
 
 
-def three_nn_raw(query, cand):
+def ball_query_multi(xyz, query, radii, nsamples):
+    """ball_query for 1 <= R <= 4 radii in one launch (every distance computed once): xyz [B,N,3], query [B,S,3] ->
+    a list of R [B,S,nsample_r] int32 tensors, each equal to ball_query(xyz, query, radius_r, nsample_r) bit for bit."""
+    _need_gpu(xyz, query)
+    xyz, query = xyz.detach().contiguous(), query.detach().contiguous()
+    B, N, _ = xyz.shape
+    S = query.shape[1]
+    R = len(radii)
+    if R != len(nsamples) or not 1 <= R <= 4:
+        raise RuntimeError('ball_query_multi: need 1..4 radii and as many list lengths (got %d / %d)' % (R, len(nsamples)))
+    outs = [torch.empty(B, S, int(ns), dtype=torch.int32, device=xyz.device) for ns in nsamples]
+    r2 = (ctypes.c_float * R)(*[float(torch.tensor(r ** 2, dtype=torch.float32)) for r in radii])
+    ns = (ctypes.c_int32 * R)(*[int(n) for n in nsamples])
+    check(lib().sug_ball_query_multi(_p(xyz), _p(query), B, N, S, R, r2, ns, _ptrs(outs), _st()), 'sug_ball_query_multi')
+    return outs
+
+
+def three_nn_raw(query, cand, direct=False):
+    """direct: distances as sum((q - c)^2) over x, y, z (model/PTran_utils.py:36) instead of the expanded form."""
     _need_gpu(query, cand)
     query, cand = query.detach().contiguous(), cand.detach().contiguous()
     B, N, _ = query.shape
     S = cand.shape[1]
     idx = torch.empty(B, N, 3, dtype=torch.int32, device=query.device)
     dist = torch.empty(B, N, 3, dtype=torch.float32, device=query.device)
-    check(lib().sug_three_nn(_p(query), _p(cand), B, N, S, _p(idx), _p(dist), _st()), 'sug_three_nn')
+    if direct:
+        check(lib().sug_three_nn_direct(_p(query), _p(cand), B, N, S, _p(idx), _p(dist), _st()), 'sug_three_nn_direct')
+    else:
+        check(lib().sug_three_nn(_p(query), _p(cand), B, N, S, _p(idx), _p(dist), _st()), 'sug_three_nn')
     return idx, dist
+
+
+class _FPInterp(torch.autograd.Function):
+    """cat(points1, 3-NN inverse-distance interpolation of src) of PointNetFeaturePropagation.forward
+    (model/pointnet2_utils.py:305-312): the interpolation is written into its column slice of the [B,N,D1+D2] row
+    buffer (sug_fp_interp_fwd), points1 is copied into the other.  Backward: d src by destination row over the sorted
+    reverse lists of idx3 (sug_fp_interp_bwd: no atomics, bit-identical run to run); d points1 is a view of g."""
+
+    @staticmethod
+    def forward(ctx, points1, src, idx3, d3):
+        _need_gpu(points1, src, idx3, d3)
+        src, B, S, D2, lds = _rows3(src)
+        N = idx3.shape[1]
+        D1 = 0 if points1 is None else points1.shape[2]
+        out = torch.empty(B, N, D1 + D2, dtype=torch.float32, device=src.device)
+        if D1:
+            out[:, :, :D1].copy_(points1)
+        w3 = torch.empty(B, N, 3, dtype=torch.float32, device=src.device)
+        dst = ctypes.c_void_p(out.data_ptr() + 4 * D1)
+        check(lib().sug_fp_interp_fwd(_p(src), lds, _p(idx3), _p(d3), B, N, S, D2, dst, D1 + D2, _p(w3), _st()),
+              'sug_fp_interp_fwd')
+        ctx.save_for_backward(idx3, w3)
+        ctx.meta = (B, N, S, D1, D2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx3, w3 = ctx.saved_tensors
+        B, N, S, D1, D2 = ctx.meta
+        g = g.contiguous()
+        dsrc = None
+        if ctx.needs_input_grad[1]:
+            dsrc = torch.empty(B, S, D2, dtype=torch.float32, device=g.device)
+            off = torch.empty(B, S + 1, dtype=torch.int32, device=g.device)
+            ent = torch.empty(B, 3 * N, dtype=torch.int32, device=g.device)
+            gs = ctypes.c_void_p(g.data_ptr() + 4 * D1)
+            check(lib().sug_fp_interp_bwd(gs, D1 + D2, _p(idx3), _p(w3), B, N, S, D2, _p(off), _p(ent), _p(dsrc), D2, _st()),
+                  'sug_fp_interp_bwd')
+        return (g[:, :, :D1] if D1 and ctx.needs_input_grad[0] else None), dsrc, None, None
+
+
+def fp_interp(xyz1, xyz2, points1, points2, direct=False):
+    """Rows form of feature propagation's interpolation: xyz1 [B,N,3], xyz2 [B,S,3], points1 [B,N,D1] or None, points2
+    [B,S,D2] -> [B,N,D1+D2] = cat(points1, interp).  S == 1 broadcasts points2 (model/pointnet2_utils.py:298-299), S == 2
+    is an error as in the reference (its weight.view(B, N, 3, 1) fails on two columns).  The coordinates are data: the
+    reference's gradient through the distances is not formed, and asking for it raises."""
+    _need_gpu(xyz1, xyz2, points1, points2)
+    if xyz1.requires_grad or xyz2.requires_grad:
+        raise RuntimeError('fp_interp: no gradient flows to the coordinates (xyz1 / xyz2 require grad); the interpolation '
+                           'weights are treated as constants -- pass detached coordinates')
+    B, N, _ = xyz1.shape
+    S = xyz2.shape[1]
+    if S == 1:
+        interp = points2.expand(B, N, points2.shape[2])
+        return interp.contiguous() if points1 is None else torch.cat([points1, interp], dim=-1)
+    if S == 2:
+        raise RuntimeError('feature propagation needs S == 1 or S >= 3 coarse points: with S = 2 the reference itself fails '
+                           '(three neighbours are taken of two candidates)')
+    idx3, d3 = three_nn_raw(xyz1, xyz2, direct=direct)
+    return _FPInterp.apply(points1, points2, idx3, d3)
 
 
 class _ThreeNN(torch.autograd.Function):
@@ -350,6 +431,12 @@ class _GatherRows(torch.autograd.Function):
         d = torch.zeros(B, N, C, dtype=torch.float32, device=g.device)
         check(L.sug_scatter_add_rows(_p(g), C, _p(idx2), B, N, S, C, _p(d), C, _st()), 'sug_scatter_add_rows')
         return d, None
+
+
+def reverse_lists_fit(B, N, E):
+    """Do E index entries per cloud into N destinations fit the LDS-resident reverse-list build (what the ordered
+    backwards of gather_rows and of the first set-abstraction layer on neighbour lists need)?"""
+    return bool(lib().sug_scatter_rows_ordered_supported(B, N, E))
 
 
 def gather_rows(feat, idx):
