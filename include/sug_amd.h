@@ -868,6 +868,45 @@ int sug_ptcls_head_bwd(const float* dlogits, const float* mean, const float* h1,
                        float* dpoints, float* dW1, float* db1, float* dW2, float* db2, float* dW3, float* db3,
                        void* stream);
 
+/* ---- Device-resident data pipeline (UnifiedPointDG.__getitem__, data/dataloader.py:302-327, for a whole batch) ----
+ * From the resident dataset pts [M, P, 3] and the device index list idx [B] write out [B, 3, N], one workgroup per cloud,
+ * in the reference's order:
+ *   1. SUG_PREP_NORMALIZE: normal_pc over all P points (mean in fp64 in one fixed order, centred in fp64 and rounded once,
+ *      divided by the largest norm);
+ *   2. pre_rot (HOST pointer to 9 floats, row-major, or null): p . R, rotate_shape's product;
+ *   3. SUG_PREP_ROTATE_Z: p . [[c, -s, 0], [s, c, 0], [0, 0, 1]] with one angle per cloud (rotation_point_cloud);
+ *      SUG_PREP_JITTER: + clip(sigma * n, -clip, clip) per coordinate, n standard normal (jitter_point_cloud);
+ *   4. P < N: rows P .. N-1 are exact zeros; P > N: a uniformly random ordered subset of N points; P == N: identity
+ *      (a random permutation with SUG_PREP_SHUFFLE: random_sample_pc of all the points);
+ *   5. the transposed store.
+ * Each random input comes from the caller when its pointer is given -- angles [B], noise [B, P, 3] (indexed by the source
+ * point), sel [B, N] (source point per output row, needs N <= P) -- and is drawn in the kernel when it is null:
+ * Philox4x32-10 with key = (seed low word, seed high word) and counter
+ *      (c low word, c high word, cloud slot b in the batch, purpose | index),      c = *counter, read on the device,
+ *   purpose SUG_PREP_DRAW_ANGLE,  index 0:      angle = (word0 >> 8) * 2^-24 * 2 pi;
+ *   purpose SUG_PREP_DRAW_SUBSET, index q:      words 0..3 are the sort keys of points 4q .. 4q+3; the kept points are the
+ *                                               first N in ascending (word, point index) order;
+ *   purpose SUG_PREP_DRAW_NOISE,  index n:      the three normals of OUTPUT row n, Box-Muller with u = ((w >> 8) + 1) * 2^-24,
+ *                                               v = (w >> 8) * 2^-24: r(word0) cos(2 pi v(word1)), r(word0) sin(2 pi v(word1)),
+ *                                               r(word2) cos(2 pi v(word3)),  r(w) = sqrt(-2 ln u(w)).
+ * A caller that bumps *counter by one per launch never repeats a counter; a captured launch replays with fresh draws.
+ * counter may be null only when nothing is drawn.  Debug outputs (each may be null): angles_out [B], noise_out [B, N, 3]
+ * (the unit normals used for each output row, zeros for padding), sel_out [B, N] (source point, -1 for padding).
+ * An idx entry outside [0, M) or a sel entry outside [0, P) is never dereferenced: the cloud / row is written as NaN.
+ * Limits, checked on the host before the launch: B >= 1, 1 <= P <= 4096, N <= 1.5 * P (the reference raises "Too few
+ * points" there).  Vector stores only, no atomics; bit-reproducible from (inputs, seed, *counter). */
+#define SUG_PREP_NORMALIZE 1
+#define SUG_PREP_ROTATE_Z 2
+#define SUG_PREP_JITTER 4
+#define SUG_PREP_SHUFFLE 8
+#define SUG_PREP_DRAW_ANGLE 0x00000000u
+#define SUG_PREP_DRAW_SUBSET 0x10000000u
+#define SUG_PREP_DRAW_NOISE 0x20000000u
+int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
+                      const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
+                      uint64_t seed, const uint64_t* counter, float sigma, float clip, float* out,
+                      float* angles_out, float* noise_out, int32_t* sel_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,8 @@ SIGNATURES = {
     'sug_ptcls_head_fwd': [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     'sug_ptcls_head_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                            _vp, _vp, _vp, _vp, _vp],
+    'sug_prepare_batch': [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _f32, _f32, _vp,
+                          _vp, _vp, _vp, _vp],
 }
 
 STATS_BLOCKS = 1024        # SUG_STATS_BLOCKS

@@ -1,0 +1,240 @@
+// Device-resident data pipeline: what UnifiedPointDG.__getitem__ (data/dataloader.py:302-327) does per cloud -- normal_pc,
+// the fixed pre-rotation, the random z-rotation, the clipped jitter, zero padding or a random ordered subset, the transpose
+// -- for a whole batch in one launch, one workgroup per cloud.  Counter layout of the in-kernel draws: include/sug_amd.h.
+#include "common.h"
+
+namespace {
+
+constexpr int PREP_MAX_P = 4096;
+constexpr int PREP_MAX_WAVES = 16;
+
+// Philox4x32-10 (Salmon et al., SC'11): counter c[4], key k[2]
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t w[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+__device__ __forceinline__ float u24(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }              // [0, 1)
+__device__ __forceinline__ float u24_open(uint32_t w) { return (float)((w >> 8) + 1u) * 5.9604644775390625e-8f; }  // (0, 1]
+
+// one compare-exchange of a bitonic stage: slots i and i + j, ascending where (i & k) == 0
+__device__ __forceinline__ void sort_pair(unsigned long long* key, int i, int j, int k) {
+  const unsigned long long x = key[i], y = key[i + j];
+  if ((x > y) == ((i & k) == 0)) { key[i] = y; key[i + j] = x; }
+}
+
+struct PrepArgs {
+  const float* pts;         // [M, P, 3]
+  const int32_t* idx;       // [B]
+  const float* angles;      // [B] or null
+  const float* noise;       // [B, P, 3] or null
+  const int32_t* sel;       // [B, N] or null
+  const uint64_t* counter;  // [1] or null (only when nothing is drawn in the kernel)
+  float* out;               // [B, 3, N]
+  float* angles_out;        // [B] or null
+  float* noise_out;         // [B, N, 3] or null
+  int32_t* sel_out;         // [B, N] or null
+  float pre[9];             // pre-rotation, row-major (used when has_pre)
+  uint64_t seed;
+  int M, P, N, P2;
+  int stages, has_pre, sort;
+  float sigma, clip;
+};
+
+__global__ __launch_bounds__(1024) void prepare_batch_kernel(const PrepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  float* s_xyz = reinterpret_cast<float*>(s_raw);                                            // [P, 3]
+  unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_raw + (((size_t)a.P * 12 + 15) & ~(size_t)15));  // [P2] when sort
+  __shared__ double s_sum[PREP_MAX_WAVES][3];
+  __shared__ float s_max[PREP_MAX_WAVES];
+
+  const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
+  const int lane = t & (WAVE - 1), wv = t / WAVE, nw = T / WAVE;
+  const int P = a.P, N = a.N;
+  float* ob = a.out + (int64_t)b * 3 * N;
+  const int ci = a.idx[b];
+  if (ci < 0 || ci >= a.M) {            // an index outside the dataset: never read there, mark the cloud (uniform over the block)
+    for (int i = t; i < 3 * N; i += T) ob[i] = NAN;
+    return;
+  }
+  const float* pb = a.pts + (int64_t)ci * P * 3;
+  for (int i = t; i < 3 * P; i += T) s_xyz[i] = pb[i];
+
+  uint32_t c0 = 0, c1 = 0;
+  if (a.counter) {
+    const uint64_t c = *a.counter;
+    c0 = (uint32_t)c; c1 = (uint32_t)(c >> 32);
+  }
+  const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
+  if (a.sort) {                         // subset keys: Philox block q -> points 4q .. 4q+3; past P: last in the order
+    for (int q = t; q < a.P2 / 4; q += T) {
+      uint32_t w[4];
+      philox4x32_10(c0, c1, (uint32_t)b, SUG_PREP_DRAW_SUBSET | (uint32_t)q, k0, k1, w);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int p = 4 * q + j;
+        s_key[p] = p < P ? ((unsigned long long)w[j] << 32) | (unsigned)p : ~0ull;
+      }
+    }
+  }
+  __syncthreads();
+
+  float den = 1.0f;                     // max norm; the points are divided by it, as in the reference
+  if (a.stages & SUG_PREP_NORMALIZE) {
+    // mean over all P points: fp64 partial sums, lanes by xor-shuffle, waves in index order -- one fixed order
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int p = t; p < P; p += T) {
+      sx += (double)s_xyz[3 * p + 0]; sy += (double)s_xyz[3 * p + 1]; sz += (double)s_xyz[3 * p + 2];
+    }
+    sx = wave_sum_d(sx); sy = wave_sum_d(sy); sz = wave_sum_d(sz);
+    if (lane == 0) { s_sum[wv][0] = sx; s_sum[wv][1] = sy; s_sum[wv][2] = sz; }
+    __syncthreads();
+    double mx = 0.0, my = 0.0, mz = 0.0;
+    for (int w = 0; w < nw; ++w) { mx += s_sum[w][0]; my += s_sum[w][1]; mz += s_sum[w][2]; }
+    mx /= (double)P; my /= (double)P; mz /= (double)P;
+    float m2 = 0.0f;
+    for (int p = t; p < P; p += T) {
+      const float x = (float)((double)s_xyz[3 * p + 0] - mx), y = (float)((double)s_xyz[3 * p + 1] - my),
+                  z = (float)((double)s_xyz[3 * p + 2] - mz);
+      s_xyz[3 * p + 0] = x; s_xyz[3 * p + 1] = y; s_xyz[3 * p + 2] = z;
+      m2 = fmaxf(m2, sq3(x, y, z));
+    }
+    m2 = wave_max_f(m2);
+    if (lane == 0) s_max[wv] = m2;
+    __syncthreads();
+    m2 = s_max[0];
+    for (int w = 1; w < nw; ++w) m2 = fmaxf(m2, s_max[w]);
+    den = sqrtf(m2);
+  }
+
+  if (a.sort) {
+    // Bitonic sort of (word, point) over P2 >= 128 slots, one compare-exchange per lane and stage on the pair (i, i + j).
+    // Strides j <= 64 stay inside an aligned 128-slot chunk, which one wave owns: those stages (56 of the 66 at P2 = 2048)
+    // need wave-level ordering only; a stride above 64 crosses chunks and takes a workgroup barrier.
+    const int chunks = a.P2 / 128;
+    for (int k = 2; k <= a.P2; k <<= 1) {
+      int j = k >> 1;
+      for (; j > 64; j >>= 1) {
+        for (int q = t; q < a.P2 / 2; q += T) sort_pair(s_key, ((q & ~(j - 1)) << 1) | (q & (j - 1)), j, k);
+        __syncthreads();
+      }
+      for (int c = wv; c < chunks; c += nw) {
+        for (int jj = j; jj > 0; jj >>= 1) {
+          sort_pair(s_key, c * 128 + (((lane & ~(jj - 1)) << 1) | (lane & (jj - 1))), jj, k);
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+      if (k >= 128) __syncthreads();      // the next k starts with a stride across chunks (or the sort is done)
+    }
+  }
+
+  float ang = 0.0f, cs = 1.0f, sn = 0.0f;
+  if (a.stages & SUG_PREP_ROTATE_Z) {
+    if (a.angles) {
+      ang = a.angles[b];
+    } else {
+      uint32_t w[4];
+      philox4x32_10(c0, c1, (uint32_t)b, SUG_PREP_DRAW_ANGLE, k0, k1, w);
+      ang = u24(w[0]) * 6.28318530717958647692f;
+    }
+    sincosf(ang, &sn, &cs);
+  }
+  if (a.angles_out && t == 0) a.angles_out[b] = ang;
+
+  const bool jit = (a.stages & SUG_PREP_JITTER) != 0;
+  for (int n = t; n < N; n += T) {
+    int src;
+    if (a.sel) src = a.sel[(int64_t)b * N + n];
+    else if (a.sort) src = (int)(unsigned)s_key[n];
+    else src = n < P ? n : -1;
+    float x = 0.0f, y = 0.0f, z = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
+    if (src >= P || (a.sel && src < 0)) {       // a supplied index outside the cloud
+      x = y = z = NAN;
+    } else if (src >= 0) {
+      x = s_xyz[3 * src + 0]; y = s_xyz[3 * src + 1]; z = s_xyz[3 * src + 2];
+      if (a.stages & SUG_PREP_NORMALIZE) { x = x / den; y = y / den; z = z / den; }
+      if (a.has_pre) {                          // x.dot(R): out_j = (x R_0j + y R_1j) + z R_2j
+        const float u = (x * a.pre[0] + y * a.pre[3]) + z * a.pre[6], v = (x * a.pre[1] + y * a.pre[4]) + z * a.pre[7],
+                    w = (x * a.pre[2] + y * a.pre[5]) + z * a.pre[8];
+        x = u; y = v; z = w;
+      }
+      if (a.stages & SUG_PREP_ROTATE_Z) {       // [[c, -s, 0], [s, c, 0], [0, 0, 1]], row vector on the left
+        const float u = x * cs + y * sn, v = y * cs - x * sn;
+        x = u; y = v;
+      }
+      if (jit) {
+        if (a.noise) {
+          const float* nb = a.noise + ((int64_t)b * P + src) * 3;
+          g0 = nb[0]; g1 = nb[1]; g2 = nb[2];
+        } else {                                // Box-Muller: words 0, 1 -> two normals, words 2, 3 -> the third
+          uint32_t w[4];
+          philox4x32_10(c0, c1, (uint32_t)b, SUG_PREP_DRAW_NOISE | (uint32_t)n, k0, k1, w);
+          const float r0 = sqrtf(-2.0f * logf(u24_open(w[0]))), r1 = sqrtf(-2.0f * logf(u24_open(w[2])));
+          float s0, q0, s1, q1;
+          sincosf(6.28318530717958647692f * u24(w[1]), &s0, &q0);
+          sincosf(6.28318530717958647692f * u24(w[3]), &s1, &q1);
+          g0 = r0 * q0; g1 = r0 * s0; g2 = r1 * q1;
+        }
+        x += fminf(fmaxf(a.sigma * g0, -a.clip), a.clip);
+        y += fminf(fmaxf(a.sigma * g1, -a.clip), a.clip);
+        z += fminf(fmaxf(a.sigma * g2, -a.clip), a.clip);
+      }
+    }
+    ob[n] = x; ob[N + n] = y; ob[2 * N + n] = z;              // [3, N]: coalesced along N
+    if (a.sel_out) a.sel_out[(int64_t)b * N + n] = src;
+    if (a.noise_out) {
+      float* no = a.noise_out + ((int64_t)b * N + n) * 3;
+      no[0] = g0; no[1] = g1; no[2] = g2;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
+                                 const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
+                                 uint64_t seed, const uint64_t* counter, float sigma, float clip, float* out,
+                                 float* angles_out, float* noise_out, int32_t* sel_out, void* stream) {
+  SUG_REQUIRE(pts && idx && out, "sug_prepare_batch: null pointer (pts, idx and out are required)");
+  SUG_REQUIRE(B > 0, "sug_prepare_batch: B=%d: an empty batch", B);
+  SUG_REQUIRE(M > 0 && P > 0 && N > 0, "sug_prepare_batch: bad shape M=%d P=%d N=%d", M, P, N);
+  SUG_REQUIRE(P <= PREP_MAX_P, "sug_prepare_batch: P=%d > %d points per cloud", P, PREP_MAX_P);
+  SUG_REQUIRE(2 * (int64_t)N <= 3 * (int64_t)P, "sug_prepare_batch: too few points: N=%d > 1.5 * P=%d", N, P);
+  SUG_REQUIRE((stages & ~(SUG_PREP_NORMALIZE | SUG_PREP_ROTATE_Z | SUG_PREP_JITTER | SUG_PREP_SHUFFLE)) == 0,
+              "sug_prepare_batch: unknown bits in stages=%d", stages);
+  SUG_REQUIRE(!sel || N <= P, "sug_prepare_batch: sel given but N=%d > P=%d (padding rows have no source point)", N, P);
+  const bool sort = !sel && (P > N || (P == N && (stages & SUG_PREP_SHUFFLE)));
+  const bool draws = sort || ((stages & SUG_PREP_ROTATE_Z) && !angles) || ((stages & SUG_PREP_JITTER) && !noise);
+  SUG_REQUIRE(!draws || counter, "sug_prepare_batch: null counter: in-kernel draws need the device batch counter");
+  SUG_REQUIRE(sigma >= 0.f && clip >= 0.f, "sug_prepare_batch: sigma and clip must not be negative");
+  PrepArgs a;
+  a.pts = pts; a.idx = idx; a.angles = angles; a.noise = noise; a.sel = sel; a.counter = draws ? counter : nullptr;
+  a.out = out; a.angles_out = angles_out; a.noise_out = noise_out; a.sel_out = sel_out;
+  for (int i = 0; i < 9; ++i) a.pre[i] = pre_rot ? pre_rot[i] : (i % 4 == 0 ? 1.f : 0.f);
+  a.seed = seed; a.M = M; a.P = P; a.N = N;
+  int P2 = 128;                 // sort slots: a power of two, whole 128-slot chunks
+  while (P2 < P) P2 <<= 1;
+  a.P2 = P2; a.stages = stages; a.has_pre = pre_rot != nullptr; a.sort = sort;
+  a.sigma = sigma; a.clip = clip;
+  const size_t sh = (((size_t)P * 12 + 15) & ~(size_t)15) + (sort ? (size_t)P2 * 8 : 0);
+  if (sh > 64 * 1024) {
+    static SugLdsOptIn note;
+    if (int rc = sug_allow_dynamic_lds(note, &prepare_batch_kernel, 96 * 1024, "sug_prepare_batch")) return rc;
+  }
+  const int threads = P <= 256 ? 256 : (P <= 1024 ? 512 : 1024);
+  hipLaunchKernelGGL(prepare_batch_kernel, dim3(B), dim3(threads), sh, (hipStream_t)stream, a);
+  SUG_LAUNCH_CHECK("sug_prepare_batch");
+  return SUG_OK;
+}

@@ -1,0 +1,2 @@
+"""Host-side mirror of the reference's data/ package (data_utils.py, dataloader.py: same names and argument order) with
+the clouds resident on the device and the per-batch work in one HIP kernel (sug_prepare_batch)."""

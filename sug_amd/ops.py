@@ -6,6 +6,7 @@ CPU path.  Feature tensors are point-major rows [B,N,C].
 """
 import contextlib
 import ctypes
+import math
 import os as _os
 
 import torch
@@ -3012,6 +3013,70 @@ class _SegMean(torch.autograd.Function):
 def seg_mean(x, off):
     """[B, C]: per-cloud mean of the rows x [N, C] (model/KPConv_model.py global_average)."""
     return _SegMean.apply(x, off)
+
+
+# ----------------------------------------------------------------------------- data pipeline
+PREP_NORMALIZE, PREP_ROTATE_Z, PREP_JITTER, PREP_SHUFFLE = 1, 2, 4, 8            # SUG_PREP_* stage bits
+PREP_MAX_POINTS = 4096
+
+
+def rotation_matrix(axis, angle):
+    """rotate_shape's matrix (data/data_utils.py:47-49) for `x.dot(R)`, evaluated in fp64, as 9 floats row-major."""
+    c, s = math.cos(angle), math.sin(angle)
+    if axis == 'x':
+        return (1.0, 0.0, 0.0, 0.0, c, -s, 0.0, s, c)
+    if axis == 'y':
+        return (c, 0.0, s, 0.0, 1.0, 0.0, -s, 0.0, c)
+    return (c, -s, 0.0, s, c, 0.0, 0.0, 0.0, 1.0)
+
+
+_PRE_ROTATE_X = rotation_matrix('x', -math.pi / 2)              # UnifiedPointDG's fixed pre-rotation
+
+
+def prepare_batch(pts, idx, num_points, pre_rotate, aug, *, angles=None, noise=None, sel=None, seed=None, counter=None,
+                  out=None, sigma=0.01, clip=0.05, return_draws=False, stages=None, pre_matrix=None):
+    """UnifiedPointDG.__getitem__ for a batch in one launch (sug_prepare_batch): pts [M,P,3] fp32 resident dataset,
+    idx [B] int32 -> [B,3,num_points] fp32.  Random inputs come from `angles` [B] / `noise` [B,P,3] / `sel` [B,N] when
+    given, else from the in-kernel Philox generator keyed by `seed` at the batch counter held in the device tensor
+    `counter` (int64, one element).  `stages` overrides the stage bits (default: normalise, plus z-rotation and jitter when
+    `aug`), `pre_matrix` (9 floats) the pre-rotation (default rotate_shape(.., 'x', -pi/2) when `pre_rotate`).
+    return_draws: also (angles [B], noise [B,N,3] per kept point, sel [B,N]).  No host synchronisation; with `out` and
+    `counter` given the call is one kernel launch and can be captured."""
+    _need_gpu(pts, idx, angles, noise, sel, counter, out)
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise ValueError('prepare_batch: pts must be a contiguous fp32 [M, P, 3] tensor, got %s %s' % (tuple(pts.shape), pts.dtype))
+    if idx.dim() != 1 or idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise ValueError('prepare_batch: idx must be a contiguous int32 [B] tensor')
+    M, P, _ = pts.shape
+    B, N = idx.shape[0], int(num_points)
+    dev = pts.device
+    if stages is None:
+        stages = PREP_NORMALIZE | ((PREP_ROTATE_Z | PREP_JITTER) if aug else 0)
+    if pre_matrix is None and pre_rotate:
+        pre_matrix = _PRE_ROTATE_X
+    pre = (ctypes.c_float * 9)(*pre_matrix) if pre_matrix is not None else None
+
+    def given(t, shape, dtype, name):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError('prepare_batch: %s must be a contiguous %s tensor of shape %s, got %s %s'
+                             % (name, dtype, shape, t.dtype, tuple(t.shape)))
+    given(angles, (B,), torch.float32, 'angles')
+    given(noise, (B, P, 3), torch.float32, 'noise')
+    given(sel, (B, N), torch.int32, 'sel')
+    given(out, (B, 3, N), torch.float32, 'out')
+    given(counter, (1,), torch.int64, 'counter')
+    if out is None:
+        out = torch.empty(B, 3, N, dtype=torch.float32, device=dev)
+    a_out = n_out = s_out = None
+    if return_draws:
+        a_out = torch.empty(B, dtype=torch.float32, device=dev)
+        n_out = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+        s_out = torch.empty(B, N, dtype=torch.int32, device=dev)
+    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(lib().sug_prepare_batch(_p(pts), M, P, _p(idx), B, N, stages, pre, _p(angles), _p(noise), _p(sel), seed,
+                                  _p(counter), sigma, clip, _p(out), _p(a_out), _p(n_out), _p(s_out), _st()),
+          'sug_prepare_batch')
+    return (out, a_out, n_out, s_out) if return_draws else out
 
 
 def _ctx_property(field):
