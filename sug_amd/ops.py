@@ -23,19 +23,23 @@ class StepContext:
       bn_groups          G equal contiguous parts of the batch (Net_MDA.forward_pair: source clouds, then target clouds) that the
                          reference sends through the network in G separate forward calls: BatchNorm statistics and running-buffer
                          updates per part, in order
-      start_queue        pre-drawn FPS starts of this forward (the reference's call order), consumed by draw_start
+      start_queue        pre-drawn FPS starts of this forward (Net_MDA.forward_pair draws them in the reference's call order:
+                         every farthest_point_sample of the source forward, then those of the target forward), consumed by
+                         draw_start
       start_provider     None, or a callable (B, N) -> starts: a graph's start feeder (record / provide), a test's table
-      geometry_plan      FPS + ball-query results of this pass computed up front (Pointnet2_g.plan_geometry), popped in call order
-      profile            None, or {kernel name: [(event, event, shape)]}: bench.py's per-kernel HIP-event timings
+      geometry_plan      FPS + ball-query results of several encoder passes over ONE batch computed up front
+                         (Pointnet2_g.plan_geometry: both depend on the coordinates and the start draws only, so the semantic
+                         and the node pass of a step share their launches): a list of (new_xyz, idx) per sample_and_group call,
+                         popped in call order by pointnet2_utils.sample_and_group_idx
+      profile            None, or {kernel name: [(event, event, shape)]}: bench.py's per-kernel HIP-event timings (see _timed)
       profile_only       None, or the set of name prefixes that get events
       parallel_branches  independent small-kernel chains on forked streams (opt-in; measured slower)
       fused_heads        fused LayerNorm + activation in the FC heads (SUGStep switches it on for its own forwards)
       w16_cache          step-scoped cache of 16-bit weight copies (Point Transformer, fp16 mode) or None
       bn_record          None, or the list collecting (BatchNorm module, batch-statistics coefficients) of a shared prefix
-      pending_counts     None, or the deferred num_batches_tracked increments of this pass
-      last_coef, last_coef_pair   the batch-statistics coefficients of the most recent BatchNorm op(s), for bn_record"""
+      pending_counts     None, or the deferred num_batches_tracked increments of this pass"""
     __slots__ = ('bn_groups', 'start_queue', 'start_provider', 'geometry_plan', 'profile', 'profile_only', 'parallel_branches',
-                 'fused_heads', 'w16_cache', 'bn_record', 'pending_counts', 'last_coef', 'last_coef_pair')
+                 'fused_heads', 'w16_cache', 'bn_record', 'pending_counts')
 
     def __init__(self):
         self.bn_groups = 1
@@ -44,22 +48,11 @@ class StepContext:
         self.parallel_branches = False
         self.fused_heads = False
         self.w16_cache = self.bn_record = self.pending_counts = None
-        self.last_coef, self.last_coef_pair = None, (None, None)
 
 
 CTX = StepContext()
 
 SIGMA_LIST = (0.01, 0.1, 1, 10, 100)       # model/mmd.py:23
-
-
-# bench.py sets PROFILE = {} to time selected kernels with events on the launch stream.
-# PROFILE_ONLY (a set of name prefixes or None) restricts which kernels get events: every
-# event pair costs host time, and an eager step is host-bound.  While a hipGraph is being
-# captured the events are created `external` so that they become event-record nodes.
-
-# FPS start indices: the reference draws torch.randint(0, N, (B,)) from the CPU default
-# generator once per farthest_point_sample call.  A provider (SUGStep's graph mode) may hand
-# out device-resident slices instead, filled from the same draws, so a step can be replayed.
 
 
 # Independent branches of a step (the two classifier heads, the two attention layers, the three MMD terms) are chains of
@@ -102,12 +95,11 @@ def capture_guard():
     capture: hipGraphExecDestroy / hipFree under a global-mode capture aborted the process (seen once in a full test run,
     round 6: 'Fatal Python error: Aborted ... Garbage-collecting' inside a captured forward).  The collector stays OFF for the
     duration of the capture (dead cycles wait for the next automatic collection outside it; a full collection here costs
-    ~0.1 s in a large process and a step is captured in up to six pieces), and the module-level tensor caches are dropped
-    first (their tensors may live in an older graph's pool and would otherwise be released -- by reference count, collector
+    ~0.1 s in a large process and a step is captured in up to six pieces), and the module-level tensor cache is dropped
+    first (its tensors may live in an older graph's pool and would otherwise be released -- by reference count, collector
     or not -- by the first op of the capture that replaces them)."""
     import gc
     clear_rows_cache()
-    CTX.last_coef, CTX.last_coef_pair = None, (None, None)
     was = gc.isenabled()
     gc.disable()
     try:
@@ -117,24 +109,16 @@ def capture_guard():
             gc.enable()
 
 
-# Domain groups of a batch: with BN_GROUPS = G the batch dimension holds G equal contiguous parts
-# (Net_MDA.forward_pair: source clouds then target clouds) that the reference sends through the
-# network in G separate forward calls.  Everything per-cloud / per-row is oblivious to that; the
-# BatchNorm ops compute statistics and update the running buffers per part, in order, so the
-# result is the one of G separate calls.
-
-
 @contextlib.contextmanager
 def bn_groups(g):
+    """The batch holds g domain groups (see StepContext.bn_groups) inside the block.  Everything per-cloud / per-row is
+    oblivious to that; the BatchNorm ops compute statistics and update the running buffers per part, in order, so the result
+    is the one of g separate calls."""
     old, CTX.bn_groups = CTX.bn_groups, int(g)
     try:
         yield
     finally:
         CTX.bn_groups = old
-
-
-# Pre-drawn FPS starts (Net_MDA.forward_pair draws them in the reference's call order: every
-# farthest_point_sample of the source forward, then those of the target forward).
 
 
 @contextlib.contextmanager
@@ -146,14 +130,10 @@ def start_queue(q):
         CTX.start_queue = old
 
 
-# Geometry of several encoder passes over ONE batch, computed up front (Pointnet2_g.plan_geometry): farthest-point sampling and
-# ball query depend on the coordinates and the start draws only, so the semantic and the node pass of a step can share
-# their launches (FPS is one workgroup per cloud and `npoint` dependent rounds: 128 clouds fill half of the chip for
-# 0.34 ms; both passes in one launch take the same 0.34 ms).  A list of (new_xyz, idx) per sample_and_group call, in call
-# order; pointnet2_utils.sample_and_group_idx pops from it.
-
-
 def draw_start(B, N):
+    """FPS start indices [B]: the reference draws torch.randint(0, N, (B,)) from the CPU default generator once per
+    farthest_point_sample call.  A start queue or a provider (SUGStep's graph mode) hands out the same draws made up front
+    -- the provider as device-resident slices, so a step can be replayed."""
     if CTX.start_queue:                 # draws made up front for this forward (Net_MDA.forward_pair: the reference's order)
         t = CTX.start_queue.pop(0)
         if t.numel() != B:
@@ -175,6 +155,8 @@ def draw_group_start(B, N):
 
 
 def _timed(name, shape, call):
+    """call(), between two timing events on the launch stream when bench.py profiles this kernel name (CTX.profile = {};
+    CTX.profile_only restricts the names: every event pair costs host time, and an eager step is host-bound)."""
     if CTX.profile is None or (CTX.profile_only is not None and not name.startswith(tuple(CTX.profile_only))):
         return call()
     if torch.cuda.is_current_stream_capturing():        # timing events cannot be captured on ROCm
@@ -687,6 +669,51 @@ def eval_coef(gamma, beta, running_mean, running_var, eps):
     return torch.stack([scale, beta - running_mean * scale, running_mean, rstd, running_var]).contiguous()
 
 
+class _BNState:
+    """What a fused BatchNorm op needs of its nn.BatchNorm module besides weight and bias (those stay arguments of the
+    autograd.Function: autograd must see them): built once at the public entry point, passed to .apply as ONE non-tensor.
+    `train` is the kernels' int flag, G = CTX.bn_groups at the time of the call."""
+    __slots__ = ('mean', 'var', 'training', 'train', 'eps', 'momentum', 'G')
+
+    def __init__(self, running_mean, running_var, training, eps, momentum):
+        self.mean, self.var = running_mean, running_var
+        self.training = bool(training)
+        self.train = 1 if training else 0
+        self.eps, self.momentum, self.G = eps, momentum, CTX.bn_groups
+
+
+def _bn_state(bn):
+    return _BNState(bn.running_mean, bn.running_var, bn.training, bn.eps, bn.momentum)
+
+
+def _bn_params(gamma, beta, st, C):
+    """-> contiguous (gamma, beta) and the [G, 5, C] coefficient buffer of a fused BatchNorm op: left for the kernel to fill
+    in train mode, the running-statistics coefficients broadcast over the groups (one copy launch) in eval mode."""
+    g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+    coef = torch.empty(st.G, 5, C, dtype=torch.float32, device=g.device)
+    if not st.training:
+        coef.copy_(eval_coef(g, b, st.mean, st.var, st.eps))
+    return g, b, coef
+
+
+def _stats_ws(C, dev):
+    """Workspace of the column-statistics reductions over C channels."""
+    return torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
+
+
+def _check_groups(op, n, what, G, seg=None):
+    if seg is None and n % G:
+        raise RuntimeError('%s: %d %s do not split into %d domain groups' % (op, n, what, G))
+    if seg is not None and n % (G * seg):
+        raise RuntimeError('%s: %d %s do not split into %d groups of %d-row segments' % (op, n, what, G, seg))
+
+
+def _dgamma_dbeta(rf):
+    """rf [2C] = dbeta | dgamma as the backward kernels write them -> (dgamma, dbeta)."""
+    C = rf.numel() // 2
+    return rf[C:], rf[:C]
+
+
 def affine_act(z, coef, slope, out=None):
     """out[...,c] = leaky(scale[c]*z + shift[c]); z [..., C] rows."""
     _need_gpu(z)
@@ -708,7 +735,7 @@ def col_stats(y2, ws=None):
     rows, C = y2.shape
     stats = torch.empty(2 * C, dtype=torch.float64, device=y2.device)
     if ws is None:
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=y2.device)
+        ws = _stats_ws(C, y2.device)
     check(lib().sug_col_stats(_p(y2), y2.stride(0), rows, C, _p(stats), _p(ws), _st()), 'sug_col_stats')
     return stats
 
@@ -718,39 +745,37 @@ class _BNActRows(torch.autograd.Function):
     Train mode uses batch statistics and updates the running ones like nn.BatchNorm."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, running_mean, running_var, training, slope, eps, momentum, G):
+    def forward(ctx, y, gamma, beta, st, slope):
         _need_gpu(y, gamma)
         C = y.shape[-1]
         y2 = y.reshape(-1, C)
         if y2.stride(1) != 1 or y2.stride(0) != C:
             y2 = y2.contiguous()
         rows = y2.shape[0]
-        if rows % G:
-            raise RuntimeError('bn_act_rows: %d rows do not split into %d domain groups' % (rows, G))
+        _check_groups('bn_act_rows', rows, 'rows', st.G)
         dev = y.device
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        if training:
-            coef = torch.empty(G, 5, C, dtype=torch.float32, device=dev)
-        else:
-            coef = eval_coef(g, b, running_mean, running_var, eps).unsqueeze(0).repeat(G, 1, 1)
+        g, b, coef = _bn_params(gamma, beta, st, C)
         out = torch.empty(rows, C, dtype=torch.float32, device=dev)
         stats = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
-        check(lib().sug_bn_act_rows_fwd(_p(y2), C, rows, C, G, _p(g), _p(b), 1 if training else 0, eps, momentum,
-                                        float(slope), _p(running_mean), _p(running_var), _p(coef), _p(out), C,
+        ws = _stats_ws(C, dev)
+        check(lib().sug_bn_act_rows_fwd(_p(y2), C, rows, C, st.G, _p(g), _p(b), st.train, st.eps, st.momentum,
+                                        float(slope), _p(st.mean), _p(st.var), _p(coef), _p(out), C,
                                         _p(stats), _p(ws), _st()), 'sug_bn_act_rows_fwd')
-        CTX.last_coef = coef
-        if any(ctx.needs_input_grad[i] for i in (0, 1, 2)):
+        if any(ctx.needs_input_grad[i] for i in (0, 1, 2)):             # y, gamma, beta
             ctx.save_for_backward(y2, coef)
-            ctx.meta = (rows, C, float(slope), bool(training), tuple(y.shape), G)
-        return out.view(y.shape)
+            ctx.meta = (rows, C, float(slope), st.training, tuple(y.shape), st.G)
+        ctx.mark_non_differentiable(coef)
+        ctx.set_materialize_grads(False)
+        return out.view(y.shape), coef
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, _gcoef):
         y2, coef = ctx.saved_tensors
         rows, C, slope, training, shape, G = ctx.meta
+        if gout is None:                    # an undefined gradient counts as zeros, as if autograd had materialised it
+            gout = torch.zeros_like(y2)
         dy, dgamma, dbeta = _bn_act_rows_backward(gout, y2, coef, rows, C, slope, training, G)
-        return dy.view(shape), dgamma, dbeta, None, None, None, None, None, None, None
+        return dy.view(shape), dgamma, dbeta, None, None
 
 
 def _bn_act_rows_backward(gout, y2, coef, rows, C, slope, training, G):
@@ -761,12 +786,12 @@ def _bn_act_rows_backward(gout, y2, coef, rows, C, slope, training, G):
         g2 = g2.contiguous()
     a = torch.empty(rows, C, dtype=torch.float32, device=dev)
     red = torch.empty(G, 2 * C, dtype=torch.float64, device=dev)
-    ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
+    ws = _stats_ws(C, dev)
     dy = torch.empty(rows, C, dtype=torch.float32, device=dev) if training else a
     rf = torch.empty(2 * C, dtype=torch.float32, device=dev)
-    check(lib().sug_bn_act_rows_bwd(_p(g2), g2.stride(0), _p(y2), C, _p(coef), rows, C, G, 1 if training else 0,
+    check(lib().sug_bn_act_rows_bwd(_p(g2), g2.stride(0), _p(y2), C, _p(coef), rows, C, G, int(training),
                                     slope, _p(a), _p(red), _p(dy), _p(ws), _p(rf), _st()), 'sug_bn_act_rows_bwd')
-    return dy, rf[C:], rf[:C]
+    return (dy,) + _dgamma_dbeta(rf)
 
 
 class _SAFirstLayer(torch.autograd.Function):
@@ -774,49 +799,46 @@ class _SAFirstLayer(torch.autograd.Function):
     grouped [B,S,ns,3+D] tensor (sug_sa_first_fwd / bwd)."""
 
     @staticmethod
-    def forward(ctx, P, Q, idx, gamma, beta, running_mean, running_var, training, eps, momentum, G):
+    def forward(ctx, P, Q, idx, gamma, beta, st):
         _need_gpu(P, Q, idx)
         P, Q = P.contiguous(), Q.contiguous()
         idx = _i32(idx).contiguous()
         B, N, C = P.shape
         S, ns = idx.shape[1], idx.shape[2]
-        if B % G:
-            raise RuntimeError('sa_first_layer: %d clouds do not split into %d domain groups' % (B, G))
+        _check_groups('sa_first_layer', B, 'clouds', st.G)
         dev = P.device
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        if training:
-            coef = torch.empty(G, 5, C, dtype=torch.float32, device=dev)
-        else:
-            coef = eval_coef(g, b, running_mean, running_var, eps).unsqueeze(0).repeat(G, 1, 1)
+        g, b, coef = _bn_params(gamma, beta, st, C)
         Z = torch.empty(B, S, ns, C, dtype=torch.float32, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
-        check(lib().sug_sa_first_fwd(_p(P.detach()), C, _p(Q.detach()), _p(idx), B, N, S, ns, C, G, _p(g), _p(b),
-                                     1 if training else 0, eps, momentum, _p(running_mean), _p(running_var), _p(coef),
+        ws = _stats_ws(C, dev)
+        check(lib().sug_sa_first_fwd(_p(P.detach()), C, _p(Q.detach()), _p(idx), B, N, S, ns, C, st.G, _p(g), _p(b),
+                                     st.train, st.eps, st.momentum, _p(st.mean), _p(st.var), _p(coef),
                                      _p(Z), _p(ws), _st()), 'sug_sa_first_fwd')
         ctx.save_for_backward(P, Q, idx, coef)
-        ctx.meta = (bool(training), G)
+        ctx.meta = (st.train, st.G)
         return Z
 
     @staticmethod
     def backward(ctx, gz):
         P, Q, idx, coef = ctx.saved_tensors
-        training, G = ctx.meta
+        train, G = ctx.meta
         B, N, C = P.shape
         S, ns = idx.shape[1], idx.shape[2]
-        dev = gz.device
         gz = gz.contiguous()
-        red = torch.zeros(G + 1, 2 * C, dtype=torch.float64, device=dev)
-        dP = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-        dQ = torch.empty(B, S, C, dtype=torch.float32, device=dev)
-        rf = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
-        off = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
-        ent = torch.empty(B, S * ns, dtype=torch.int32, device=dev)
-        segsum = torch.empty(2, B, S, C, dtype=torch.float32, device=dev)
-        check(lib().sug_sa_first_bwd(_p(gz), _p(P), C, _p(Q), _p(idx), B, N, S, ns, C, G, 1 if training else 0, _p(coef),
-                                     _p(red), _p(off), _p(ent), _p(segsum), _p(dP), _p(dQ), _p(ws), _p(rf), _st()),
-              'sug_sa_first_bwd')
-        return dP, dQ, None, rf[C:], rf[:C], None, None, None, None, None, None
+        bufs = _sa_first_bwd_buffers(B, N, S, ns, C, G, gz.device)
+        check(lib().sug_sa_first_bwd(_p(gz), _p(P), C, _p(Q), _p(idx), B, N, S, ns, C, G, train, _p(coef),
+                                     *map(_p, bufs), _st()), 'sug_sa_first_bwd')
+        dP, dQ, rf = bufs[4], bufs[5], bufs[7]
+        return (dP, dQ, None) + _dgamma_dbeta(rf) + (None,)
+
+
+def _sa_first_bwd_buffers(B, N, S, ns, C, G, dev):
+    """The outputs and workspaces of sug_sa_first_bwd / sug_sa_first_geo_bwd, in the order both kernels take them:
+    (red, off, ent, segsum, dP, dQ, ws, rf)."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    return (torch.zeros(G + 1, 2 * C, dtype=torch.float64, device=dev),
+            torch.empty(B, N + 1, dtype=torch.int32, device=dev), torch.empty(B, S * ns, dtype=torch.int32, device=dev),
+            torch.empty(2, B, S, C, **f32), torch.empty(B, N, C, **f32), torch.empty(B, S, C, **f32),
+            _stats_ws(C, dev), torch.empty(2 * C, **f32))
 
 
 class _SAFirstLayerGeo(torch.autograd.Function):
@@ -826,58 +848,45 @@ class _SAFirstLayerGeo(torch.autograd.Function):
     gradients (dP, dQ) route the loss to Wx and b through the ordinary linear backward."""
 
     @staticmethod
-    def forward(ctx, Pf, Px, Q, idx, xyz, cent, Wx, bias, gamma, beta, running_mean, running_var, training, eps, momentum, G):
+    def forward(ctx, Pf, Px, Q, idx, xyz, cent, Wx, bias, gamma, beta, st):
         _need_gpu(Px, Q, idx, xyz)
         idx = _i32(idx).contiguous()
         B, N, C = Px.shape
         S, ns = idx.shape[1], idx.shape[2]
-        if B % G:
-            raise RuntimeError('sa_first_layer: %d clouds do not split into %d domain groups' % (B, G))
+        _check_groups('sa_first_layer', B, 'clouds', st.G)
         dev = Px.device
         Pfc = None if Pf is None else Pf.detach().contiguous()
         xyz, cent = xyz.detach().contiguous(), cent.detach().contiguous()
         Wxc = Wx.detach().contiguous()
         bc = None if bias is None else bias.detach().contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        if training:
-            coef = torch.empty(G, 5, C, dtype=torch.float32, device=dev)
-        else:
-            coef = eval_coef(g, b, running_mean, running_var, eps).unsqueeze(0).repeat(G, 1, 1)
+        g, b, coef = _bn_params(gamma, beta, st, C)
         Z = torch.empty(B, S, ns, C, dtype=torch.float32, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
-        check(lib().sug_sa_first_geo_fwd(_p(Pfc), C, _p(xyz), _p(cent), _p(Wxc), 3, _p(bc), _p(idx), B, N, S, ns, C, G, _p(g), _p(b),
-                                         1 if training else 0, eps, momentum, _p(running_mean), _p(running_var), _p(coef), _p(Z),
+        ws = _stats_ws(C, dev)
+        check(lib().sug_sa_first_geo_fwd(_p(Pfc), C, _p(xyz), _p(cent), _p(Wxc), 3, _p(bc), _p(idx), B, N, S, ns, C, st.G,
+                                         _p(g), _p(b), st.train, st.eps, st.momentum, _p(st.mean), _p(st.var), _p(coef), _p(Z),
                                          _p(ws), _st()), 'sug_sa_first_geo_fwd')
         saved = [idx, coef, xyz, cent, Wxc] + ([Pfc] if Pfc is not None else []) + ([bc] if bc is not None else [])
         ctx.save_for_backward(*saved)
-        ctx.meta = (bool(training), G, Pfc is not None, bc is not None, N, C)
+        ctx.meta = (st.train, st.G, Pfc is not None, bc is not None, N, C)
         return Z
 
     @staticmethod
     def backward(ctx, gz):
-        training, G, has_p, has_b, N, C = ctx.meta
+        train, G, has_p, has_b, N, C = ctx.meta
         sv = list(ctx.saved_tensors)
         idx, coef, xyz, cent, Wxc = sv[:5]
         Pfc = sv[5] if has_p else None
         bc = sv[5 + int(has_p)] if has_b else None
         B, S, ns = idx.shape
-        dev = gz.device
         gz = gz.contiguous()
-        red = torch.zeros(G + 1, 2 * C, dtype=torch.float64, device=dev)
-        dP = torch.empty(B, N, C, dtype=torch.float32, device=dev)
-        dQ = torch.empty(B, S, C, dtype=torch.float32, device=dev)
-        rf = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
-        off = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
-        ent = torch.empty(B, S * ns, dtype=torch.int32, device=dev)
-        segsum = torch.empty(2, B, S, C, dtype=torch.float32, device=dev)
+        bufs = _sa_first_bwd_buffers(B, N, S, ns, C, G, gz.device)
         check(lib().sug_sa_first_geo_bwd(_p(gz), _p(Pfc), C, _p(xyz), _p(cent), _p(Wxc), 3, _p(bc), _p(idx), B, N, S, ns, C, G,
-                                         1 if training else 0, _p(coef), _p(red), _p(off), _p(ent), _p(segsum), _p(dP), _p(dQ),
-                                         _p(ws), _p(rf), _st()), 'sug_sa_first_geo_bwd')
+                                         train, _p(coef), *map(_p, bufs), _st()), 'sug_sa_first_geo_bwd')
+        dP, dQ, rf = bufs[4], bufs[5], bufs[7]
         # Pf and Px receive the SAME gradient tensor on purpose (y depends on them only through Pf[j] + Px-routed terms with
         # identical row gradients): both are non-leaf outputs of linear_rows whose backward only reads its upstream
         # gradient, so the alias is never written through; a clone would cost a pass over [B,N,C]
-        return (dP if has_p else None), dP, dQ, None, None, None, None, None, rf[C:], rf[:C], None, None, None, None, None, None
+        return ((dP if has_p else None), dP, dQ, None, None, None, None, None) + _dgamma_dbeta(rf) + (None,)
 
 
 SA_FIRST_GEO = _os.environ.get('SUG_SA_FIRST_GEO', '0') == '1'  # opt-in: y = Pf[j] + b + Wx.(x_j - c_s) (measured: no accuracy gain, 1 % slower)
@@ -885,8 +894,7 @@ SA_FIRST_GEO = _os.environ.get('SUG_SA_FIRST_GEO', '0') == '1'  # opt-in: y = Pf
 
 def sa_first_layer_geo(Pf, Px, Q, idx, xyz, cent, Wx, bias, bn):
     _count_bn_call(bn)
-    return _SAFirstLayerGeo.apply(Pf, Px, Q, idx, xyz, cent, Wx, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                  bn.training, bn.eps, bn.momentum, CTX.bn_groups)
+    return _SAFirstLayerGeo.apply(Pf, Px, Q, idx, xyz, cent, Wx, bias, bn.weight, bn.bias, _bn_state(bn))
 
 
 SA_FIRST = _os.environ.get('SUG_SA_FIRST', '1') != '0'          # 0: grouped tensor + GEMM (the reference's arithmetic) instead
@@ -900,8 +908,7 @@ def sa_first_layer(P, Q, idx, bn):
     """P [B,N,C] = W.[xyz ; feats] per point, Q [B,S,C] = Wxyz.new_xyz - b per centroid, idx [B,S,ns] ball-query
     lists -> relu(bn(P[idx] - Q)) [B,S,ns,C] (train-mode statistics over each domain group's rows)."""
     _count_bn_call(bn)
-    return _SAFirstLayer.apply(P, Q, idx, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.eps,
-                               bn.momentum, CTX.bn_groups)
+    return _SAFirstLayer.apply(P, Q, idx, bn.weight, bn.bias, _bn_state(bn))
 
 
 class _LNAct(torch.autograd.Function):
@@ -1224,9 +1231,9 @@ def record_bn_stats():
         CTX.bn_record = prev
 
 
-def _record_bn(bn):
+def _record_bn(bn, coef):
     if CTX.bn_record is not None and bn.training and bn.track_running_stats:
-        CTX.bn_record.append((bn, CTX.last_coef))
+        CTX.bn_record.append((bn, coef))
 
 
 def replay_bn_stats(rec):
@@ -1269,9 +1276,8 @@ def bn_replay(bn, coef):
 def bn_act_rows(y, bn, slope):
     """bn: an nn.BatchNorm{1,2}d module whose parameters / running buffers are used."""
     _count_bn_call(bn)
-    out = _BNActRows.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, slope, bn.eps,
-                           bn.momentum, CTX.bn_groups)
-    _record_bn(bn)
+    out, coef = _BNActRows.apply(y, bn.weight, bn.bias, _bn_state(bn), slope)
+    _record_bn(bn, coef)
     return out
 
 
@@ -1280,47 +1286,43 @@ class _BNActPool(torch.autograd.Function):
     two backward (sug_bn_act_pool_*)."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, running_mean, running_var, training, slope, eps, momentum, G):
+    def forward(ctx, y, gamma, beta, st, slope):
         _need_gpu(y, gamma)
         y, B, N, C, ld = _rows3(y)
-        if B % G:
-            raise RuntimeError('bn_act_pool: %d clouds do not split into %d domain groups' % (B, G))
+        G = st.G
+        _check_groups('bn_act_pool', B, 'clouds', G)
         dev = y.device
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        if training:
-            coef = torch.empty(G, 5, C, dtype=torch.float32, device=dev)
-        else:
-            coef = eval_coef(g, b, running_mean, running_var, eps).unsqueeze(0).repeat(G, 1, 1)
+        g, b, coef = _bn_params(gamma, beta, st, C)
         pooled = torch.empty(B, 2 * C, dtype=torch.float32, device=dev)      # [max | mean]: torch.cat((max, mean), 1) in place
         omax, omean = pooled[:, :C], pooled[:, C:]
         arg = torch.empty(B, C, dtype=torch.int32, device=dev)
         stats = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        wss = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
+        wss = _stats_ws(C, dev)
         wsp = torch.empty(12 * (B // G) * C, dtype=torch.float32, device=dev)
-        check(lib().sug_bn_act_pool_layer_fwd(_p(y), ld, B, N, C, G, _p(g), _p(b), 1 if training else 0, eps, momentum,
-                                              float(slope), _p(running_mean), _p(running_var), _p(coef), _p(omax),
+        check(lib().sug_bn_act_pool_layer_fwd(_p(y), ld, B, N, C, G, _p(g), _p(b), st.train, st.eps, st.momentum,
+                                              float(slope), _p(st.mean), _p(st.var), _p(coef), _p(omax),
                                               _p(omean), 2 * C, _p(arg), _p(stats), _p(wss), _p(wsp), _st()),
               'sug_bn_act_pool_layer_fwd')
         ctx.save_for_backward(y, coef, arg)
-        ctx.meta = (B, N, C, ld, float(slope), bool(training), G)
+        ctx.meta = (B, N, C, ld, float(slope), st.train, G)
         return pooled
 
     @staticmethod
     def backward(ctx, g):
         y, coef, arg = ctx.saved_tensors
-        B, N, C, ld, slope, training, G = ctx.meta
+        B, N, C, ld, slope, train, G = ctx.meta
         dev = y.device
         if g.stride(1) != 1 or g.stride(0) < 2 * C:
             g = g.contiguous()
         gmax, gmean, ldp = g[:, :C], g[:, C:], g.stride(0)
         red = torch.empty(G, 2 * C, dtype=torch.float64, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
+        ws = _stats_ws(C, dev)
         dy = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         rf = torch.empty(2 * C, dtype=torch.float32, device=dev)
         check(lib().sug_bn_act_pool_layer_bwd(_p(y), ld, _p(coef), _p(gmax), _p(gmean), ldp, _p(arg), B, N, C, G, slope,
-                                              1 if training else 0, _p(red), _p(ws), _p(dy), C, _p(rf), _st()),
+                                              train, _p(red), _p(ws), _p(dy), C, _p(rf), _st()),
               'sug_bn_act_pool_layer_bwd')
-        return dy, rf[C:], rf[:C], None, None, None, None, None, None, None
+        return (dy,) + _dgamma_dbeta(rf) + (None, None)
 
 
 def bn_update_stats(y, bn):
@@ -1335,12 +1337,11 @@ def bn_update_stats(y, bn):
     if y2.stride(1) != 1:
         y2 = y2.contiguous()
     rows, G = y2.shape[0], CTX.bn_groups
-    if rows % G:
-        raise RuntimeError('bn_update_stats: %d rows do not split into %d domain groups' % (rows, G))
+    _check_groups('bn_update_stats', rows, 'rows', G)
     rg = rows // G
     g, b = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
     coef = torch.empty(5, C, dtype=torch.float32, device=y.device)
-    ws = torch.empty(STATS_BLOCKS * 2 * C, dtype=torch.float32, device=y.device)
+    ws = _stats_ws(C, y.device)
     for i in range(G):
         yi = y2[i * rg:(i + 1) * rg]
         check(lib().sug_col_stats_bn(_p(yi), yi.stride(0), rg, C, _p(g), _p(b), bn.eps, bn.momentum,
@@ -1353,8 +1354,7 @@ def bn_act_pool_cat(y, bn, slope):
     """cat((max over points, mean over points), 1) [B, 2C] of act(bn(y)), y [B,N,C]: the kernels write the two halves of
     the concatenated feature (Model.py:113-116) and read the two halves of its gradient in place."""
     _count_bn_call(bn)
-    return _BNActPool.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, slope, bn.eps,
-                            bn.momentum, CTX.bn_groups)
+    return _BNActPool.apply(y, bn.weight, bn.bias, _bn_state(bn), slope)
 
 
 def bn_act_pool(y, bn, slope):
@@ -1365,51 +1365,71 @@ def bn_act_pool(y, bn, slope):
 
 
 # ----------------------------------------------------------------------------- EdgeConv
+def _edgeconv_out(out_holder, B, N, Co, dev):
+    """The [B,N,Co] destination of an EdgeConv layer: fresh, or the caller's (a column slice of a wider rows buffer, see
+    assemble_rows; passed in a list so that autograd does not treat it as an input of the node)."""
+    if out_holder is None:
+        return torch.empty(B, N, Co, dtype=torch.float32, device=dev)
+    out = out_holder[0]
+    if tuple(out.shape) != (B, N, Co) or out.stride(2) != 1 or out.stride(0) != N * out.stride(1) \
+            or out.dtype != torch.float32 or out.requires_grad:
+        raise RuntimeError('edgeconv: bad destination slice')
+    return out
+
+
+def _edgeconv_backward(gout, z, arg, s1, pq, ldpq, idx, coef, B, N, k, Co, G, slope, train):
+    """sug_edgeconv_layer_bwd from what either EdgeConv forward saved: -> (dpq [B,N,2Co], dgamma, dbeta)."""
+    dev = gout.device
+    gout, _, _, _, ldg = _rows3(gout)                           # a column slice of a wider buffer is fine
+    a = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
+    # per-group dbeta | dgamma, plus a zero row the scatter reads in eval mode (statistics constant)
+    red = (torch.empty if train else torch.zeros)(G + 1, 2 * Co, dtype=torch.float64, device=dev)
+    ws = _stats_ws(Co, dev)
+    off = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
+    ent = torch.empty(B, N * k, dtype=torch.int32, device=dev)
+    dpq = torch.empty(B, N, 2 * Co, dtype=torch.float32, device=dev)
+    rf = torch.empty(2 * Co, dtype=torch.float32, device=dev)
+    check(_timed('edgeconv_layer_bwd_Co%d' % Co, {'B': B, 'N': N, 'k': k, 'Co': Co},
+                 lambda: lib().sug_edgeconv_layer_bwd(_p(gout), ldg, _p(z), _p(arg), _p(s1), _p(pq), ldpq, _p(idx),
+                                                      _p(coef), B, N, k, Co, G, train, slope, _p(a),
+                                                      _p(red), _p(off), _p(ent), _p(dpq), 2 * Co, _p(ws), _p(rf), _st())),
+          'sug_edgeconv_layer_bwd')
+    return (dpq,) + _dgamma_dbeta(rf)
+
+
 class _EdgeConv(torch.autograd.Function):
     """BN(train or eval) + LeakyReLU + max over k of y = P[idx] + Q, see include/sug_amd.h."""
 
     @staticmethod
-    def forward(ctx, pq, idx, gamma, beta, running_mean, running_var, training, slope, eps, momentum, G, out_holder,
-                grad_on=True):
+    def forward(ctx, pq, idx, gamma, beta, st, slope, out_holder, grad_on=True):
         _need_gpu(pq, idx, gamma)
         pq, B, N, C2, ld = _rows3(pq)
         Co = C2 // 2
         idx = _i32(idx).contiguous()
         k = idx.shape[2]
-        if B % G:
-            raise RuntimeError('edgeconv: %d clouds do not split into %d domain groups' % (B, G))
+        G = st.G
+        _check_groups('edgeconv', B, 'clouds', G)
         dev = pq.device
-        gamma_c, beta_c = gamma.detach().contiguous(), beta.detach().contiguous()
+        gamma_c, beta_c, coef = _bn_params(gamma, beta, st, Co)
         # (needs_input_grad reports requires_grad of the inputs even under torch.no_grad(): the caller passes the grad
         # mode, or the no-grad passes of a step would write s1 -- 4*Co bytes per point -- for a backward that never runs)
-        need_bwd = grad_on and any(ctx.needs_input_grad[i] for i in (0, 2, 3))
+        need_bwd = grad_on and any(ctx.needs_input_grad[i] for i in (0, 2, 3))         # pq, gamma, beta
         z = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
         arg = torch.empty(B, N, Co, dtype=torch.uint8, device=dev)
         s1 = torch.empty(B, N, Co, dtype=torch.float32, device=dev) if need_bwd else None
         stats = torch.empty(2 * Co, dtype=torch.float64, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * Co, dtype=torch.float32, device=dev)
-        coef = torch.empty(G, 5, Co, dtype=torch.float32, device=dev)
-        if not training:
-            coef.copy_(eval_coef(gamma_c, beta_c, running_mean, running_var, eps))
-        if out_holder is None:
-            out = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
-        else:
-            # caller-provided destination (a column slice of a wider rows buffer, see assemble_rows);
-            # passed in a list so that autograd does not treat it as an input of this node
-            out = out_holder[0]
-            if tuple(out.shape) != (B, N, Co) or out.stride(2) != 1 or out.stride(0) != N * out.stride(1) \
-                    or out.dtype != torch.float32 or out.requires_grad:
-                raise RuntimeError('edgeconv: bad destination slice')
+        ws = _stats_ws(Co, dev)
+        out = _edgeconv_out(out_holder, B, N, Co, dev)
         ldo = out.stride(1)
         check(_timed('edgeconv_layer_fwd_Co%d' % Co, {'B': B, 'N': N, 'k': k, 'Co': Co},
                      lambda: lib().sug_edgeconv_layer_fwd(_p(pq), ld, _p(idx), _p(gamma_c), _p(beta_c), B, N, k, Co, G,
-                                                          1 if training else 0, eps, momentum, float(slope),
-                                                          _p(running_mean), _p(running_var), _p(z), _p(arg), _p(s1),
+                                                          st.train, st.eps, st.momentum, float(slope),
+                                                          _p(st.mean), _p(st.var), _p(z), _p(arg), _p(s1),
                                                           _p(coef), _p(out), ldo, _p(stats), _p(ws), _st())),
               'sug_edgeconv_layer_fwd')
         if need_bwd:
             ctx.save_for_backward(pq, idx, z, arg, s1, coef)
-            ctx.meta = (B, N, k, Co, ld, float(slope), bool(training), G)
+            ctx.meta = (B, N, k, Co, ld, float(slope), st.train, G)
         coef_out = coef[0] if G == 1 else coef
         ctx.mark_non_differentiable(coef_out)
         ctx.set_materialize_grads(False)
@@ -1417,33 +1437,19 @@ class _EdgeConv(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout, _gcoef):
-        pq, idx, z, arg, s1, coef = ctx.saved_tensors
-        B, N, k, Co, ld, slope, training, G = ctx.meta
         if gout is None:
-            return (None,) * 13
-        dev = gout.device
-        gout, _, _, _, ldg = _rows3(gout)                           # a column slice of a wider buffer is fine
-        a = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
-        # per-group dbeta | dgamma, plus a zero row the scatter reads in eval mode (statistics constant)
-        red = (torch.empty if training else torch.zeros)(G + 1, 2 * Co, dtype=torch.float64, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * Co, dtype=torch.float32, device=dev)
-        off = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
-        ent = torch.empty(B, N * k, dtype=torch.int32, device=dev)
-        dpq = torch.empty(B, N, 2 * Co, dtype=torch.float32, device=dev)
-        rf = torch.empty(2 * Co, dtype=torch.float32, device=dev)
-        check(_timed('edgeconv_layer_bwd_Co%d' % Co, {'B': B, 'N': N, 'k': k, 'Co': Co},
-                     lambda: lib().sug_edgeconv_layer_bwd(_p(gout), ldg, _p(z), _p(arg), _p(s1), _p(pq), ld, _p(idx),
-                                                          _p(coef), B, N, k, Co, G, 1 if training else 0, slope, _p(a),
-                                                          _p(red), _p(off), _p(ent), _p(dpq), 2 * Co, _p(ws), _p(rf), _st())),
-              'sug_edgeconv_layer_bwd')
-        return dpq, None, rf[Co:], rf[:Co], None, None, None, None, None, None, None, None, None
+            return (None,) * 8
+        pq, idx, z, arg, s1, coef = ctx.saved_tensors
+        B, N, k, Co, ld, slope, train, G = ctx.meta
+        dpq, dgamma, dbeta = _edgeconv_backward(gout, z, arg, s1, pq, ld, idx, coef, B, N, k, Co, G, slope, train)
+        return dpq, None, dgamma, dbeta, None, None, None, None
 
 
 def edgeconv_bn_act_max(pq, idx, gamma, beta, running_mean, running_var, training, slope, eps=1e-5, momentum=0.1,
                         out=None):
     """pq [B,N,2*Co] = x.[W1;W2-W1]^T, idx [B,N,k] -> (out [B,N,Co], coef [5,Co] = scale, shift,
     batch mean, rstd, unbiased batch variance; [G,5,Co] under bn_groups(G > 1))."""
-    return _EdgeConv.apply(pq, idx, gamma, beta, running_mean, running_var, training, slope, eps, momentum, CTX.bn_groups,
+    return _EdgeConv.apply(pq, idx, gamma, beta, _BNState(running_mean, running_var, training, eps, momentum), slope,
                            None if out is None else [out], torch.is_grad_enabled())
 
 
@@ -1469,46 +1475,36 @@ class _EdgeConvFused(torch.autograd.Function):
     (sug_edgeconv_fused_layer_fwd).  [P|Q] is written only for a backward (sug_edgeconv_layer_bwd reads it)."""
 
     @staticmethod
-    def forward(ctx, x, wcat, bias, idx, gamma, beta, running_mean, running_var, training, slope, eps, momentum, G,
-                out_holder, grad_on=True):
+    def forward(ctx, x, wcat, bias, idx, gamma, beta, st, slope, out_holder, grad_on=True):
         _need_gpu(x, wcat, idx, gamma)
         x3, B, N, C, ld = _rows3(x)
         Co = wcat.shape[0] // 2
         idx = _i32(idx).contiguous()
         k = idx.shape[2]
-        if B % G:
-            raise RuntimeError('edgeconv: %d clouds do not split into %d domain groups' % (B, G))
+        G = st.G
+        _check_groups('edgeconv', B, 'clouds', G)
         dev = x.device
         w = wcat.detach().contiguous()
         b1 = None if bias is None else bias.detach().contiguous()
-        gamma_c, beta_c = gamma.detach().contiguous(), beta.detach().contiguous()
+        gamma_c, beta_c, coef = _bn_params(gamma, beta, st, Co)
         # (needs_input_grad ignores torch.no_grad(): the caller passes the grad mode -- see _EdgeConv)
-        need_bwd = grad_on and any(ctx.needs_input_grad[i] for i in (0, 1, 2, 4, 5))
+        need_bwd = grad_on and any(ctx.needs_input_grad[i] for i in (0, 1, 2, 4, 5))   # x, wcat, bias, gamma, beta
         z = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
         arg = torch.empty(B, N, Co, dtype=torch.uint8, device=dev) if need_bwd else None
         s1 = torch.empty(B, N, Co, dtype=torch.float32, device=dev) if need_bwd else None
         pq = torch.empty(B, N, 2 * Co, dtype=torch.float32, device=dev) if need_bwd else None
-        ws = torch.empty(STATS_BLOCKS * 2 * Co, dtype=torch.float32, device=dev)
-        coef = torch.empty(G, 5, Co, dtype=torch.float32, device=dev)
-        if not training:
-            coef.copy_(eval_coef(gamma_c, beta_c, running_mean, running_var, eps))
-        if out_holder is None:
-            out = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
-        else:
-            out = out_holder[0]
-            if tuple(out.shape) != (B, N, Co) or out.stride(2) != 1 or out.stride(0) != N * out.stride(1) \
-                    or out.dtype != torch.float32 or out.requires_grad:
-                raise RuntimeError('edgeconv: bad destination slice')
+        ws = _stats_ws(Co, dev)
+        out = _edgeconv_out(out_holder, B, N, Co, dev)
         check(_timed('edgeconv_fused_fwd_C%d_Co%d' % (C, Co), {'B': B, 'N': N, 'k': k, 'Co': Co, 'C': C, 'train': int(need_bwd)},
                      lambda: lib().sug_edgeconv_fused_layer_fwd(_p(x3), ld, C, _p(w), _p(b1), _p(idx), _p(gamma_c), _p(beta_c),
-                                                                B, N, k, Co, G, 1 if training else 0, eps, momentum,
-                                                                float(slope), _p(running_mean), _p(running_var), _p(z),
+                                                                B, N, k, Co, G, st.train, st.eps, st.momentum,
+                                                                float(slope), _p(st.mean), _p(st.var), _p(z),
                                                                 _p(arg), _p(s1), _p(pq), 2 * Co, _p(coef), _p(out),
                                                                 out.stride(1), _p(ws), _st())),
               'sug_edgeconv_fused_layer_fwd')
         if need_bwd:
             ctx.save_for_backward(x3, w, idx, z, arg, s1, coef, pq)
-            ctx.meta = (B, N, k, C, Co, float(slope), bool(training), G, b1 is not None, tuple(x.shape))
+            ctx.meta = (B, N, k, C, Co, float(slope), st.train, G, b1 is not None, tuple(x.shape))
         coef_out = coef[0] if G == 1 else coef
         ctx.mark_non_differentiable(coef_out)
         ctx.set_materialize_grads(False)
@@ -1517,38 +1513,25 @@ class _EdgeConvFused(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, _gcoef):
         if gout is None:
-            return (None,) * 15
+            return (None,) * 10
         x3, w, idx, z, arg, s1, coef, pq = ctx.saved_tensors
-        B, N, k, C, Co, slope, training, G, has_bias, xshape = ctx.meta
-        dev = gout.device
-        gout, _, _, _, ldg = _rows3(gout)                           # a column slice of a wider buffer is fine
-        a = torch.empty(B, N, Co, dtype=torch.float32, device=dev)
-        red = (torch.empty if training else torch.zeros)(G + 1, 2 * Co, dtype=torch.float64, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * Co, dtype=torch.float32, device=dev)
-        off = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
-        ent = torch.empty(B, N * k, dtype=torch.int32, device=dev)
-        dpq = torch.empty(B, N, 2 * Co, dtype=torch.float32, device=dev)
-        rf = torch.empty(2 * Co, dtype=torch.float32, device=dev)
-        check(_timed('edgeconv_layer_bwd_Co%d' % Co, {'B': B, 'N': N, 'k': k, 'Co': Co},
-                     lambda: lib().sug_edgeconv_layer_bwd(_p(gout), ldg, _p(z), _p(arg), _p(s1), _p(pq), 2 * Co, _p(idx),
-                                                          _p(coef), B, N, k, Co, G, 1 if training else 0, slope, _p(a),
-                                                          _p(red), _p(off), _p(ent), _p(dpq), 2 * Co, _p(ws), _p(rf), _st())),
-              'sug_edgeconv_layer_bwd')
+        B, N, k, C, Co, slope, train, G, has_bias, xshape = ctx.meta
+        dpq, dgamma, dbeta = _edgeconv_backward(gout, z, arg, s1, pq, 2 * Co, idx, coef, B, N, k, Co, G, slope, train)
         x2 = x3.reshape(B * N, C) if x3.is_contiguous() else x3.view(B * N, C) if x3.stride(0) == N * x3.stride(1) else x3.reshape(B * N, C)
         dpq2 = dpq.view(B * N, 2 * Co)
         dx, dw, _ = linear_rows_backward(x2, w, dpq2, ctx.needs_input_grad[0], ctx.needs_input_grad[1], False)
         db = None
         if has_bias and ctx.needs_input_grad[2]:
             db = colsum(dpq2[:, Co:])                              # the bias rides on the Q half
-        return (None if dx is None else dx.view(xshape)), dw, db, None, rf[Co:], rf[:Co], None, None, None, None, None, \
-            None, None, None, None
+        return (None if dx is None else dx.view(xshape)), dw, db, None, dgamma, dbeta, None, None, None, None
 
 
 def edgeconv_fused(x, wcat, bias, idx, bn_weight, bn_bias, running_mean, running_var, training, slope, eps=1e-5,
                    momentum=0.1, out=None):
     """x [B,N,C] rows, wcat [2Co, C] = [W1 ; W2-W1], idx [B,N,k] -> (out [B,N,Co], coef) as edgeconv_bn_act_max."""
-    return _EdgeConvFused.apply(x, wcat, bias, idx, bn_weight, bn_bias, running_mean, running_var, training, slope, eps,
-                                momentum, CTX.bn_groups, None if out is None else [out], torch.is_grad_enabled())
+    return _EdgeConvFused.apply(x, wcat, bias, idx, bn_weight, bn_bias,
+                                _BNState(running_mean, running_var, training, eps, momentum), slope,
+                                None if out is None else [out], torch.is_grad_enabled())
 
 
 # ----------------------------------------------------------------------------- per-point MLP + max
@@ -1567,46 +1550,44 @@ class _PointMLPMax(torch.autograd.Function):
     the [rows,Co]x[Co,K] one -- and the matching weight-gradient term comes from X^T X."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, training, slope, eps, momentum, seg, G):
+    def forward(ctx, x, weight, bias, gamma, beta, st, slope, seg):
         _need_gpu(x, weight, gamma)
         K = x.shape[-1]
         x2 = x.reshape(-1, K)
         if x2.stride(1) != 1 or x2.stride(0) % 4 or x2.data_ptr() % 16:
             x2 = x2.contiguous()
         rows, Co = x2.shape[0], weight.shape[0]
-        if rows % (G * seg):
-            raise RuntimeError('pointmlp_max: %d rows do not split into %d groups of %d-row segments' % (rows, G, seg))
+        _check_groups('pointmlp_max', rows, 'rows', st.G, seg)
         S = rows // seg
         dev = x.device
         w2 = weight.detach().reshape(Co, K).contiguous()
         b1 = None if bias is None else bias.detach().contiguous()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        g, b, coef = _bn_params(gamma, beta, st, Co)
         zext = torch.empty(S, Co, dtype=torch.float32, device=dev)
         arg = torch.empty(S, Co, dtype=torch.int32, device=dev)
         out = torch.empty(S, Co, dtype=torch.float32, device=dev)
-        ws = torch.empty(STATS_BLOCKS * 2 * Co, dtype=torch.float32, device=dev)
-        if training:
-            coef = torch.empty(G, 5, Co, dtype=torch.float32, device=dev)
-        else:
-            coef = eval_coef(g, b, running_mean, running_var, eps).unsqueeze(0).repeat(G, 1, 1)
+        ws = _stats_ws(Co, dev)
         check(_timed('pointmlp_max_K%d_Co%d' % (K, Co), {'B': rows, 'N': seg, 'k': K, 'Co': Co},
                      lambda: lib().sug_pointmlp_max_layer_fwd(_p(x2), x2.stride(0), rows, K, _p(w2), _p(b1), _p(g), _p(b),
-                                                              Co, seg, G, 1 if training else 0, eps, momentum,
-                                                              float(slope), _p(running_mean), _p(running_var), _p(zext),
+                                                              Co, seg, st.G, st.train, st.eps, st.momentum,
+                                                              float(slope), _p(st.mean), _p(st.var), _p(zext),
                                                               _p(arg), _p(coef), _p(out), Co, _p(ws), _st())),
               'sug_pointmlp_max_layer_fwd')
-        CTX.last_coef = coef
-        if any(ctx.needs_input_grad[i] for i in (0, 1, 2, 3, 4)):
+        if any(ctx.needs_input_grad[i] for i in (0, 1, 2, 3, 4)):       # x, weight, bias, gamma, beta
             ctx.save_for_backward(x2, w2, b1, zext, arg, coef)
-            ctx.meta = (rows, K, Co, seg, G, float(slope), bool(training), tuple(x.shape), tuple(weight.shape))
-        return out
+            ctx.meta = (rows, K, Co, seg, st.G, float(slope), st.training, tuple(x.shape), tuple(weight.shape))
+        ctx.mark_non_differentiable(coef)
+        ctx.set_materialize_grads(False)
+        return out, coef
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, _gcoef):
         x2, w2, b1, zext, arg, coef = ctx.saved_tensors
         rows, K, Co, seg, G, slope, training, xshape, wshape = ctx.meta
+        if gout is None:                    # an undefined gradient counts as zeros, as if autograd had materialised it
+            gout = torch.zeros_like(zext)
         dx, dw, db, dgamma, dbeta = _pointmlp_max_backward(gout, x2, w2, b1, zext, arg, coef, rows, K, Co, seg, G, slope, training)
-        return dx.view(xshape), dw.view(wshape), db, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return dx.view(xshape), dw.view(wshape), db, dgamma, dbeta, None, None, None
 
 
 def _pointmlp_max_backward(gout, x2, w2, b1, zext, arg, coef, rows, K, Co, seg, G, slope, training):
@@ -1619,7 +1600,7 @@ def _pointmlp_max_backward(gout, x2, w2, b1, zext, arg, coef, rows, K, Co, seg, 
         gout = gout.contiguous()        # e.g. a column slice of a [.., 3 + C] gradient: the float4 kernels need aligned rows
     a = torch.empty(S, Co, dtype=torch.float32, device=dev)
     red = torch.empty(G, 2 * Co, dtype=torch.float64, device=dev)
-    ws = torch.empty(STATS_BLOCKS * 2 * Co, dtype=torch.float32, device=dev)
+    ws = _stats_ws(Co, dev)
     dx = torch.empty(rows, K, dtype=torch.float32, device=dev) if training else \
         torch.zeros(rows, K, dtype=torch.float32, device=dev)
     # dw (accumulated over the groups) and the identically-zero bias gradient of a train-mode layer: ONE zero fill
@@ -1657,23 +1638,22 @@ def _pointmlp_max_backward(gout, x2, w2, b1, zext, arg, coef, rows, K, Co, seg, 
                                             Co, seg, _p(dxg), K, _p(dws), _p(wsp), _st()),
               'sug_pointmlp_max_bwd_sparse')
         check(L.sug_pointmlp_max_bwd_dwfix(_p(dw), _p(dws), _p(kbk2[0]), _p(kbk2[1]), _p(w2), _p(xtx), _p(sx), K, Co,
-                                           1 if training else 0, _st()), 'sug_pointmlp_max_bwd_dwfix')
+                                           int(training), _st()), 'sug_pointmlp_max_bwd_dwfix')
     rf = torch.empty(2 * Co, dtype=torch.float32, device=dev)
     check(L.sug_fold_groups(_p(red), G, 2 * Co, _p(rf), _st()), 'sug_fold_groups')      # dbeta | dgamma over the groups, in group order
     db = None
     if b1 is not None:
         # a bias in front of train-mode BatchNorm has zero gradient identically
         db = zbuf[Co * K:].view_as(b1) if training else a.sum(dim=0)
-    return dx, dw, db, rf[Co:], rf[:Co]
+    return (dx, dw, db) + _dgamma_dbeta(rf)
 
 
 def pointmlp_max(x, weight, bias, bn, slope, seg):
     """x [..., K] rows (segments of `seg` consecutive rows), weight [Co, K(,1,1)], bn an nn.BatchNorm
     module -> [rows/seg, Co] = max over each segment of LeakyReLU_slope(bn(x.W^T + b))."""
     _count_bn_call(bn)
-    out = _PointMLPMax.apply(x, weight, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training,
-                             slope, bn.eps, bn.momentum, seg, CTX.bn_groups)
-    _record_bn(bn)
+    out, coef = _PointMLPMax.apply(x, weight, bias, bn.weight, bn.bias, _bn_state(bn), slope, seg)
+    _record_bn(bn, coef)
     return out
 
 
@@ -1692,64 +1672,52 @@ class _BNActPointMLPMax(torch.autograd.Function):
     _bn_act_rows_backward through BN1."""
 
     @staticmethod
-    def forward(ctx, y, g1, be1, rm1, rv1, slope1, eps1, mom1, weight, bias, g2, be2, rm2, rv2, slope2, eps2, mom2,
-                training, seg, G, want_z, last_grad, grad_on):
+    def forward(ctx, y, g1, be1, weight, bias, g2, be2, st1, slope1, st2, slope2, seg, want_z, last_grad, grad_on):
         _need_gpu(y, weight, g1, g2)
         K = y.shape[-1]
         y2 = y.reshape(-1, K)
         if y2.stride(1) != 1 or y2.stride(0) != K or y2.data_ptr() % 16:
             y2 = y2.contiguous()
         rows, Co = y2.shape[0], weight.shape[0]
-        if rows % (G * seg):
-            raise RuntimeError('bn_act_pointmlp_max: %d rows do not split into %d groups of %d-row segments' % (rows, G, seg))
-        S, rg = rows // seg, rows // G
+        G, training = st1.G, st1.training                   # one mode for both layers: bn_act_pointmlp_max checks it
+        _check_groups('bn_act_pointmlp_max', rows, 'rows', G, seg)
+        S = rows // seg
         dev = y.device
         L = lib()
-        g1c, be1c = g1.detach().contiguous(), be1.detach().contiguous()
-        ws = torch.empty(STATS_BLOCKS * 2 * max(K, Co), dtype=torch.float32, device=dev)
+        g1c, be1c, coef1 = _bn_params(g1, be1, st1, K)
+        ws = _stats_ws(max(K, Co), dev)
         if training:
-            coef1 = torch.empty(G, 5, K, dtype=torch.float32, device=dev)
-            check(L.sug_col_stats_bn_grouped(_p(y2), K, rows, K, G, _p(g1c), _p(be1c), eps1, mom1, _p(rm1), _p(rv1), _p(coef1),
-                                             _p(ws), _st()), 'sug_col_stats_bn_grouped')
-        else:
-            coef1 = eval_coef(g1c, be1c, rm1, rv1, eps1).unsqueeze(0).repeat(G, 1, 1).contiguous()
-        need1 = grad_on and any(ctx.needs_input_grad[i] for i in (0, 1, 2))
-        need2 = grad_on and last_grad and (need1 or any(ctx.needs_input_grad[i] for i in (8, 9, 10, 11)))
+            check(L.sug_col_stats_bn_grouped(_p(y2), K, rows, K, G, _p(g1c), _p(be1c), st1.eps, st1.momentum, _p(st1.mean),
+                                             _p(st1.var), _p(coef1), _p(ws), _st()), 'sug_col_stats_bn_grouped')
+        need1 = grad_on and any(ctx.needs_input_grad[i] for i in (0, 1, 2))             # y, g1, be1
+        need2 = grad_on and last_grad and (need1 or any(ctx.needs_input_grad[i] for i in (3, 4, 5, 6)))  # weight, bias, g2, be2
         z = torch.empty(rows, K, dtype=torch.float32, device=dev) if (want_z or need2) else None
         w2 = weight.detach().reshape(Co, K).contiguous()
         b1 = None if bias is None else bias.detach().contiguous()
-        g2c, be2c = g2.detach().contiguous(), be2.detach().contiguous()
+        g2c, be2c, coef2 = _bn_params(g2, be2, st2, Co)
         zext = torch.empty(S, Co, dtype=torch.float32, device=dev)
         arg = torch.empty(S, Co, dtype=torch.int32, device=dev)
         out = torch.empty(S, Co, dtype=torch.float32, device=dev)
-        if training:
-            coef2 = torch.empty(G, 5, Co, dtype=torch.float32, device=dev)
-        else:
-            coef2 = eval_coef(g2c, be2c, rm2, rv2, eps2).unsqueeze(0).repeat(G, 1, 1).contiguous()
         check(_timed('pointmlp_max_K%d_Co%d' % (K, Co), {'B': rows, 'N': seg, 'k': K, 'Co': Co},
                      lambda: L.sug_pointmlp_max_layer_fwd_xf(_p(y2), K, rows, K, _p(coef1), float(slope1), _p(z), K, _p(w2), _p(b1),
-                                                             _p(g2c), _p(be2c), Co, seg, G, 1 if training else 0, eps2, mom2,
-                                                             float(slope2), _p(rm2), _p(rv2), _p(zext), _p(arg), _p(coef2),
-                                                             _p(out), Co, _p(ws), _st())),
+                                                             _p(g2c), _p(be2c), Co, seg, G, st2.train, st2.eps, st2.momentum,
+                                                             float(slope2), _p(st2.mean), _p(st2.var), _p(zext), _p(arg),
+                                                             _p(coef2), _p(out), Co, _p(ws), _st())),
               'sug_pointmlp_max_layer_fwd_xf')
-        CTX.last_coef_pair = (coef1, coef2)
         ctx.need1, ctx.need2 = need1, need2
         if need1 or need2:
             ctx.save_for_backward(y2, coef1, z, w2, b1, zext, arg, coef2)
-            ctx.meta = (rows, K, Co, seg, G, float(slope1), float(slope2), bool(training), tuple(y.shape), tuple(weight.shape))
-        if not last_grad:
-            ctx.mark_non_differentiable(out)
+            ctx.meta = (rows, K, Co, seg, G, float(slope1), float(slope2), training, tuple(y.shape), tuple(weight.shape))
+        ctx.mark_non_differentiable(*((coef1, coef2) if last_grad else (coef1, coef2, out)))
         ctx.set_materialize_grads(False)
-        if z is None:
-            return out, None
-        return out, z.view(y.shape)
+        return out, (None if z is None else z.view(y.shape)), coef1, coef2
 
     @staticmethod
-    def backward(ctx, gout, gz):
+    def backward(ctx, gout, gz, _gcoef1, _gcoef2):
         if not (ctx.need1 or ctx.need2):
             # nothing was saved: neither the input nor any parameter of the two layers takes a gradient (a gradient that
             # still arrives at z -- want_z with the layers frozen -- has nowhere to go; ADVICE r5)
-            return (None,) * 23
+            return (None,) * 15
         y2, coef1, z, w2, b1, zext, arg, coef2 = ctx.saved_tensors
         rows, K, Co, seg, G, slope1, slope2, training, yshape, wshape = ctx.meta
         dz = dw = db = dg2 = db2 = None
@@ -1763,7 +1731,7 @@ class _BNActPointMLPMax(torch.autograd.Function):
         if ctx.need1 and dz is not None:
             dy, dg1, db1 = _bn_act_rows_backward(dz, y2, coef1, rows, K, slope1, training, G)
             dy = dy.view(yshape)
-        return (dy, dg1, db1, None, None, None, None, None, dw, db, dg2, db2) + (None,) * 11
+        return dy, dg1, db1, dw, db, dg2, db2, None, None, None, None, None, None, None, None
 
 
 def bn_act_pointmlp_max(y, bn1, slope1, weight, bias, bn2, slope2, seg, want_z=False, last_grad=True):
@@ -1776,13 +1744,11 @@ def bn_act_pointmlp_max(y, bn1, slope1, weight, bias, bn2, slope2, seg, want_z=F
         raise RuntimeError('bn_act_pointmlp_max: the two BatchNorm layers must be in the same mode (train / eval)')
     _count_bn_call(bn1)
     _count_bn_call(bn2)
-    out, z = _BNActPointMLPMax.apply(y, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, slope1, bn1.eps, bn1.momentum,
-                                     weight, bias, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, slope2, bn2.eps,
-                                     bn2.momentum, bn1.training, seg, CTX.bn_groups, want_z, last_grad, torch.is_grad_enabled())
-    if CTX.bn_record is not None:                      # a shared prefix replays these running-statistics updates (record_bn_stats)
-        for bn, coef in zip((bn1, bn2), CTX.last_coef_pair):
-            if bn.training and bn.track_running_stats:
-                CTX.bn_record.append((bn, coef))
+    out, z, coef1, coef2 = _BNActPointMLPMax.apply(y, bn1.weight, bn1.bias, weight, bias, bn2.weight, bn2.bias, _bn_state(bn1),
+                                                   slope1, _bn_state(bn2), slope2, seg, want_z, last_grad,
+                                                   torch.is_grad_enabled())
+    _record_bn(bn1, coef1)                             # a shared prefix replays these running-statistics updates (record_bn_stats)
+    _record_bn(bn2, coef2)
     return out, z
 
 
@@ -2677,6 +2643,9 @@ class _GateBN(torch.autograd.Function):
         return dx, dz, dgb[0], dgb[1], None, None, None, None, None
 
 
+GATE_BN_FUSED = _os.environ.get('SUG_GATE_BN_FUSED', '1') != '0'
+
+
 def gate_bn_supported(x, bn):
     return GATE_BN_FUSED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] <= 1024 and bn.affine and \
         (bn.training or bn.track_running_stats) and bn.momentum is not None and CTX.bn_groups == 1
@@ -2690,9 +2659,6 @@ def gate_bn(x, z, bn):
     track = bn.track_running_stats
     return _GateBN.apply(x, z, bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None,
                          bn.training or not track, bn.eps, bn.momentum)
-
-
-GATE_BN_FUSED = _os.environ.get('SUG_GATE_BN_FUSED', '1') != '0'
 
 
 class _EdgeWeightSplit(torch.autograd.Function):
@@ -2842,7 +2808,6 @@ def chamfer_weights(a, b, method):
     return out
 
 
-# ----------------------------------------------------------------------------- the old module-level names of the context fields
 # ----------------------------------------------------------------------------- KPConv backbone
 # Packed clouds (rows of all clouds of a level back to back) with int32 device offsets off [B+1]; neighbour tables
 # [Nq, H] int32 whose missing slots hold the shadow index Ns (sug_amd/csrc/kpconv.hip).
@@ -3084,7 +3049,8 @@ def _ctx_property(field):
 
 
 class _OpsModule(type(_os)):
-    """`ops.BN_GROUPS`, `ops.START_PROVIDER = f`, ... read and write CTX (see StepContext)."""
+    """The old module-level names of the context fields: `ops.BN_GROUPS`, `ops.START_PROVIDER = f`, ... read and write CTX
+    (see StepContext)."""
     BN_GROUPS = _ctx_property('bn_groups')
     START_QUEUE = _ctx_property('start_queue')
     START_PROVIDER = _ctx_property('start_provider')
@@ -3096,8 +3062,6 @@ class _OpsModule(type(_os)):
     W16_CACHE = _ctx_property('w16_cache')
     BN_RECORD = _ctx_property('bn_record')
     _PENDING_COUNTS = _ctx_property('pending_counts')
-    _LAST_COEF_PAIR = _ctx_property('last_coef_pair')
-    _LAST_COEF = _ctx_property('last_coef')
 
 
 import sys as _sys
