@@ -32,57 +32,10 @@ import weakref
 import torch
 
 from . import ops
+from .graph_replay import StartFeeder, refusal_text, tensor_outputs
 
 ENABLED = os.environ.get('SUG_CALL_GRAPHS', '1') != '0'
 MAX_INSTANCES_PER_KEY = 4
-
-
-class StartFeeder:
-    """FPS start indices for a replayable forward / step: drawn from the CPU default generator in call
-    order with the same (B, N) sequence as an eager run (so the random stream is the
-    reference's, model/point_utils.py:17), but delivered through one static device buffer."""
-
-    def __init__(self, device):
-        self.device = device
-        self.plan = []          # (B, N) per farthest_point_sample call
-        self.host = self.dev = None
-        self.cursor = 0
-
-    def record(self, B, N):     # provider during the eager planning run
-        self.plan.append((B, N))
-        return torch.randint(0, N, (B,), dtype=torch.long)
-
-    def build(self):
-        total = max(sum(b for b, _ in self.plan), 1)
-        # two pinned staging buffers, used alternately: the host must not overwrite one while its
-        # asynchronous copy to the device may still be pending (replays are not synchronised)
-        self.host = [torch.empty(total, dtype=torch.int32).pin_memory() for _ in range(2)]
-        self.done = [None, None]
-        self.turn = 0
-        self.dev = torch.zeros(total, dtype=torch.int32, device=self.device)
-
-    def refill(self):           # before every replay
-        if not self.plan:
-            return
-        h = self.host[self.turn]
-        if self.done[self.turn] is not None:
-            self.done[self.turn].synchronize()
-        off = 0
-        for B, N in self.plan:
-            h[off:off + B] = torch.randint(0, N, (B,), dtype=torch.long).to(torch.int32)
-            off += B
-        self.dev.copy_(h, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.done[self.turn] = ev
-        self.turn ^= 1
-
-    def provide(self, B, N):    # provider during capture
-        off = sum(b for b, _ in self.plan[:self.cursor])
-        assert self.cursor < len(self.plan) and self.plan[self.cursor] == (B, N), \
-            'forward structure changed between planning and capture'
-        self.cursor += 1
-        return self.dev[off:off + B]
 
 
 class _Unsupported(RuntimeError):
@@ -205,9 +158,7 @@ class CallGraphs:
 
     # ------------------------------------------------------------------ the call
     def _eligible(self, model, x):
-        if not (x.is_cuda and not x.requires_grad and ops.CTX.bn_groups == 1 and ops.CTX.start_queue is None and
-                ops.CTX.geometry_plan is None and ops.CTX.start_provider is None and ops.CTX.profile is None and
-                ops.CTX.bn_record is None):
+        if not (x.is_cuda and not x.requires_grad and ops.CTX.unscoped()):
             return False
         if torch.cuda.is_current_stream_capturing():
             return False
@@ -257,8 +208,7 @@ class CallGraphs:
             try:
                 inst = self._capture(model, ks, x, flags, dep)
             except Exception as e:      # capture refused: this key stays eager, in this process
-                ops.CTX.start_provider = None
-                ks.eager_only, ks.why = True, '%s: %s' % (type(e).__name__, str(e).splitlines()[0] if str(e) else '')
+                ks.eager_only, ks.why = True, refusal_text(e)
                 self.stats['refused'] += 1
                 if os.environ.get('SUG_CALL_GRAPHS_STRICT') == '1':
                     raise
@@ -275,17 +225,14 @@ class CallGraphs:
         if ks.plan is not None and ks.bwd_seen[0]:
             return model._forward_impl(x, *flags)
         feeder = StartFeeder(x.device)
-        ops.CTX.start_provider = feeder.record
-        try:
+        with feeder.recording():
             out = model._forward_impl(x, *flags)
-        finally:
-            ops.CTX.start_provider = None
         ks.plan = feeder.plan
         # a capture of this key waits until one eager backward has run (every GEMM shape of the key has then been looked
         # up outside a capture): any output's gradient hook says the backward has started, and the next forward call
         # cannot come before it has finished
         seen = ks.bwd_seen
-        for t in ([out] if isinstance(out, torch.Tensor) else (out or ())):
+        for t in tensor_outputs(out)[0]:
             if isinstance(t, torch.Tensor) and t.requires_grad:
                 t.register_hook(lambda g_, s=seen: s.__setitem__(0, True))
         return out
@@ -313,21 +260,18 @@ class CallGraphs:
         # captured gradient to them makes the engine synchronise the capture stream with the default stream, which
         # invalidates the capture (torch warns 'AccumulateGrad node's stream does not match'; hipStreamEndCapture crashed).
         alias = {id(q): q.detach().requires_grad_(q.requires_grad) for q in self._params}
-        ops.CTX.start_provider = inst.feeder.provide
         # 16-bit weight copies (Point Transformer, fp16 mode): a caller's step-scoped cache holds tensors made outside this
         # capture, for the parameters rather than their aliases -- the captured call keeps its OWN cache: every weight is cast
         # once per call, inside the graph, from the live parameter storage
         from .model import Ptran_transformer as _PT
-        keep_w16 = ops.CTX.w16_cache
-        ops.CTX.w16_cache = {} if (keep_w16 is not None or _PT.GEMM_DTYPE is not None) else None
+        own_w16 = {} if (ops.CTX.w16_cache is not None or _PT.GEMM_DTYPE is not None) else None
         try:
             for m_, n_, q in self._slots:
                 m_._parameters[n_] = alias[id(q)]
-            with ops.capture_guard(), torch.cuda.graph(inst.graph_f, capture_error_mode='thread_local'):
+            with ops.CTX.scoped(w16_cache=own_w16), inst.feeder.providing(), ops.capture_guard(), \
+                    torch.cuda.graph(inst.graph_f, capture_error_mode='thread_local'):
                 with ops.deferred_bn_counts():
                     out = model._forward_impl(inst.x, *flags)
-            if inst.feeder.cursor != len(inst.feeder.plan):
-                raise _Unsupported('the captured forward drew %d FPS starts, the eager one %d' % (inst.feeder.cursor, len(inst.feeder.plan)))
             if hasattr(g, 'last_prefix'):
                 e = g.last_prefix(inst.x)
                 if e is not None:
@@ -335,12 +279,9 @@ class CallGraphs:
                     if dep is None and bool(getattr(g, 'share_prefix', False)) and all(t.requires_grad for t in e.tensors):
                         exported = e
         finally:
-            ops.CTX.start_provider = None
-            ops.CTX.w16_cache = keep_w16
             for m_, n_, q in self._slots:
                 m_._parameters[n_] = q
-        inst.single = isinstance(out, torch.Tensor)
-        outs = [out] if inst.single else list(out if out is not None else ())
+        outs, inst.single = tensor_outputs(out)
         if not outs or not all(isinstance(t, torch.Tensor) and t.is_floating_point() and t.requires_grad for t in outs):
             raise _Unsupported('this forward mode does not return differentiable tensors only')
         pref = list(exported.tensors) if exported is not None else []

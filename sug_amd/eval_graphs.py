@@ -14,7 +14,7 @@ that loop launches kernel by kernel from Python.  This module replays it instead
   * a key is (signature, input shape, forward flags).  Its first call runs eagerly on the copy and records the
     farthest-point-sampling start plan; the second is captured (torch.no_grad, ops.capture_guard) and replayed at once; later
     calls copy the batch into the static input, draw the FPS starts from the CPU generator in call order
-    (call_graphs.StartFeeder: the random stream of the eager calls) and replay.  The last, partial batch of a test set is
+    (graph_replay.StartFeeder: the random stream of the eager calls) and replay.  The last, partial batch of a test set is
     a key of its own and replays from the second epoch on;
   * at most MAX_KEYS keys per runner and MAX_RUNNERS runners, least recently used first out (their graph pools are freed);
   * the eager call on the model handed in is used instead -- and the reason recorded in FALLBACKS -- when the model is in
@@ -32,7 +32,7 @@ import weakref
 import torch
 
 from . import ops
-from .call_graphs import StartFeeder
+from .graph_replay import LRU, StartFeeder, refusal_text, tensor_outputs
 
 MAX_KEYS = 8
 MAX_RUNNERS = 2
@@ -66,8 +66,7 @@ def fallback_reason(model, x):
         return 'KPConv: level sizes depend on the data'
     if any(m.training for m in model.modules()):
         return 'train mode'
-    if not (ops.CTX.bn_groups == 1 and ops.CTX.start_queue is None and ops.CTX.geometry_plan is None and
-            ops.CTX.start_provider is None and ops.CTX.profile is None and ops.CTX.bn_record is None):
+    if not ops.CTX.unscoped():
         return 'scoped ops.CTX field'
     if torch.cuda.is_current_stream_capturing():
         return 'capture in progress'
@@ -77,36 +76,15 @@ def fallback_reason(model, x):
 
 
 class _Key:
-    __slots__ = ('plan', 'graph', 'x', 'feeder', 'outs', 'single', 'eager_only', 'why')
+    __slots__ = ('graph', 'x', 'feeder', 'outs', 'single', 'eager_only', 'why')
 
     def __init__(self):
-        self.plan = self.graph = self.x = self.feeder = self.outs = self.why = None
+        self.why = None
         self.single = self.eager_only = False
+        self.release()
 
     def release(self):
         self.graph = self.x = self.feeder = self.outs = None
-
-
-class _LRU(collections.OrderedDict):
-    """An OrderedDict bounded to `limit` entries: get() marks an entry used, put() evicts the least recently used ones."""
-
-    def __init__(self, limit, on_evict):
-        super().__init__()
-        self.limit, self.on_evict = limit, on_evict
-
-    def get(self, k, default=None):
-        if k in self:
-            self.move_to_end(k)
-            return self[k]
-        return default
-
-    def put(self, k, v):
-        self[k] = v
-        self.move_to_end(k)
-        while len(self) > self.limit:
-            _, old = self.popitem(last=False)
-            self.on_evict(old)
-        return v
 
 
 def _release_key(ks):
@@ -126,7 +104,7 @@ class EvalRunner:
         sd = self.net.state_dict(keep_vars=True)
         self._names = list(sd.keys())
         self._dst = [t.detach() for t in sd.values()]
-        self.keys = _LRU(MAX_KEYS, _release_key)
+        self.keys = LRU(MAX_KEYS, _release_key)
         self.stats = {'eager': 0, 'captured': 0, 'replayed': 0, 'refused': 0, 'evicted': 0}
         self.why = None                         # reason of the last refused capture
         # Net_MDA's flags in the order of _forward_impl, defaults filled in: equal calls get equal keys
@@ -208,7 +186,7 @@ class EvalRunner:
             if ks.eager_only:
                 self.stats['eager'] += 1
                 return self._plain(x, flags)
-            if ks.plan is None:
+            if ks.feeder is None:               # first call of the key: eager, the feeder records the start plan
                 return self._eager_plan(ks, x, flags)
             if ks.graph is None:
                 try:
@@ -216,7 +194,7 @@ class EvalRunner:
                 except Exception as e:       # this key stays eager, in this process
                     ks.release()
                     ks.eager_only = True
-                    ks.why = self.why = '%s: %s' % (type(e).__name__, str(e).splitlines()[0] if str(e) else '')
+                    ks.why = self.why = refusal_text(e)
                     self.stats['refused'] += 1
                     return None
                 self.stats['captured'] += 1
@@ -230,44 +208,25 @@ class EvalRunner:
             return outs[0] if ks.single else tuple(outs)
 
     def _plain(self, x, flags):
-        keep = ops.CTX.w16_cache
-        ops.CTX.w16_cache = None
-        try:
+        with ops.CTX.scoped(w16_cache=None):
             return self.net(x, **flags)
-        finally:
-            ops.CTX.w16_cache = keep
 
     def _eager_plan(self, ks, x, flags):
         self.stats['eager'] += 1
         feeder = StartFeeder(x.device)
-        ops.CTX.start_provider = feeder.record
-        try:
+        with feeder.recording():
             out = self._plain(x, flags)
-        finally:
-            ops.CTX.start_provider = None
-        ks.plan = feeder.plan
+        ks.feeder = feeder              # (unbuilt: _capture gives it its buffers)
         return out
 
     def _capture(self, ks, x, flags):
-        dev = x.device
         ks.x = x.detach().clone()
-        ks.feeder = StartFeeder(dev)
-        ks.feeder.plan = list(ks.plan)
         ks.feeder.build()
         ks.graph = torch.cuda.CUDAGraph()
-        keep = ops.CTX.w16_cache
-        ops.CTX.w16_cache = None
-        ops.CTX.start_provider = ks.feeder.provide
-        try:
-            with ops.capture_guard(), torch.cuda.graph(ks.graph, capture_error_mode='thread_local'):
-                out = self.net(ks.x, **flags)
-        finally:
-            ops.CTX.start_provider = None
-            ops.CTX.w16_cache = keep
-        if ks.feeder.cursor != len(ks.feeder.plan):
-            raise RuntimeError('the captured forward drew %d FPS starts, the eager one %d' % (ks.feeder.cursor, len(ks.feeder.plan)))
-        ks.single = isinstance(out, torch.Tensor)
-        outs = [out] if ks.single else list(out)
+        with ops.CTX.scoped(w16_cache=None), ks.feeder.providing(), ops.capture_guard(), \
+                torch.cuda.graph(ks.graph, capture_error_mode='thread_local'):
+            out = self.net(ks.x, **flags)
+        outs, ks.single = tensor_outputs(out)
         if not outs or not all(isinstance(t, torch.Tensor) for t in outs):
             raise RuntimeError('this forward mode does not return tensors only')
         ks.outs = outs
@@ -279,7 +238,7 @@ class EvalRunner:
 
 
 # ---------------------------------------------------------------------- runners of the process
-_RUNNERS = _LRU(MAX_RUNNERS, lambda r: r.release())
+_RUNNERS = LRU(MAX_RUNNERS, lambda r: r.release())
 
 
 def runner_for(model):

@@ -797,12 +797,9 @@ class Net_MDA(nn.Module):
             # starts is the same stream and needs no concatenation.
             draws = [[ops.draw_group_start(B, n) for n in plan] for _ in range(2)]
             queue = [torch.cat((draws[0][c], draws[1][c])) for c in range(len(plan))]
-        keep_plan, ops.CTX.geometry_plan = ops.CTX.geometry_plan, (list(geometry) if geometry is not None else None)
-        try:
+        with ops.CTX.scoped(geometry_plan=list(geometry) if geometry is not None else None):
             out = self._forward_pair(x_pair, node_adaptation, paired_out, queue, B, B2, dual)
             left = len(ops.CTX.geometry_plan or ())
-        finally:
-            ops.CTX.geometry_plan = keep_plan
         if left:        # a planned entry nobody popped = a sampling stage that drew its start a second time
             raise RuntimeError('geometry plan of this pass was not consumed by the encoder (%d entries left)' % left)
         return out

@@ -37,7 +37,10 @@ class StepContext:
       fused_heads        fused LayerNorm + activation in the FC heads (SUGStep switches it on for its own forwards)
       w16_cache          step-scoped cache of 16-bit weight copies (Point Transformer, fp16 mode) or None
       bn_record          None, or the list collecting (BatchNorm module, batch-statistics coefficients) of a shared prefix
-      pending_counts     None, or the deferred num_batches_tracked increments of this pass"""
+      pending_counts     None, or the deferred num_batches_tracked increments of this pass
+
+    `scoped(**fields)` is the one way a field is set for the duration of a block; `unscoped()` says that no field which must
+    block a graph capture is set.  A new field of that kind is added to `unscoped()` and nowhere else."""
     __slots__ = ('bn_groups', 'start_queue', 'start_provider', 'geometry_plan', 'profile', 'profile_only', 'parallel_branches',
                  'fused_heads', 'w16_cache', 'bn_record', 'pending_counts')
 
@@ -48,6 +51,23 @@ class StepContext:
         self.parallel_branches = False
         self.fused_heads = False
         self.w16_cache = self.bn_record = self.pending_counts = None
+
+    @contextlib.contextmanager
+    def scoped(self, **fields):
+        """Set the named fields inside the block; on exit (also by an exception) they hold their values of entry again."""
+        old = {k: getattr(self, k) for k in fields}
+        for k, v in fields.items():
+            setattr(self, k, v)
+        try:
+            yield self
+        finally:
+            for k, v in old.items():
+                setattr(self, k, v)
+
+    def unscoped(self):
+        """True when every field that a captured graph would bake in (or that changes what a forward computes) is at rest."""
+        return self.bn_groups == 1 and self.start_queue is None and self.geometry_plan is None and \
+            self.start_provider is None and self.profile is None and self.bn_record is None
 
 
 CTX = StepContext()
@@ -109,25 +129,15 @@ def capture_guard():
             gc.enable()
 
 
-@contextlib.contextmanager
 def bn_groups(g):
     """The batch holds g domain groups (see StepContext.bn_groups) inside the block.  Everything per-cloud / per-row is
     oblivious to that; the BatchNorm ops compute statistics and update the running buffers per part, in order, so the result
     is the one of g separate calls."""
-    old, CTX.bn_groups = CTX.bn_groups, int(g)
-    try:
-        yield
-    finally:
-        CTX.bn_groups = old
+    return CTX.scoped(bn_groups=int(g))
 
 
-@contextlib.contextmanager
 def start_queue(q):
-    old, CTX.start_queue = CTX.start_queue, (list(q) if q is not None else None)
-    try:
-        yield
-    finally:
-        CTX.start_queue = old
+    return CTX.scoped(start_queue=list(q) if q is not None else None)
 
 
 def draw_start(B, N):
@@ -1224,11 +1234,8 @@ def _count_bn_call(bn, n=None):
 
 @contextlib.contextmanager
 def record_bn_stats():
-    prev, CTX.bn_record = CTX.bn_record, []
-    try:
+    with CTX.scoped(bn_record=[]):
         yield CTX.bn_record
-    finally:
-        CTX.bn_record = prev
 
 
 def _record_bn(bn, coef):

@@ -14,6 +14,7 @@ all-reduce per step; with `global_mmd=True` the MMD is the single-GPU loss of th
 batch (differentiable all-gather of the [m, D+10] features and of logits/labels for the SDA
 weights; backward = reduce-scatter), otherwise reference-style local MMD (train_dg.py).
 """
+import contextlib
 import os
 
 import torch
@@ -22,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .graph_replay import LRU, StartFeeder
 from .model import mmd
 
 GEO_MMD = {'NAME': 'SOFT_MMD', 'LABEL_SCALE': 50, 'GEO_SCALE': 1}
@@ -191,9 +193,6 @@ class GradReducer:
         self.flats = self.members = self.handles = None
 
 
-from .call_graphs import StartFeeder as _StartFeeder      # FPS start draws of a replayable step (moved there in round 6)
-
-
 class SUGStep:
     def __init__(self, model, lr=1e-3, weight_decay=5e-5, lr_scaler=1.0, methods=None, criterion=None,
                  global_mmd=True, fused_adam=None, share_prefix=True, use_graph=False, pair_domains=True,
@@ -240,9 +239,8 @@ class SUGStep:
         own_adam = on_gpu and (fused_adam is None or fused_adam)
         # hipGraph mode: the whole step (forwards, losses, backward, 3 Adam updates) is captured once and replayed, FPS
         # start indices fed through a static buffer.  One rank: one graph per configuration key;
-        # more ranks: five captured segments around the four collectives (_segmented_step).
+        # more ranks: five captured segments around the four collectives (_capture_segments).
         self.use_graph = bool(use_graph) and next(model.parameters()).is_cuda
-        # more than one rank: the step is captured as FIVE graph segments around its four collectives (_segmented_step)
         self.segmented = self.use_graph and (self.world > 1 or force_segmented)
         self._graphs = None
         self._total = None
@@ -515,56 +513,49 @@ class SUGStep:
         builds the Adam update plans OUTSIDE any capture), the second captures, later ones replay.  At most
         `max_graphs` captured steps are kept (least recently used first out); a graph whose optimizers have rebuilt
         their device-side plan since the capture (load_state_dict, ...) is dropped and captured again."""
-        mmd_on = epoch >= self.methods['PURE_CLS_EPOCH']
-        key = self._graph_key(mmd_on, (data, label, data_t, label_t))
+        batch = (data, label, data_t, label_t)
+        key = self._graph_key(epoch >= self.methods['PURE_CLS_EPOCH'], batch)
         if self._graphs is None:
-            self._graphs = {}
+            self._graphs = LRU(self.max_graphs)
         for o in self._opts():                              # a schedule step since the last replay: new lr -> device
             if hasattr(o, 'refresh_device_scalars'):
                 o.refresh_device_scalars()
-        st = self._graphs.get(key)
+        st = self._graphs.get(key)                          # (a hit is the most recently used key from here on)
         if st is not None and st.get('gens') is not None and st['gens'] != self._plan_generations():
             del self._graphs[key]                           # raw pointers into a freed Adam plan: never replay
             st = None
-        if self.segmented:
-            if st is None:
-                while len(self._graphs) >= self.max_graphs:
-                    self._graphs.pop(next(iter(self._graphs)))
-            return self._segmented_step(st, key, data, label, data_t, label_t, epoch)
+        # the whole-step and the segmented form supply what "run uncaptured", "capture" and "replay" mean
+        seg = self.segmented
+        slot = 'graphs' if seg else 'graph'
         if st is None:
-            while len(self._graphs) >= self.max_graphs:
-                self._graphs.pop(next(iter(self._graphs)))  # dicts keep insertion order; a hit re-inserts (below)
-            st = {'feeder': _StartFeeder(data.device), 'graph': None, 'gens': None}
-            self._graphs[key] = st
-            ops.CTX.start_provider = st['feeder'].record
-            try:
-                out = self._eager_step(data, label, data_t, label_t, epoch)
-            finally:
-                ops.CTX.start_provider = None
+            self._graphs.limit = self.max_graphs
+            st = self._graphs.put(key, {'feeder': StartFeeder(data.device), slot: None, 'gens': None})
+            with st['feeder'].recording():
+                out = self._plan_segments(st, batch, epoch) if seg else self._eager_step(*batch, epoch)
             st['feeder'].build()
             return out
-        self._graphs[key] = self._graphs.pop(key)           # most recently used last
-        if st['graph'] is None:
-            st['in'] = [t.clone() for t in (data, label, data_t, label_t)]
+        if st[slot] is None:
+            st['in'] = [t.clone() for t in batch]
             for o in self._opts():
                 o.zero_grad(set_to_none=True)
-            st['feeder'].cursor = 0
-            st['graph'] = torch.cuda.CUDAGraph()
-            if os.environ.get('SUG_GRAPH_DUMP'):
-                st['graph'].enable_debug_mode()
-            ops.CTX.start_provider = st['feeder'].provide
-            try:
-                with ops.capture_guard(), torch.cuda.graph(st['graph']):
-                    st['out'] = self._eager_step(*st['in'], epoch)
-            finally:
-                ops.CTX.start_provider = None
+            (self._capture_segments if seg else self._capture_whole)(st, key, epoch)
             st['gens'] = self._plan_generations()
-            if os.environ.get('SUG_GRAPH_DUMP'):
-                st['graph'].debug_dump(os.environ['SUG_GRAPH_DUMP'])
-        for dst, src in zip(st['in'], (data, label, data_t, label_t)):
+        for dst, src in zip(st['in'], batch):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src, non_blocking=True)
         st['feeder'].refill()
+        return self._replay_segments(st) if seg else self._replay_whole(st)
+
+    def _capture_whole(self, st, key, epoch):
+        st['graph'] = torch.cuda.CUDAGraph()
+        if os.environ.get('SUG_GRAPH_DUMP'):
+            st['graph'].enable_debug_mode()
+        with st['feeder'].providing(), ops.capture_guard(), torch.cuda.graph(st['graph']):
+            st['out'] = self._eager_step(*st['in'], epoch)
+        if os.environ.get('SUG_GRAPH_DUMP'):
+            st['graph'].debug_dump(os.environ['SUG_GRAPH_DUMP'])
+
+    def _replay_whole(self, st):
         if self._tick is not None:
             # Historical guard (SUG_GRAPH_GUARD=1): an early round-1 version of the step faulted in its second
             # back-to-back replay (a torch scatter kernel that has since left the step read out-of-range indices; an
@@ -610,44 +601,36 @@ class SUGStep:
         gloo_gpu = dist.get_backend() == 'gloo'
 
         def seg_a(S):
-            from .model import Ptran_transformer as _PT
-            ops.CTX.w16_cache = ops.w16_prefill(getattr(self, '_w16_plan', None) or []) if _PT.GEMM_DTYPE is not None else None
-            fused_before, ops.CTX.fused_heads = ops.CTX.fused_heads, (self.fused_heads or ops.CTX.fused_heads)
-            par_before, ops.CTX.parallel_branches = ops.CTX.parallel_branches, (self.parallel_branches or ops.CTX.parallel_branches)
-            try:
-                model._cuts = S['cuts'] = []
-                pair = torch.cat((data, data_t), dim=0)
-                dual = self.single_pass and mmd_on
-                if mmd_on and not dual and hasattr(model, 'plan_pair_geometry') and os.environ.get('SUG_PLAN_GEOMETRY', '1') != '0':
-                    model.plan_pair_geometry(pair, passes=2)
-                if dual:
-                    (p_s1, p_s2, f_s1, f_s2), (p_t1, p_t2, f_t1, f_t2), (node_s, node_t) = model.forward_pair(pair, dual=True)
-                else:
-                    (p_s1, p_s2, f_s1, f_s2), (p_t1, p_t2, f_t1, f_t2) = model.forward_pair(pair)
-                S['loss_cls'] = (0.5 * M_['SRC_LOSS_WEIGHT'] * M_['CLS_WEIGHT']) * (self.criterion(p_s1, label) +
-                                                                                   self.criterion(p_s2, label))
-                if mmd_on:
-                    if not dual:
-                        node_s, node_t = model.forward_pair(pair, node_adaptation=True)
-                    S['loc'] = (node_s, node_t, f_s1, f_t1, f_s2, f_t2)
-                    vals = [label, label_t, node_s.detach(), node_t.detach(), f_s1.detach(), f_t1.detach(), f_s2.detach(),
-                            f_t2.detach(), p_s1.detach(), p_t1.detach(), p_s2.detach(), p_t2.detach()]
-                    if geo.get('GEO_WEIGHTS'):
-                        vals.append(mmd.chamfer_distances(data, data_t).reshape(-1, 1))
-                    cols, meta = [], []
-                    for t in vals:
-                        t2 = t.reshape(t.shape[0], -1)
-                        meta.append((t2.shape[1], t.dtype, tuple(t.shape[1:])))
-                        cols.append(t2 if t2.dtype == torch.float32 else t2.to(torch.float32))
-                    S['meta'] = meta
-                    S['packed'] = torch.cat(cols, dim=1)
-            finally:
-                model._cuts = None
-                ops.CTX.fused_heads = fused_before
-                ops.CTX.parallel_branches = par_before
-                if ops.CTX.w16_cache is not None:
-                    self._w16_plan = ops.w16_plan(ops.CTX.w16_cache)
-                ops.CTX.w16_cache = None
+            with self._step_scope():
+                try:
+                    model._cuts = S['cuts'] = []
+                    pair = torch.cat((data, data_t), dim=0)
+                    dual = self.single_pass and mmd_on
+                    if mmd_on and not dual and hasattr(model, 'plan_pair_geometry') and os.environ.get('SUG_PLAN_GEOMETRY', '1') != '0':
+                        model.plan_pair_geometry(pair, passes=2)
+                    if dual:
+                        (p_s1, p_s2, f_s1, f_s2), (p_t1, p_t2, f_t1, f_t2), (node_s, node_t) = model.forward_pair(pair, dual=True)
+                    else:
+                        (p_s1, p_s2, f_s1, f_s2), (p_t1, p_t2, f_t1, f_t2) = model.forward_pair(pair)
+                    S['loss_cls'] = (0.5 * M_['SRC_LOSS_WEIGHT'] * M_['CLS_WEIGHT']) * (self.criterion(p_s1, label) +
+                                                                                       self.criterion(p_s2, label))
+                    if mmd_on:
+                        if not dual:
+                            node_s, node_t = model.forward_pair(pair, node_adaptation=True)
+                        S['loc'] = (node_s, node_t, f_s1, f_t1, f_s2, f_t2)
+                        vals = [label, label_t, node_s.detach(), node_t.detach(), f_s1.detach(), f_t1.detach(), f_s2.detach(),
+                                f_t2.detach(), p_s1.detach(), p_t1.detach(), p_s2.detach(), p_t2.detach()]
+                        if geo.get('GEO_WEIGHTS'):
+                            vals.append(mmd.chamfer_distances(data, data_t).reshape(-1, 1))
+                        cols, meta = [], []
+                        for t in vals:
+                            t2 = t.reshape(t.shape[0], -1)
+                            meta.append((t2.shape[1], t.dtype, tuple(t.shape[1:])))
+                            cols.append(t2 if t2.dtype == torch.float32 else t2.to(torch.float32))
+                        S['meta'] = meta
+                        S['packed'] = torch.cat(cols, dim=1)
+                finally:
+                    model._cuts = None
 
         def col_gather(S):
             if not mmd_on:
@@ -801,31 +784,21 @@ class SUGStep:
                 col[i](S)
         return S['out']
 
-    def _segmented_step(self, st, key, data, label, data_t, label_t, epoch):
-        """Graph mode on more than one rank: plan (uncaptured), capture the segments into hipGraphs that share one memory
-        pool, then per step: replay A, all-gather, replay B, all-reduce, replay C1, all-reduce (async), replay C2, all-reduce, replay D."""
-        if st is None:
-            st = {'feeder': _StartFeeder(data.device), 'graphs': None, 'gens': None, 'S': {}}
-            self._graphs[key] = st
-            ops.CTX.start_provider = st['feeder'].record
-            try:
-                out = self._run_segments(self._segments(data, label, data_t, label_t, epoch), st['S'])
-            finally:
-                ops.CTX.start_provider = None
-            st['feeder'].build()
-            st['S'] = {'static': st['S']['static']}         # keep only the collective buffers
-            return out
-        self._graphs[key] = self._graphs.pop(key)
-        if st['graphs'] is None:
-            st['in'] = [t.clone() for t in (data, label, data_t, label_t)]
-            for o in self._opts():
-                o.zero_grad(set_to_none=True)
-            st['feeder'].cursor = 0
-            segs = self._segments(*st['in'], epoch)
-            S = st['S']
-            graphs, pool, err = [], None, None
-            ops.CTX.start_provider = st['feeder'].provide
-            try:
+    # Graph mode on more than one rank (_graph_step's segmented form): plan (uncaptured), capture the segments into hipGraphs
+    # that share one memory pool, then per step: replay A, all-gather, replay B, all-reduce, replay C1, all-reduce (async),
+    # replay C2, all-reduce, replay D.
+    def _plan_segments(self, st, batch, epoch):
+        S = {}
+        out = self._run_segments(self._segments(*batch, epoch), S)
+        st['S'] = {'static': S['static']}                   # keep only the collective buffers
+        return out
+
+    def _capture_segments(self, st, key, epoch):
+        segs = self._segments(*st['in'], epoch)
+        S = st['S']
+        graphs, pool, err = [], None, None
+        try:
+            with st['feeder'].providing():
                 for fn in segs['device']:
                     g = torch.cuda.CUDAGraph()
                     # thread_local: the process group's watchdog thread queries events of finished collectives while
@@ -834,31 +807,26 @@ class SUGStep:
                         fn(S)
                     pool = g.pool() if pool is None else pool
                     graphs.append(g)
-            except RuntimeError as e:                      # (reported below, after every rank has been heard)
-                err = e
-            finally:
-                ops.CTX.start_provider = None
-            # the ranks must agree before the first replay: a rank whose capture failed would otherwise meet the others'
-            # all-gather with a different collective.  One flag all-reduce per capture (not per step).
-            ok = torch.tensor([0.0 if err is not None else 1.0], device=data.device)
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-            if float(ok.item()) < 1.0:
-                self._graphs.pop(key, None)
-                for o in self._opts():                    # gradients of the aborted capture point into its discarded pool
-                    o.zero_grad(set_to_none=True)
-                if self.share_prefix:
-                    self.model.g.clear_prefix_cache()
-                raise RuntimeError('segmented hipGraph capture failed on %s: %s' % (
-                    'this rank' if err is not None else 'another rank', str(err).splitlines()[0] if err is not None else ''))
-            st['graphs'], st['segs'], st['out'] = graphs, segs, S['out']
-            st['gens'] = self._plan_generations()
-            # autograd objects of the capture are no longer needed: the graphs own the memory
-            for k in ('loc', 'terms', 'loss_cls', 'cuts', 'cut_grads'):
-                S.pop(k, None)
-        for dst, src in zip(st['in'], (data, label, data_t, label_t)):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src, non_blocking=True)
-        st['feeder'].refill()
+        except RuntimeError as e:                          # (reported below, after every rank has been heard)
+            err = e
+        # the ranks must agree before the first replay: a rank whose capture failed would otherwise meet the others'
+        # all-gather with a different collective.  One flag all-reduce per capture (not per step).
+        ok = torch.tensor([0.0 if err is not None else 1.0], device=segs['device_of'])
+        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+        if float(ok.item()) < 1.0:
+            self._graphs.pop(key, None)
+            for o in self._opts():                        # gradients of the aborted capture point into its discarded pool
+                o.zero_grad(set_to_none=True)
+            if self.share_prefix:
+                self.model.g.clear_prefix_cache()
+            raise RuntimeError('segmented hipGraph capture failed on %s: %s' % (
+                'this rank' if err is not None else 'another rank', str(err).splitlines()[0] if err is not None else ''))
+        st['graphs'], st['segs'], st['out'] = graphs, segs, S['out']
+        # autograd objects of the capture are no longer needed: the graphs own the memory
+        for k in ('loc', 'terms', 'loss_cls', 'cuts', 'cut_grads'):
+            S.pop(k, None)
+
+    def _replay_segments(self, st):
         S, col = st['S'], st['segs']['collective']
         ev = self.collective_events
         for i, (g, c) in enumerate(zip(st['graphs'], col + (None,))):
@@ -889,23 +857,26 @@ class SUGStep:
                     sizes[name] = stat[key].numel() * stat[key].element_size()
         return {'ms': out, 'bytes': sizes}
 
-    def _eager_step(self, data, label, data_t, label_t, epoch=0):
-        mmd_on = epoch >= self.methods['PURE_CLS_EPOCH']
+    @contextlib.contextmanager
+    def _step_scope(self):
+        """The forwards of one step: the trainer's `fused_heads` / `parallel_branches` switched on (if it or the context
+        asks), and 16-bit weight copies shared by them -- from the second step on refreshed by one multi-tensor copy into the
+        first step's buffers (`_w16_plan`)."""
         from .model import Ptran_transformer as _PT
-        # 16-bit weight copies shared by this step's forwards; from the second step on they are refreshed by one
-        # multi-tensor copy into the first step's buffers
         ops.CTX.w16_cache = ops.w16_prefill(getattr(self, '_w16_plan', None) or []) if _PT.GEMM_DTYPE is not None else None
-        fused_before, ops.CTX.fused_heads = ops.CTX.fused_heads, (self.fused_heads or ops.CTX.fused_heads)
-        par_before, ops.CTX.parallel_branches = ops.CTX.parallel_branches, (self.parallel_branches or ops.CTX.parallel_branches)
         try:
-            with ops.deferred_bn_counts():            # every num_batches_tracked increment of the step's forwards: one launch
-                loss_cls, loss_geo, loss_sem = self.losses(data, label, data_t, label_t, mmd_on, combine=True)
+            with ops.CTX.scoped(fused_heads=self.fused_heads or ops.CTX.fused_heads,
+                                parallel_branches=self.parallel_branches or ops.CTX.parallel_branches):
+                yield
         finally:
-            ops.CTX.fused_heads = fused_before
-            ops.CTX.parallel_branches = par_before
             if ops.CTX.w16_cache is not None:
                 self._w16_plan = ops.w16_plan(ops.CTX.w16_cache)
             ops.CTX.w16_cache = None
+
+    def _eager_step(self, data, label, data_t, label_t, epoch=0):
+        mmd_on = epoch >= self.methods['PURE_CLS_EPOCH']
+        with self._step_scope(), ops.deferred_bn_counts():    # every num_batches_tracked increment of the step's forwards: one launch
+            loss_cls, loss_geo, loss_sem = self.losses(data, label, data_t, label_t, mmd_on, combine=True)
         loss = getattr(self, '_total', None)             # set by losses() when the tail was combined in one launch
         self._total = None
         if loss is None:

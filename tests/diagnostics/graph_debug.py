@@ -5,7 +5,8 @@ import torch
 from bench import synth
 from sug_amd import ops
 from sug_amd.model.Model import Net_MDA
-from sug_amd.train_step import SUGStep, _StartFeeder
+from sug_amd.graph_replay import StartFeeder
+from sug_amd.train_step import SUGStep
 
 B = int(os.environ.get('B', 32)); STEPS = int(os.environ.get('STEPS', 6))
 share = os.environ.get('SHARE', '1') == '1'
@@ -30,7 +31,7 @@ if os.environ.get('GOLD') == '1':
     data = [G['data'].cuda(), G['label'].cuda(), G['data_t'].cuda(), G['label_t'].cuda()]
 if os.environ.get('FEED_EAGER') == '1':
     tr = SUGStep(net, share_prefix=share, use_graph=False)
-    fd = _StartFeeder(dev)
+    fd = StartFeeder(dev)
     ops.START_PROVIDER = fd.record
     tr.step(*data); torch.cuda.synchronize()
     fd.build()

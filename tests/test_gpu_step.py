@@ -535,12 +535,25 @@ def test_prefix_cache_is_keyed_on_tensor_identity_not_on_the_address(model_name)
     xa, xb = O.synth_clouds(2, 1024, g), O.synth_clouds(2, 1024, g)
     outs = []
     with torch.no_grad():
-        a = xa.cuda()
+        # The first batch sits BETWEEN two live allocations of its own size: its block can then not merge with a freed
+        # neighbour when it is released, stays an exact fit for the second batch, and the allocator (best fit, lowest
+        # address first) hands it out again once the other exact fits are taken -- without the fence the reuse depended on
+        # what the forward's temporaries left free around the block.
+        fence = [xa.cuda() for _ in range(16)]
+        size = -(-fence[0].numel() * fence[0].element_size() // 512) * 512      # the allocator's granularity
+        ptrs = {t.data_ptr() for t in fence}
+        mid = [i for i, t in enumerate(fence) if t.data_ptr() - size in ptrs and t.data_ptr() + size in ptrs]
+        if not mid:
+            pytest.skip('no three adjacent allocations among %s' % sorted('%x' % p for p in ptrs))
+        a = fence.pop(mid[0])
         addr = a.data_ptr()
         torch.manual_seed(1)
         nets[0](a, mid_feat=True)
         del a
         b = xb.cuda()
+        while b.data_ptr() != addr and len(fence) < 80:
+            fence.append(b)                 # another exact fit at a lower address: keep it, ask again
+            b = xb.cuda()
         if b.data_ptr() != addr:
             pytest.skip('the allocator did not reuse the address (%x vs %x)' % (b.data_ptr(), addr))
         assert b._version == 0
