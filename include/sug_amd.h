@@ -768,6 +768,21 @@ int sug_ce_pair_fwd(const float* logits1, const float* logits2, int64_t ld, cons
  * the pair's gradient). */
 int sug_ce_pair_bwd(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int M, int Mtot, int C,
                     float w, int64_t ignore_index, const float* g, const float* lse, float* d1, float* d2, void* stream);
+/* Cross entropy of ONE classifier head, the source-only loop's loss (train_source.py:86, :120):
+ * nn.CrossEntropyLoss(reduction='mean', ignore_index, label_smoothing) of logits [M, C] (fp32, row stride ld >= C) against
+ * label int64 [M]: loss[0] = mean over the counting rows of (1-eps)*(lse - z[label]) + eps * mean_c(lse - z_c); lse [M + 1] =
+ * the rows' log-sum-exp, lse[M] = the number of counting rows.  Labels as sug_ce_pair_fwd takes them (ignore_index rows are
+ * skipped and left out of the mean; any other label outside [0, C) makes loss and gradient NaN; no counting row: NaN, as
+ * torch).  totals (device double[2], may be null) keeps the epoch's books in the same launch, train_source.py:130-131 without
+ * the .item(): totals[0] += (double)loss * M, totals[1] += M (M, not the counting rows, as the reference).
+ * 1 <= M <= 1024, 2 <= C <= 64, checked on the host before any launch (-1, sug_last_error()).  One workgroup, a wave per row;
+ * the rows' terms are summed in fp64 in one fixed order; no float atomics, no memset node: capturable. */
+int sug_ce_fwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index, float label_smoothing,
+               float* loss, float* lse, double* totals, void* stream);
+/* Its gradient: dlogits [M, C] (dense) = g[0] * (softmax - target) / lse[M] in the counting rows, target =
+ * (1-eps)*onehot + eps/C; zero in ignored rows. */
+int sug_ce_bwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index, float label_smoothing,
+               const float* g, const float* lse, float* dlogits, void* stream);
 /* out3 = { loss_cls + wg*v_geo + ws*(v_sem1 + v_sem2), wg*v_geo, ws*(v_sem1 + v_sem2) } (train_dg_single_gpu.py:314-324; the
  * weights MMD_WEIGHT * GEO_SCALE and 0.5 * MMD_WEIGHT * SEM_SCALE folded by the caller); null v_* = term absent.
  * Backward: out4 = g[0] * {1, wg, ws, ws}. */

@@ -84,6 +84,76 @@ __global__ void loss_combine_bwd_kernel(const float* __restrict__ g, float wg, f
     out[0] = gv; out[1] = wg * gv; out[2] = ws * gv; out[3] = ws * gv;
   }
 }
+// ---- single-head cross entropy of the source-only loop (train_source.py:120, :130-131) ----------------------------------
+// One workgroup of up to 16 waves: a WAVE per row, a LANE per class (C <= 64), so a row is one coalesced load and its max /
+// sum are cross-lane reductions of one fixed shape (DPP max, xor butterfly); the rows' terms meet in LDS and wave 0 folds them
+// in fp64 -- lane l takes rows l, l + 64, ... in order, then the butterfly -- an order that does not depend on the number of
+// waves launched.  Thread 0 writes the loss and keeps the epoch's books (plain fp64 read-modify-write: one workgroup, stream
+// order).
+constexpr int CE1_MAXC = 64;
+constexpr int CE1_MAXROWS = 1024;
+
+__global__ __launch_bounds__(1024) void ce_fwd_kernel(const float* __restrict__ logits, int64_t ld,
+                                                      const int64_t* __restrict__ label, int M, int C, int64_t ignore_index,
+                                                      float eps, float* __restrict__ loss, float* __restrict__ lse,
+                                                      double* __restrict__ totals) {
+  __shared__ float s_term[CE1_MAXROWS];
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nwave = blockDim.x / WAVE;
+  for (int r = wave; r < M; r += nwave) {                 // wave-uniform trip count
+    const float* row = logits + (int64_t)r * ld;
+    const bool in = lane < C;
+    const float z = in ? row[lane] : -INFINITY;
+    const float mx = wave_max_f(z);
+    const float l = mx + logf(wave_sum_f(in ? expf(z - mx) : 0.f));     // logsumexp of the row
+    // label contract of sug_ce_pair_fwd: ignore_index rows count for nothing, any other label outside [0, C) poisons the loss
+    const int64_t y = label[r];
+    float term = 0.f;
+    if (y != ignore_index) {
+      term = (y < 0 || y >= C) ? NAN : l - row[y];                      // -log_softmax(row)[y]
+      if (eps > 0.f) term = (1.f - eps) * term + (eps / (float)C) * wave_sum_f(in ? l - z : 0.f);
+    }
+    if (lane == 0) {
+      lse[r] = l;
+      s_term[r] = term;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    double a = 0.0;
+    int cnt = 0;
+    for (int i = lane; i < M; i += WAVE) {
+      a += (double)s_term[i];
+      cnt += label[i] != ignore_index;
+    }
+    a = wave_sum_d(a);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) {
+      const float v = (float)(a / (double)cnt);           // no row counts -> 0 / 0 = NaN, as torch
+      lse[M] = (float)cnt;                                // the backward divides by it
+      loss[0] = v;
+      if (totals) {                                       // loss_total += loss.item() * data.size(0); data_total += data.size(0)
+        totals[0] += (double)v * (double)M;
+        totals[1] += (double)M;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ label,
+                                                     int M, int C, int64_t ignore_index, float eps, const float* __restrict__ g,
+                                                     const float* __restrict__ lse, float* __restrict__ d) {
+  const int n = M * C;                                    // <= 65536
+  const float f = g[0] / lse[M], on = 1.f - eps + eps / (float)C, off = eps / (float)C;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
+    const int r = e / C, c = e - r * C;
+    const int64_t y = label[r];
+    float v = 0.f;
+    if (y != ignore_index)
+      v = (y < 0 || y >= C) ? NAN : f * (expf(logits[(int64_t)r * ld + c] - lse[r]) - (c == y ? on : off));
+    d[e] = v;
+  }
+}
 }  // namespace
 
 extern "C" int sug_ce_pair_fwd(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int M, int C,
@@ -105,6 +175,33 @@ extern "C" int sug_ce_pair_bwd(const float* logits1, const float* logits2, int64
   hipLaunchKernelGGL(ce_pair_bwd_kernel, dim3((unsigned)sug_divup(n, 256)), dim3(256), 0, (hipStream_t)stream, logits1, logits2, ld,
                      label, M, Mtot, C, w, ignore_index, g, lse, d1, d2);
   SUG_LAUNCH_CHECK("sug_ce_pair_bwd");
+  return SUG_OK;
+}
+
+extern "C" int sug_ce_fwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index,
+                          float label_smoothing, float* loss, float* lse, double* totals, void* stream) {
+  SUG_REQUIRE(M >= 1 && M <= CE1_MAXROWS && C >= 2 && C <= CE1_MAXC && ld >= C,
+              "sug_ce_fwd: unsupported shape M=%d rows, C=%d classes, ld=%lld (1 <= M <= %d, 2 <= C <= %d, ld >= C)", M, C,
+              (long long)ld, CE1_MAXROWS, CE1_MAXC);
+  SUG_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "sug_ce_fwd: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  SUG_REQUIRE(logits && label && loss && lse, "sug_ce_fwd: null pointer");
+  const int waves = M < 16 ? M : 16;
+  hipLaunchKernelGGL(ce_fwd_kernel, dim3(1), dim3(WAVE * waves), 0, (hipStream_t)stream, logits, ld, label, M, C, ignore_index,
+                     label_smoothing, loss, lse, totals);
+  SUG_LAUNCH_CHECK("sug_ce_fwd");
+  return SUG_OK;
+}
+
+extern "C" int sug_ce_bwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index,
+                          float label_smoothing, const float* g, const float* lse, float* dlogits, void* stream) {
+  SUG_REQUIRE(M >= 1 && M <= CE1_MAXROWS && C >= 2 && C <= CE1_MAXC && ld >= C,
+              "sug_ce_bwd: unsupported shape M=%d rows, C=%d classes, ld=%lld (1 <= M <= %d, 2 <= C <= %d, ld >= C)", M, C,
+              (long long)ld, CE1_MAXROWS, CE1_MAXC);
+  SUG_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "sug_ce_bwd: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  SUG_REQUIRE(logits && label && g && lse && dlogits, "sug_ce_bwd: null pointer");
+  hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)sug_divup((int64_t)M * C, 256)), dim3(256), 0, (hipStream_t)stream, logits, ld,
+                     label, M, C, ignore_index, label_smoothing, g, lse, dlogits);
+  SUG_LAUNCH_CHECK("sug_ce_bwd");
   return SUG_OK;
 }
 

@@ -203,6 +203,8 @@ def _split_clouds(x):
 class KPFCls(nn.Module):
     """model/KPConv_model.py:60-90.  B = 1 works here (the reference builds an empty cloud list for it)."""
 
+    graph_capturable = False        # level sizes depend on the data, as KPConv_g's: SourceStep runs it eagerly
+
     def __init__(self, config=None, increase_channel_when_downsample=True):
         super().__init__()
         self.config = KPConvConfig if config is None else config

@@ -2137,6 +2137,54 @@ def ce_pair(y1, y2, label, w, ignore_index=-100):
     return _CEPair.apply(y1, y2, label, w, ignore_index)
 
 
+CE_MAX_ROWS, CE_MAX_CLASSES = 1024, 64
+
+
+class _CE(torch.autograd.Function):
+    """nn.CrossEntropyLoss(reduction='mean', ignore_index, label_smoothing) of ONE head in one launch each way
+    (sug_ce_fwd / sug_ce_bwd); the forward's launch also adds (loss * M, M) to the caller's `totals`."""
+
+    @staticmethod
+    def forward(ctx, y, label, ignore_index, label_smoothing, totals):
+        _need_gpu(y, label, totals)
+        if y.dim() != 2 or y.dtype != torch.float32 or label.numel() != y.shape[0]:
+            raise RuntimeError('ops.ce: fp32 logits [M, C] and M labels (got %s %s, %d labels)' % (tuple(y.shape), y.dtype, label.numel()))
+        if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 2 or not totals.is_contiguous()):
+            raise RuntimeError('ops.ce: totals is a contiguous float64 tensor of 2 elements')
+        M, C = y.shape
+        a = y if (y.stride(1) == 1 and y.stride(0) >= C) else y.contiguous()
+        lab = label.reshape(-1).long().contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=y.device)
+        lse = torch.empty(M + 1, dtype=torch.float32, device=y.device)          # + the number of counting rows
+        check(lib().sug_ce_fwd(_p(a), a.stride(0), _p(lab), M, C, int(ignore_index), float(label_smoothing), _p(loss), _p(lse),
+                               _p(totals), _st()), 'sug_ce_fwd')
+        ctx.save_for_backward(a, lab, lse)
+        ctx.meta = (M, C, int(ignore_index), float(label_smoothing))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, lab, lse = ctx.saved_tensors
+        M, C, ign, eps = ctx.meta
+        gs = g.detach().to(dtype=torch.float32).reshape(1)
+        d = torch.empty(M, C, dtype=torch.float32, device=a.device)
+        check(lib().sug_ce_bwd(_p(a), a.stride(0), _p(lab), M, C, ign, eps, _p(gs), _p(lse), _p(d), _st()), 'sug_ce_bwd')
+        return d, None, None, None, None
+
+
+def ce_supported(y, label):
+    return y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and 1 <= y.shape[0] <= CE_MAX_ROWS \
+        and 2 <= y.shape[1] <= CE_MAX_CLASSES and label.numel() == y.shape[0]
+
+
+def ce(logits, label, ignore_index=-100, label_smoothing=0.0, totals=None):
+    """logits [M, C] fp32 (any row stride), label [M] -> 0-d loss = nn.CrossEntropyLoss(ignore_index=..., label_smoothing=...)
+    with ce_pair's label semantics (ignore_index rows skipped, any other label outside [0, C) -> NaN).  totals: None or a
+    device float64 [2] that the same launch advances by (loss * M, M) -- the epoch's books of train_source.py:130-131.
+    1 <= M <= 1024, 2 <= C <= 64 (the library refuses anything else)."""
+    return _CE.apply(logits, label, ignore_index, label_smoothing, totals)
+
+
 class _LossCombine(torch.autograd.Function):
     """(loss_cls + wg*v_geo + ws*(v_sem1 + v_sem2), wg*v_geo, ws*(v_sem1 + v_sem2)) in one launch each way; the two parts
     are returned for reporting only (non-differentiable)."""
