@@ -922,6 +922,40 @@ int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B,
                       uint64_t seed, const uint64_t* counter, float sigma, float clip, float* out,
                       float* angles_out, float* noise_out, int32_t* sel_out, void* stream);
 
+/* ---- Batched point-to-point ICP fitness (the geometric sub-domain splitter, dataset_splitter.py:217-231) ----------------
+ * icp_distance() calls open3d's registration_icp(source, target, max_correspondence_distance=0.15) once per cloud; this
+ * entry point registers B (source, target) pairs in one launch, one workgroup per pair.  src [B or 1, Ns, 3] fp32 with
+ * src_batch_stride in floats: 0 = one source for all pairs (the splitter's anchor), else 3*Ns; tgt [B, Nt, 3] fp32.
+ * Per pair: count [B] (correspondences of the last evaluation; fitness = count / Ns), rmse [B] (inlier RMSE), iters [B]
+ * (updates applied), transform [B, 4, 4] row-major (the accumulated source -> target transform).
+ *
+ * open3d cannot be run where this library is built or tested, so what follows is a RESTATEMENT of its registration_icp with
+ * the defaults (identity init, TransformationEstimationPointToPoint without scaling, ICPConvergenceCriteria(1e-6, 1e-6,
+ * 30)) under these assumptions: (a) open3d converts the points to double and works in double; (b) its KD-tree radius
+ * search returns the exact nearest neighbour and accepts it when d2 < r*r, strictly; which of two equidistant targets it
+ * returns is not specified there, here the lowest index wins; (c) the update is Eigen::umeyama without scaling, i.e.
+ * the formula below; (d) the source cloud is transformed cumulatively by each update, not from the composed transform.
+ *   evaluate: for each moving source point p the target q of least d2 = (dx*dx + dy*dy) + dz*dz on direct differences
+ *     (fp64 on the fp32 input values, no fma), ties -> lowest index; a correspondence when d2 < r*r;
+ *     count = their number, rmse = sqrt(sum d2 / count), 0 when count == 0.
+ *   loop: result = evaluate; at most max_iteration times: { stop if count == 0;  with the means pbar, qbar and
+ *     Sigma = (1/n) sum (q - qbar)(p - pbar)^T = U S V^T:  R = U diag(1, 1, sign(det U det V)) V^T, t = qbar - R pbar;
+ *     p <- R p + t for every source point; transform <- [R t; 0 1] . transform; keep the previous result, evaluate;
+ *     stop when |d fitness| < rel_fitness and |d rmse| < rel_rmse }.
+ * Sigma is formed from the raw sums (sum q p^T / n - qbar pbar^T; the splitter's clouds lie in the unit ball about their
+ * mean, where that loses nothing that matters) and decomposed by a cyclic one-sided Jacobi iteration (at most 12 sweeps).
+ * R is assembled as u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T from the two leading singular pairs, which equals the
+ * formula above whenever Sigma has rank >= 2 and is a proper rotation for EVERY Sigma: with rank 1 the rotation about the
+ * determined axis is arbitrary (an orthogonal completion: deterministic, but set by rounding residue when Sigma's second
+ * column does not vanish exactly), with rank 0 (all correspondences on one point) R = I; never NaN.
+ * All sums run in one fixed order without atomics: results are bit-identical from run to run, and a pair's result does
+ * not depend on the batch it is launched in.
+ * Checked on the host before the launch: no null pointer, B >= 1, 1 <= Ns, Nt <= 1024, 0 <= max_iteration <= 64,
+ * max_corr_dist > 0, src_batch_stride 0 or 3*Ns. */
+int sug_icp_fitness(const float* src, int64_t src_batch_stride, const float* tgt, int B, int Ns, int Nt,
+                    double max_corr_dist, int max_iteration, double rel_fitness, double rel_rmse, int32_t* count,
+                    double* rmse, int32_t* iters, double* transform, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

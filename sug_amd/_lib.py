@@ -156,6 +156,7 @@ SIGNATURES = {
                            _vp, _vp, _vp, _vp, _vp],
     'sug_prepare_batch': [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _f32, _f32, _vp,
                           _vp, _vp, _vp, _vp],
+    'sug_icp_fitness': [_vp, _i64, _vp, _i32, _i32, _i32, _f64, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp],
 }
 
 STATS_BLOCKS = 1024        # SUG_STATS_BLOCKS

@@ -2,9 +2,9 @@
 sug_prepare_batch; DeviceLoader stands where the trainer builds torch.utils.data.DataLoader(dataset, ...).
 
 What the trainer holds after `data.to(device)` / `label.to(device).long()` is what batch() returns: data
-[B, 3, N, 1] fp32 and label [B] int64 on the device.  Reading files, the sub-domain splitter and DistributedSampler stay
-with the caller (create_single_dataset / create_splitted_dataset are not mirrored): hand the arrays they load to
-UnifiedPointDG.
+[B, 3, N, 1] fp32 and label [B] int64 on the device.  Reading files and DistributedSampler stay with the caller
+(create_single_dataset / create_splitted_dataset are not mirrored): hand the arrays they load to UnifiedPointDG, or
+split one resident array into two sub-domains with sug_amd.dataset_splitter first.
 """
 import numpy as np
 import torch

@@ -3099,6 +3099,39 @@ def prepare_batch(pts, idx, num_points, pre_rotate, aug, *, angles=None, noise=N
     return (out, a_out, n_out, s_out) if return_draws else out
 
 
+# ----------------------------------------------------------------------------- sub-domain splitter
+ICP_MAX_POINTS = 1024
+
+
+def icp_fitness(src, tgt, max_corr_dist=0.15, max_iteration=30, rel_fitness=1e-6, rel_rmse=1e-6):
+    """Point-to-point ICP of B (source, target) pairs in one launch (sug_icp_fitness; open3d's registration_icp with its
+    defaults, restated in include/sug_amd.h): src [Ns, 3] (one source for every pair) or [B, Ns, 3], tgt [B, Nt, 3], fp32
+    -> (count int32 [B], rmse fp64 [B], iters int32 [B], transform fp64 [B, 4, 4]); fitness = count / Ns.  No host
+    synchronisation."""
+    _need_gpu(src, tgt)
+    if tgt.dim() != 3 or tgt.shape[2] != 3 or src.dim() not in (2, 3) or src.shape[-1] != 3:
+        raise ValueError('icp_fitness: src must be [Ns, 3] or [B, Ns, 3] and tgt [B, Nt, 3], got %s and %s'
+                         % (tuple(src.shape), tuple(tgt.shape)))
+    if src.dtype != torch.float32 or tgt.dtype != torch.float32:
+        raise ValueError('icp_fitness: fp32 clouds only, got %s and %s' % (src.dtype, tgt.dtype))
+    B, Nt, _ = tgt.shape
+    if src.dim() == 3 and src.shape[0] != B:
+        raise ValueError('icp_fitness: %d sources for %d targets' % (src.shape[0], B))
+    src, tgt = src.detach().contiguous(), tgt.detach().contiguous()
+    Ns = src.shape[-2]
+    stride = 0 if src.dim() == 2 else 3 * Ns
+    dev = tgt.device
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    rmse = torch.empty(B, dtype=torch.float64, device=dev)
+    iters = torch.empty(B, dtype=torch.int32, device=dev)
+    transform = torch.empty(B, 4, 4, dtype=torch.float64, device=dev)
+    check(_timed('icp_fitness', {'B': B, 'Ns': Ns, 'Nt': Nt},
+                 lambda: lib().sug_icp_fitness(_p(src), stride, _p(tgt), B, Ns, Nt, float(max_corr_dist), int(max_iteration),
+                                               float(rel_fitness), float(rel_rmse), _p(count), _p(rmse), _p(iters),
+                                               _p(transform), _st())), 'sug_icp_fitness')
+    return count, rmse, iters, transform
+
+
 def _ctx_property(field):
     return property(lambda self: getattr(CTX, field), lambda self, v: setattr(CTX, field, v))
 
