@@ -499,6 +499,41 @@ __global__ __launch_bounds__(256) void ptran_rev_sum_kernel(const T* __restrict_
   }
 }
 
+// ---- range scaling of the fp16 backward (ops.py: _grad_scale16): s = the power of two that brings max|g| into
+// [2^(t-1), 2^t), from the exponent field of the maximum.  Per-workgroup partial maxima, folded by one wave: no atomics,
+// no memset, nothing read by the host.  NaNs are skipped by fmaxf (they reach the gradients through g itself).
+__global__ __launch_bounds__(256) void absmax_part_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
+  __shared__ float s_m[4];
+  float m = 0.f;
+  const int64_t n4 = (reinterpret_cast<uintptr_t>(x) & 15) ? 0 : (n >> 2);
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, nt = (int64_t)gridDim.x * 256;
+  for (int64_t i = t0; i < n4; i += nt) {
+    const float4 v = x4[i];
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+  }
+  for (int64_t i = (n4 << 2) + t0; i < n; i += nt) m = fmaxf(m, fabsf(x[i]));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+}
+
+__global__ __launch_bounds__(64) void pow2_scale_kernel(const float* __restrict__ part, int np, int log2_target,
+                                                        float* __restrict__ out) {
+  float m = 0.f;
+  for (int i = threadIdx.x; i < np; i += 64) m = fmaxf(m, part[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if (threadIdx.x == 0) {
+    int field = 253 + log2_target - (int)(__float_as_uint(m) >> 23);          // biased exponent of s; m >= 0
+    field = field < 27 ? 27 : (field > 227 ? 227 : field);
+    out[0] = __uint_as_float((unsigned)field << 23);
+    out[1] = __uint_as_float((unsigned)(254 - field) << 23);
+  }
+}
+
 inline int grid_for(int64_t waves) {
   int64_t g = (waves + 3) / 4;
   if (g > 8192) g = 8192;
@@ -606,6 +641,28 @@ extern "C" int sug_ptran_relu_bwd_db(void* G, const void* T1, int64_t rows, int 
     hipLaunchKernelGGL(ptran_relu_bwd_kernel<__half>, dim3(grid_cs(rows)), dim3(256), 0, st, (__half*)G, (const __half*)T1, rows, ws);
   SUG_LAUNCH_CHECK("sug_ptran_relu_bwd_db");
   return ptran_fold(ws, grid_cs(rows), db, st, "sug_ptran_relu_bwd_db(fold)");
+}
+
+extern "C" int sug_grad_scale16(const float* g0, int64_t n0, const float* g1, int64_t n1, const float* g2, int64_t n2,
+                                int log2_target, float* out, float* ws, void* stream) {
+  SUG_REQUIRE(g0 && out && ws, "sug_grad_scale16: null pointer");
+  SUG_REQUIRE(n0 > 0 && (!g1 || n1 > 0) && (!g2 || n2 > 0), "sug_grad_scale16: empty tensor");
+  SUG_REQUIRE(log2_target >= -14 && log2_target <= 15, "sug_grad_scale16: log2_target outside fp16's exponent range");
+  hipStream_t st = (hipStream_t)stream;
+  const float* g[3] = {g0, g1, g2};
+  const int64_t n[3] = {n0, n1, n2};
+  int np = 0;                                                    // partial maxima so far: at most 3 x 256 (ws: 768 floats)
+  for (int i = 0; i < 3; ++i) {
+    if (!g[i]) continue;
+    int64_t nb = (n[i] + 4095) / 4096;                           // 4 float4 per thread and pass
+    if (nb > 256) nb = 256;
+    hipLaunchKernelGGL(absmax_part_kernel, dim3((int)nb), dim3(256), 0, st, g[i], n[i], ws + np);
+    SUG_LAUNCH_CHECK("sug_grad_scale16(absmax)");
+    np += (int)nb;
+  }
+  hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(64), 0, st, ws, np, log2_target, out);
+  SUG_LAUNCH_CHECK("sug_grad_scale16");
+  return SUG_OK;
 }
 
 extern "C" int sug_ptran_attn_fwd(const void* logits, const void* delta, const float* vf, const int32_t* nbr, int B, int n,

@@ -86,8 +86,7 @@ class TransformerBlock(nn.Module):
         p16 = PROJ_16BIT and GEMM_DTYPE is not None
         if p16:     # the lifted features stay in 16 bits between fc1 and the three projections (one rounding, no re-casts)
             lo = GEMM_DTYPE
-            lifted = ops.linear16(features, self.fc1, lo, out32=False)
-            q, kf, vf = (ops.linear16(lifted, w, lo) for w in (self.w_qs, self.w_ks, self.w_vs))
+            q, kf, vf = ops.lift_project16(features, self.fc1, self.w_qs, self.w_ks, self.w_vs, lo)
         else:
             lifted = _apply(self.fc1, features)
             q, kf, vf = _apply(self.w_qs, lifted), _apply(self.w_ks, lifted), _apply(self.w_vs, lifted)

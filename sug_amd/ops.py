@@ -1807,6 +1807,42 @@ def _dweight(gy, x):
     return torch.bmm(gy.view(S, R // S, gy.shape[1]).transpose(1, 2), x.view(S, R // S, x.shape[1]), **wide).sum(dim=0)
 
 
+# ----------------------------------------------------------------------------- fp16 gradients: range scaling
+# fp16 has 5 exponent bits: normals from 6.1e-5, nothing below 6e-8.  Under a mean-reduced loss the gradient that reaches a
+# transformer block is 1e-6 .. 1e-5 at its largest, and every 16-bit tensor of the backward (the incoming gradient rounded for
+# the GEMMs, dL, da, dT1, dU, d delta, dT0) would sit in the subnormals or round to 0.  The backward is linear in its incoming
+# gradient, so it runs on s * g with s the power of two that brings max|g| into [2^(t-1), 2^t), and its fp32 results are
+# multiplied by 1 / s: exact (a change of exponent), computed on the device from the bits of max|g| (sug_grad_scale16: no
+# host read, no synchronisation: capturable), and absent from the fp32 mode.
+# t = 4 (max|s g| in [8, 16)).  Headroom above, to fp16's 65504 = 2^16: da = g a <= 16 (softmax weights a <= 1, reached in the
+# saturated regime): 2^12; dL = a (g y - g mixed) / sqrt(512) <= 16 * 2 max|y| * 0.044 = 14 for |V + delta| = 10: 2^12; the
+# GEMM results dT1, dU, dT0 grow with the weights' row norms: sqrt(512) * |w| * |dL| is estimated at 16 for the default
+# initialisation and 640 with fc_gamma[2] multiplied by 1024 (softmax weights up to 1.0), peaks a few times that: 2^4 at the
+# least.  The estimate is held by tests/test_gpu_ptran.py at that gain (finite gradients, the same at every loss scale); an
+# overflow would put inf into every gradient of the block.  Room below: a gradient 2^-10 of the largest is still a normal
+# number (an O(1) probe used to leave 2^-14: the scaling also gains 2^4 there).
+_G16_LOG2_TARGET = 4
+
+
+def _grad_scale16(*gs):
+    """(s, 1 / s) as 0-dim fp32 device tensors for up to three contiguous fp32 tensors: s = 2^(t - floor(log2(max|g|)) - 1),
+    clamped to 2^+-100 (max|g| = 0: 2^100 * 0 = 0; inf / nan pass through g as they are).  sug_grad_scale16: two kinds of
+    launches, no memset (a torch reduction to one element brings one), nothing read by the host."""
+    gs = [g if g.is_contiguous() else g.contiguous() for g in gs]
+    dev = gs[0].device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(768, dtype=torch.float32, device=dev)
+    a = [(_p(g), g.numel()) for g in gs] + [(None, 0)] * (3 - len(gs))
+    check(lib().sug_grad_scale16(a[0][0], a[0][1], a[1][0], a[1][1], a[2][0], a[2][1], _G16_LOG2_TARGET, _p(out), _p(ws), _st()),
+          'sug_grad_scale16')
+    return out[0], out[1]
+
+
+def _scaled16(g2, s):
+    """(s * g2) rounded to fp16 in one pass."""
+    return torch.mul(g2, s, out=torch.empty_like(g2, dtype=torch.float16))
+
+
 class _Linear16(torch.autograd.Function):
     """nn.Linear on [..., K] rows with 16-bit operands (MFMA, fp32 accumulation) and fp32 parameters: the weight's
     16-bit copy comes from the step cache, the result leaves the GEMM as fp32 (`out32`) or stays 16-bit for a
@@ -1836,12 +1872,20 @@ class _Linear16(torch.autograd.Function):
         x16, w16 = ctx.saved_tensors
         xshape, xdtype, has_b, lo = ctx.meta
         g2 = g.reshape(-1, g.shape[-1])
-        g16 = g2 if g2.dtype == lo else g2.to(lo)
+        # an fp32 gradient rounded to fp16 for GEMMs with fp32 results: on s * g, results * 1 / s (_grad_scale16)
+        scaled = lo == torch.float16 and g2.dtype == torch.float32 and xdtype == torch.float32
+        if scaled:
+            s, inv = _grad_scale16(g2)
+            g16 = _scaled16(g2, s)
+        else:
+            g16 = g2 if g2.dtype == lo else g2.to(lo)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = (torch.mm(g16, w16, out_dtype=torch.float32) if xdtype == torch.float32 else torch.mm(g16, w16)).view(xshape)
         dw = _dweight(g16, x16) if ctx.needs_input_grad[1] else None
         db = colsum(g2) if (has_b and ctx.needs_input_grad[2]) else None
+        if scaled:
+            torch._foreach_mul_([t for t in (dx, dw) if t is not None], inv)
         return dx, dw, db, None, None
 
 
@@ -1849,14 +1893,69 @@ def linear16(x, layer, lo, out32=True):
     return _Linear16.apply(x, layer.weight, layer.bias, lo, out32)
 
 
+class _LiftProject16(torch.autograd.Function):
+    """fc1 and the three projections w_qs / w_ks / w_vs of a TransformerBlock with 16-bit operands and fp32 parameters:
+    lifted = fc1(x) stays 16-bit between them (one rounding, no re-casts), and so does its gradient.  That gradient is why the
+    four linears share one backward: in fp16 it is only representable scaled (_grad_scale16), and a scale cannot travel
+    between autograd nodes; here s * d lifted never leaves the function.  Forward values as four _Linear16 calls."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, wq, wk, wv, lo):
+        _need_gpu(x, w1)
+        x2 = x.reshape(-1, x.shape[-1])
+        x16 = x2 if x2.dtype == lo else x2.to(lo)
+        w16 = cast_cached(w1, lo, detach=True)
+        lifted = torch.addmm(cast_cached(b1, lo, detach=True), x16, w16.t())
+        wp = [cast_cached(w, lo, detach=True) for w in (wq, wk, wv)]
+        ctx.save_for_backward(x16, w16, lifted, *wp)
+        ctx.meta = (x.shape, lo)
+        return tuple(torch.mm(lifted, w.t(), out_dtype=torch.float32).view(*x.shape[:-1], w.shape[0]) for w in wp)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        x16, w16, lifted, *wp = ctx.saved_tensors
+        xshape, lo = ctx.meta
+        gs = [g.reshape(-1, g.shape[-1]).float() for g in gs]
+        if lo == torch.float16:
+            s, inv = _grad_scale16(*gs)
+            g16 = [_scaled16(g, s) for g in gs]
+        else:
+            g16 = [g.to(lo) for g in gs]
+        need = ctx.needs_input_grad
+        dwp = [_dweight(g, lifted) if need[3 + i] else None for i, g in enumerate(g16)]
+        dx = dw1 = db1 = None
+        if need[0] or need[1] or need[2]:
+            # s * d lifted, 16-bit: the three GEMMs and their sum as autograd runs them for three separate linears
+            dl = torch.mm(g16[0], wp[0])
+            dl += torch.mm(g16[1], wp[1])
+            dl += torch.mm(g16[2], wp[2])
+            if need[1]:
+                dw1 = _dweight(dl, x16)
+            if need[2]:
+                db1 = colsum(dl) if lo == torch.float16 else dl.sum(0, dtype=torch.float32)
+            if need[0]:
+                dx = torch.mm(dl, w16, out_dtype=torch.float32).view(xshape)
+        if lo == torch.float16:
+            torch._foreach_mul_([t for t in (dx, dw1, db1, *dwp) if t is not None], inv)
+        return dx, dw1, db1, dwp[0], dwp[1], dwp[2], None
+
+
+def lift_project16(x, fc1, w_qs, w_ks, w_vs, lo):
+    """(q, K, V) = (w_qs, w_ks, w_vs)(fc1(x)) on the 16-bit path, fp32 results."""
+    return _LiftProject16.apply(x, fc1.weight, fc1.bias, w_qs.weight, w_ks.weight, w_vs.weight, lo)
+
+
 # ----------------------------------------------------------------------------- Point Transformer attention
 # fp16 mode: the forward of a transformer block's vector attention as ONE MFMA kernel (sug_ptran_fused_fwd) instead of pos1 +
-# 3 library GEMMs + qk + attn.  Same values bit for bit (tests/test_gpu_ptran.py).  Measured at config 5's block-1 shape (1 M
-# k-expanded rows; tools/bench_ptran_fused.py, profiles/r06_ptran_fused_ab.txt): without a backward to feed 2.56 vs 3.21 ms --
-# nothing but delta is written --, with the four tensors a backward reads 3.11 vs 3.13 ms, and 19.73 vs 19.63 ms for the
-# whole config-5 step: one 130 KB workgroup per CU serialises its row passes (L2 gathers of K / V rows) with its MFMA chains,
-# the composition overlaps them across kernels at full occupancy.  Hence 'auto': the one-kernel form where no backward
-# follows (eval / no_grad forwards), the composition in training.  SUG_PTRAN_FUSED=1 / 0 forces one form.
+# 3 library GEMMs + qk + attn.  Same roundings, another order of the GEMMs' partial sums: outputs within 2e-3 of the composed
+# chain's (relative L2 3e-4), and no further from fp64 than 2 x the chain's own error (tests/test_gpu_ptran.py).  Measured at
+# config 5's block-1 shape (1 M k-expanded rows; tools/bench_ptran_fused.py, profiles/r06_ptran_fused_ab.txt): without a
+# backward to feed 2.56 vs 3.21 ms -- nothing but delta is written --, with the four tensors a backward reads 3.11 vs 3.13 ms,
+# and 19.73 vs 19.63 ms for the whole config-5 step as it stood in round 6 (before the range scaling of the fp16 backward,
+# which costs both forms the same 1.5 ms: profiles/ptran_fp16_grad_scale_ab.txt): one 130 KB workgroup per CU serialises its
+# row passes (L2 gathers of K / V rows) with its MFMA chains, the composition overlaps them across kernels at full occupancy.
+# Hence 'auto': the one-kernel form where no backward follows (eval / no_grad forwards), the composition in training.
+# SUG_PTRAN_FUSED=1 / 0 forces one form.
 PTRAN_FUSED = {'1': True, '0': False}.get(_os.environ.get('SUG_PTRAN_FUSED', 'auto'), 'auto')
 
 
@@ -1928,6 +2027,9 @@ class _PTranAttention(torch.autograd.Function):
         dev, lo = g.device, T0.dtype
         L_ = lib()
         g = g.contiguous().float()
+        if code == 1:           # the fp16 chain runs on s * g (_grad_scale16); its fp32 results are multiplied by 1 / s below
+            s, inv = _grad_scale16(g)
+            g = g * s
         off, ent = knn_reverse(nbr)
         dL, da = torch.empty_like(Lg), torch.empty_like(Lg)
         dv = torch.empty(B, n, d, dtype=torch.float32, device=dev)
@@ -1958,6 +2060,8 @@ class _PTranAttention(torch.autograd.Function):
         ws = torch.empty(1024 * 4 * d, dtype=f32, device=dev)
         check(L_.sug_ptran_pos1_bwd(_p(dT0), _p(xyz), _p(nbr), _p(w1c), _p(b1c), B, n, k, d, code, _p(dw1), _p(db1), _p(ws),
                                     _st()), 'sug_ptran_pos1_bwd')
+        if code == 1:
+            torch._foreach_mul_([dq, dk, dv, dw1, db1, dw2, db2, dwg1, dbg1, dwg2, dbg2], inv)
         return None, None, dq, dk, dv, dw1, db1, dw2, db2, dwg1, dbg1, dwg2, dbg2, None
 
 

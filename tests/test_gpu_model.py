@@ -319,6 +319,58 @@ def test_ptran_reduced_precision_mode_deviation(dtype, tol, proj16):
         PT.GEMM_DTYPE = None
     g = net.g.transformers[0].fc_gamma[0].weight.grad
     assert g is not None and bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0
+    # what these gradients are worth at a real loss's scale: test_ptran_fp16_gradients_do_not_depend_on_the_loss_scale below
+    # (fp16) and tests/test_gpu_ptran.py::test_block_gradients_scale_with_the_incoming_gradient
+
+
+def _ptran_group_grads(net, x, labels, dtype, proj16, loss_scale):
+    """Gradients of loss_scale * cross_entropy(first head), divided by loss_scale again, for the parameter groups of the
+    five transformer blocks that the k-expanded fp16 chain feeds: {(block, group): flat gradient}."""
+    import torch.nn.functional as F
+    from sug_amd.model import Ptran_transformer as PT
+    keep = PT.GEMM_DTYPE, PT.PROJ_16BIT
+    PT.GEMM_DTYPE, PT.PROJ_16BIT = dtype, proj16
+    try:
+        net.zero_grad(set_to_none=True)
+        torch.manual_seed(11)                    # the FPS starts
+        y1 = net(x, semantic_adaption=True)[0]
+        (F.cross_entropy(y1, labels) * loss_scale).backward()
+    finally:
+        PT.GEMM_DTYPE, PT.PROJ_16BIT = keep
+    blocks = [net.g.transformer1] + list(net.g.transformers)
+    return {(i, grp): torch.cat([p.grad.reshape(-1) for p in getattr(b, grp).parameters()]).double() / loss_scale
+            for i, b in enumerate(blocks) for grp in ('fc_gamma', 'w_qs', 'w_ks', 'fc_delta')}
+
+
+@pytest.mark.parametrize('proj16', [False, True])
+def test_ptran_fp16_gradients_do_not_depend_on_the_loss_scale(proj16):
+    """Net_MDA('PTran') under a mean-reduced cross entropy (B = 2, N = 1024): the deviation of the fp16 mode's gradients from
+    the fp32 mode's, same HIP path, same neighbour lists and FPS starts, is the same whether the loss is taken as is or
+    multiplied by 2^12 (and the gradients divided again).  The forward does not see the factor and the backward is linear in
+    it, so properly scaled fp16 arithmetic gives the same deviation twice; a factor 2 between the two is allowed."""
+    from sug_amd.model.Model import Net_MDA
+    torch.manual_seed(7)
+    net = Net_MDA('PTran')                      # torch's default initialisation: the gradients of a freshly built network
+    for m in net.modules():
+        if isinstance(m, (torch.nn.Dropout, torch.nn.Dropout2d)):
+            m.p = 0.0
+    net = net.cuda().train()
+    g = torch.Generator().manual_seed(3)
+    x = O.synth_clouds(2, 1024, g).cuda()
+    labels = torch.tensor([3, 8]).cuda()
+    ref = _ptran_group_grads(net, x, labels, None, False, 1.0)
+    ref_up = _ptran_group_grads(net, x, labels, None, False, 2.0 ** 12)
+    lo = _ptran_group_grads(net, x, labels, torch.float16, proj16, 1.0)
+    lo_up = _ptran_group_grads(net, x, labels, torch.float16, proj16, 2.0 ** 12)
+    rel = lambda a, b: float((a - b).norm() / b.norm())
+    bad = []
+    print('block group      |fp32 grad|   fp16 vs fp32 at loss x 1   at loss x 2^12')
+    for key in ref:
+        d1, d2 = rel(lo[key], ref[key]), rel(lo_up[key], ref_up[key])
+        print('%d     %-10s %.3e     %.3e                  %.3e' % (key[0], key[1], float(ref[key].norm()), d1, d2))
+        if not (d1 <= 2 * d2 and d2 <= 2 * d1):
+            bad.append((key, d1, d2))
+    assert not bad, bad
 
 
 def _gradient_errors(name, seed, data_seed, B=4, verbose=True):
