@@ -789,6 +789,26 @@ int sug_ce_fwd(const float* logits, int64_t ld, const int64_t* label, int M, int
  * (1-eps)*onehot + eps/C; zero in ignored rows. */
 int sug_ce_bwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index, float label_smoothing,
                const float* g, const float* lse, float* dlogits, void* stream);
+/* The scalar tail of phase 1 of the two-phase UDA step (train_uda.py:149-160, train_dg_naive_mmd.py:225-241) in one launch:
+ * logits ys1, ys2 [Ms, C] (source, heads 1 and 2) and yt1, yt2 [Mt, C] (target), fp32, ALL FOUR with row stride ld >= C (the row
+ * halves of two paired [Ms + Mt, C] tensors are pointer offsets); label int64 [Ms], label_t int64 [Mt] (may be null when a_t == 0).
+ *   CEs = CE(ys1, label) + CE(ys2, label), CEt = CE(yt1, label_t) + CE(yt2, label_t)  (CE = mean over rows, nn.CrossEntropyLoss()),
+ *   D = mean over Mt*C of |softmax(yt1) - softmax(yt2)|  (utils/train_utils.py:51-54),
+ * out4 = { a_s*CEs - D + a_t*CEt, r_s*CEs, -D, a_t*CEt };  lse [2*Ms + 2*Mt] = the rows' log-sum-exp (ys1, ys2, yt1, yt2), kept for
+ * the backward.  totals (device double[4], may be null) keeps the epoch's books in the same launch, train_uda.py:180-184 without the
+ * .item(): += { out4[1]*Ms, out4[2]*Ms, Ms, Mt }.  A label outside [0, C) makes the loss (and that row's gradient) NaN; there is no
+ * ignore_index.  1 <= Ms, Mt <= 1024, 2 <= C <= 64, checked on the host before any launch (-1, sug_last_error()).  One workgroup, a
+ * wave per row; the rows' terms are summed in fp64 in one fixed order; no atomics, no memset node: capturable, bit-reproducible. */
+int sug_mcd_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
+                     const int64_t* label_t, int Ms, int Mt, int C, float a_s, float a_t, float r_s, float* out4, float* lse,
+                     double* totals, void* stream);
+/* Its gradient for the upstream scalar g[0], four dense blocks ds1, ds2 [Ms, C] and dt1, dt2 [Mt, C] (ds1 | dt1 adjacent = the dense
+ * gradient of a paired tensor): source rows g*a_s*(softmax - onehot)/Ms; target rows, with s = sign(p1 - p2) and sign(0) = 0,
+ * dt1 = -g/(Mt*C) * p1*(s - <s,p1>), dt2 = +g/(Mt*C) * p2*(s - <s,p2>), plus g*a_t*(softmax - onehot)/Mt when a_t != 0
+ * (s_j - <s,p> is evaluated as sum_c p_c (s_j - s_c), which does not cancel for a class of probability close to 1). */
+int sug_mcd_loss_bwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
+                     const int64_t* label_t, int Ms, int Mt, int C, float a_s, float a_t, const float* g, const float* lse,
+                     float* ds1, float* ds2, float* dt1, float* dt2, void* stream);
 /* out3 = { loss_cls + wg*v_geo + ws*(v_sem1 + v_sem2), wg*v_geo, ws*(v_sem1 + v_sem2) } (train_dg_single_gpu.py:314-324; the
  * weights MMD_WEIGHT * GEO_SCALE and 0.5 * MMD_WEIGHT * SEM_SCALE folded by the caller); null v_* = term absent.
  * Backward: out4 = g[0] * {1, wg, ws, ws}. */

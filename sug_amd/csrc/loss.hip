@@ -154,6 +154,134 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
     d[e] = v;
   }
 }
+// ---- phase-1 loss of the two-phase UDA step (train_uda.py:149-160, train_dg_naive_mmd.py:225-241) ------------------------
+//   loss = a_s * (CE(ys1) + CE(ys2)) + a_t * (CE(yt1) + CE(yt2)) - mean |softmax(yt1) - softmax(yt2)|
+// in one launch each way instead of ~30.  The shape of ce_fwd_kernel: one workgroup, a WAVE per row, a LANE per class
+// (C <= 64); a row of both heads is two coalesced loads, its max / sums are cross-lane reductions of one fixed shape; the
+// rows' terms meet in LDS and wave 0 folds them in fp64 -- lane l takes rows l, l + 64, ... in order, then the butterfly -- an
+// order that does not depend on the number of waves launched.  Thread 0 writes the four scalars and keeps the epoch's books
+// (plain fp64 read-modify-write: one workgroup, stream order).  Labels outside [0, C) poison the loss with NaN.
+constexpr int MCD_MAXROWS = 1024;
+
+__device__ __forceinline__ float row_lse(float z, bool in) {
+  const float mx = wave_max_f(z);
+  return mx + logf(wave_sum_f(in ? expf(z - mx) : 0.f));
+}
+
+__global__ __launch_bounds__(1024) void mcd_loss_fwd_kernel(const float* __restrict__ ys1, const float* __restrict__ ys2,
+                                                            const float* __restrict__ yt1, const float* __restrict__ yt2, int64_t ld,
+                                                            const int64_t* __restrict__ label, const int64_t* __restrict__ label_t,
+                                                            int Ms, int Mt, int C, float a_s, float a_t, float r_s,
+                                                            float* __restrict__ out, float* __restrict__ lse,
+                                                            double* __restrict__ totals) {
+  __shared__ float s_ces[MCD_MAXROWS], s_cet[MCD_MAXROWS], s_dis[MCD_MAXROWS];
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nwave = blockDim.x / WAVE;
+  const bool in = lane < C;
+  for (int r = wave; r < Ms; r += nwave) {                // source rows: the cross entropy of both heads (wave-uniform trips)
+    const float *r1 = ys1 + (int64_t)r * ld, *r2 = ys2 + (int64_t)r * ld;
+    const float l1 = row_lse(in ? r1[lane] : -INFINITY, in), l2 = row_lse(in ? r2[lane] : -INFINITY, in);
+    if (lane == 0) {
+      const int64_t y = label[r];
+      lse[r] = l1;
+      lse[Ms + r] = l2;
+      s_ces[r] = (y < 0 || y >= C) ? NAN : (l1 - r1[y]) + (l2 - r2[y]);
+    }
+  }
+  for (int r = wave; r < Mt; r += nwave) {                // target rows: the discrepancy, and the cross entropy when a_t != 0
+    const float *r1 = yt1 + (int64_t)r * ld, *r2 = yt2 + (int64_t)r * ld;
+    const float z1 = in ? r1[lane] : -INFINITY, z2 = in ? r2[lane] : -INFINITY;
+    const float l1 = row_lse(z1, in), l2 = row_lse(z2, in);
+    const float d = wave_sum_f(in ? fabsf(expf(z1 - l1) - expf(z2 - l2)) : 0.f);
+    if (lane == 0) {
+      lse[2 * Ms + r] = l1;
+      lse[2 * Ms + Mt + r] = l2;
+      s_dis[r] = d;
+      float t = 0.f;
+      if (a_t != 0.f) {
+        const int64_t y = label_t[r];
+        t = (y < 0 || y >= C) ? NAN : (l1 - r1[y]) + (l2 - r2[y]);
+      }
+      s_cet[r] = t;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    double a = 0.0, b = 0.0, d = 0.0;
+    for (int i = lane; i < Ms; i += WAVE) a += (double)s_ces[i];
+    for (int i = lane; i < Mt; i += WAVE) {
+      b += (double)s_cet[i];
+      d += (double)s_dis[i];
+    }
+    a = wave_sum_d(a);
+    b = wave_sum_d(b);
+    d = wave_sum_d(d);
+    if (lane == 0) {
+      const float ces = (float)(a / (double)Ms), cet = (float)(b / (double)Mt);
+      const float adv = -(float)(d / ((double)Mt * (double)C));
+      float loss = a_s * ces + adv;                       // args.weight * loss_s + loss_adv (+ 0.5 * TARGET_LOSS * loss_t)
+      const float lt = a_t != 0.f ? a_t * cet : 0.f;
+      if (a_t != 0.f) loss += lt;
+      const float ls = r_s * ces;
+      out[0] = loss; out[1] = ls; out[2] = adv; out[3] = lt;
+      if (totals) {                                       // train_uda.py:180-184
+        totals[0] += (double)ls * (double)Ms;
+        totals[1] += (double)adv * (double)Ms;
+        totals[2] += (double)Ms;
+        totals[3] += (double)Mt;
+      }
+    }
+  }
+}
+
+// A wave per row of the Ms + Mt rows (source rows first), a lane per class; the four gradient blocks are dense [rows, C].
+__global__ __launch_bounds__(256) void mcd_loss_bwd_kernel(const float* __restrict__ ys1, const float* __restrict__ ys2,
+                                                           const float* __restrict__ yt1, const float* __restrict__ yt2, int64_t ld,
+                                                           const int64_t* __restrict__ label, const int64_t* __restrict__ label_t,
+                                                           int Ms, int Mt, int C, float a_s, float a_t, const float* __restrict__ g,
+                                                           const float* __restrict__ lse, float* __restrict__ ds1,
+                                                           float* __restrict__ ds2, float* __restrict__ dt1, float* __restrict__ dt2) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int R = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;      // wave-uniform
+  if (R >= Ms + Mt) return;
+  const bool in = lane < C;
+  const float gv = g[0];
+  if (R < Ms) {
+    const int64_t o = (int64_t)R * ld + lane, y = label[R];
+    const float f = gv * a_s / (float)Ms;
+    const bool bad = y < 0 || y >= C;
+    if (in) {
+      const float hot = lane == y ? 1.f : 0.f;
+      ds1[(int64_t)R * C + lane] = bad ? NAN : f * (expf(ys1[o] - lse[R]) - hot);
+      ds2[(int64_t)R * C + lane] = bad ? NAN : f * (expf(ys2[o] - lse[Ms + R]) - hot);
+    }
+    return;
+  }
+  const int r = R - Ms;
+  const int64_t o = (int64_t)r * ld + lane;
+  const float p1 = in ? expf(yt1[o] - lse[2 * Ms + r]) : 0.f, p2 = in ? expf(yt2[o] - lse[2 * Ms + Mt + r]) : 0.f;
+  const float df = p1 - p2;
+  const float s = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);                 // sign(0) = 0, as the backward of torch.abs
+  // s_j - <s,p> written as sum_c p_c (s_j - s_c) (sum_c p_c = 1): for s_j = +-1 every term has one sign, so a class whose
+  // probability is close to 1 does not lose its factor 1 - p_j to cancellation.  With P+ / P0 / P- the probability mass of the
+  // classes with s = +1 / 0 / -1:  s_j = +1 -> P0 + 2 P-,  s_j = -1 -> -(P0 + 2 P+),  s_j = 0 -> P- - P+.
+  const float up1 = wave_sum_f(s > 0.f ? p1 : 0.f), eq1 = wave_sum_f(s == 0.f ? p1 : 0.f), dn1 = wave_sum_f(s < 0.f ? p1 : 0.f);
+  const float up2 = wave_sum_f(s > 0.f ? p2 : 0.f), eq2 = wave_sum_f(s == 0.f ? p2 : 0.f), dn2 = wave_sum_f(s < 0.f ? p2 : 0.f);
+  const float t1 = s > 0.f ? eq1 + 2.f * dn1 : (s < 0.f ? -(eq1 + 2.f * up1) : dn1 - up1);
+  const float t2 = s > 0.f ? eq2 + 2.f * dn2 : (s < 0.f ? -(eq2 + 2.f * up2) : dn2 - up2);
+  const float k = gv / ((float)Mt * (float)C);
+  float v1 = -k * (p1 * t1), v2 = k * (p2 * t2);
+  if (a_t != 0.f) {
+    const int64_t y = label_t[r];
+    const float f = gv * a_t / (float)Mt, hot = lane == y ? 1.f : 0.f;
+    const bool bad = y < 0 || y >= C;
+    v1 = bad ? NAN : v1 + f * (p1 - hot);
+    v2 = bad ? NAN : v2 + f * (p2 - hot);
+  }
+  if (in) {
+    dt1[(int64_t)r * C + lane] = v1;
+    dt2[(int64_t)r * C + lane] = v2;
+  }
+}
 }  // namespace
 
 extern "C" int sug_ce_pair_fwd(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int M, int C,
@@ -202,6 +330,38 @@ extern "C" int sug_ce_bwd(const float* logits, int64_t ld, const int64_t* label,
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)sug_divup((int64_t)M * C, 256)), dim3(256), 0, (hipStream_t)stream, logits, ld,
                      label, M, C, ignore_index, label_smoothing, g, lse, dlogits);
   SUG_LAUNCH_CHECK("sug_ce_bwd");
+  return SUG_OK;
+}
+
+static int mcd_check(const char* who, int Ms, int Mt, int C, int64_t ld, float a_t) {
+  SUG_REQUIRE(Ms >= 1 && Ms <= MCD_MAXROWS && Mt >= 1 && Mt <= MCD_MAXROWS && C >= 2 && C <= CE1_MAXC && ld >= C,
+              "%s: unsupported shape Ms=%d, Mt=%d rows, C=%d classes, ld=%lld (1 <= Ms, Mt <= %d, 2 <= C <= %d, ld >= C)", who, Ms, Mt,
+              C, (long long)ld, MCD_MAXROWS, CE1_MAXC);
+  SUG_REQUIRE(a_t == a_t, "%s: a_t is NaN", who);
+  return SUG_OK;
+}
+
+extern "C" int sug_mcd_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld,
+                                const int64_t* label, const int64_t* label_t, int Ms, int Mt, int C, float a_s, float a_t, float r_s,
+                                float* out4, float* lse, double* totals, void* stream) {
+  SUG_REQUIRE(ys1 && ys2 && yt1 && yt2 && label && out4 && lse && (label_t || a_t == 0.f), "sug_mcd_loss_fwd: null pointer");
+  if (mcd_check("sug_mcd_loss_fwd", Ms, Mt, C, ld, a_t) != SUG_OK) return SUG_ERR_ARG;
+  const int rows = Ms > Mt ? Ms : Mt, waves = rows < 16 ? rows : 16;
+  hipLaunchKernelGGL(mcd_loss_fwd_kernel, dim3(1), dim3(WAVE * waves), 0, (hipStream_t)stream, ys1, ys2, yt1, yt2, ld, label, label_t,
+                     Ms, Mt, C, a_s, a_t, r_s, out4, lse, totals);
+  SUG_LAUNCH_CHECK("sug_mcd_loss_fwd");
+  return SUG_OK;
+}
+
+extern "C" int sug_mcd_loss_bwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld,
+                                const int64_t* label, const int64_t* label_t, int Ms, int Mt, int C, float a_s, float a_t,
+                                const float* g, const float* lse, float* ds1, float* ds2, float* dt1, float* dt2, void* stream) {
+  SUG_REQUIRE(ys1 && ys2 && yt1 && yt2 && label && g && lse && ds1 && ds2 && dt1 && dt2 && (label_t || a_t == 0.f),
+              "sug_mcd_loss_bwd: null pointer");
+  if (mcd_check("sug_mcd_loss_bwd", Ms, Mt, C, ld, a_t) != SUG_OK) return SUG_ERR_ARG;
+  hipLaunchKernelGGL(mcd_loss_bwd_kernel, dim3((unsigned)sug_divup((int64_t)(Ms + Mt), 4)), dim3(256), 0, (hipStream_t)stream, ys1, ys2,
+                     yt1, yt2, ld, label, label_t, Ms, Mt, C, a_s, a_t, g, lse, ds1, ds2, dt1, dt2);
+  SUG_LAUNCH_CHECK("sug_mcd_loss_bwd");
   return SUG_OK;
 }
 

@@ -2320,6 +2320,95 @@ def loss_combine(loss_cls, v_geo, v_sem1, v_sem2, wg, ws):
     return _LossCombine.apply(loss_cls, v_geo, v_sem1, v_sem2, wg, ws)
 
 
+MCD_MAX_ROWS, MCD_MAX_CLASSES = 1024, 64
+
+
+class _MCDLoss(torch.autograd.Function):
+    """The phase-1 loss of the two-phase UDA step in one launch each way (sug_mcd_loss_fwd / sug_mcd_loss_bwd); the forward's
+    launch also advances the caller's `totals`.  yt1 is None: ys1, ys2 are the PAIRED logits [Ms + Mt, C], source rows first
+    (Ms = the number of labels), and the backward writes the pair's dense gradient."""
+
+    @staticmethod
+    def forward(ctx, ys1, ys2, yt1, yt2, label, label_t, a_s, a_t, r_s, totals):
+        _need_gpu(ys1, ys2, yt1, yt2, label, label_t, totals)
+        paired = yt1 is None
+        Ms, C = label.numel(), ys1.shape[1]
+        Mt = ys1.shape[0] - Ms if paired else yt1.shape[0]
+        ts = [ys1, ys2] if paired else [ys1, ys2, yt1, yt2]
+        if any(t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != C for t in ts) or ys1.shape != ys2.shape or \
+                (not paired and (yt1.shape != yt2.shape or ys1.shape[0] != Ms)) or Mt < 1:
+            raise RuntimeError('ops.mcd_loss: fp32 logits [Ms, C] x 2 and [Mt, C] x 2 (or two paired [Ms + Mt, C]) and Ms labels '
+                               '(got %s, %d labels)' % ([tuple(t.shape) for t in ts], Ms))
+        if a_t != 0 and (label_t is None or label_t.numel() != Mt):
+            raise RuntimeError('ops.mcd_loss: a_t != 0 needs Mt = %d target labels' % Mt)
+        if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 4 or not totals.is_contiguous()):
+            raise RuntimeError('ops.mcd_loss: totals is a contiguous float64 tensor of 4 elements')
+        ld = ts[0].stride(0)
+        if any(t.stride(1) != 1 or t.stride(0) != ld for t in ts) or ld < C:      # one leading dimension for the four blocks
+            ts = [t.contiguous() for t in ts]
+            ld = C
+        if paired:
+            ts = [ts[0], ts[1], ts[0][Ms:], ts[1][Ms:]]
+        lab = label.reshape(-1).long().contiguous()
+        lab_t = label_t.reshape(-1).long().contiguous() if (a_t != 0 and label_t is not None) else None
+        out = torch.empty(4, dtype=torch.float32, device=ys1.device)
+        lse = torch.empty(2 * Ms + 2 * Mt, dtype=torch.float32, device=ys1.device)
+        check(lib().sug_mcd_loss_fwd(_p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), ld, _p(lab), _p(lab_t), Ms, Mt, C, float(a_s),
+                                     float(a_t), float(r_s), _p(out), _p(lse), _p(totals), _st()), 'sug_mcd_loss_fwd')
+        ctx.save_for_backward(lab, lse, *((lab_t,) if lab_t is not None else ()), *ts)
+        ctx.meta = (Ms, Mt, C, ld, float(a_s), float(a_t), paired, lab_t is not None)
+        loss, ls, adv, lt = out[0], out[1], out[2], out[3]
+        ctx.mark_non_differentiable(ls, adv, lt)
+        ctx.set_materialize_grads(False)          # no zero-filled scalars for the three reporting outputs (a launch each)
+        return loss, ls, adv, lt
+
+    @staticmethod
+    def backward(ctx, g, _g1, _g2, _g3):
+        Ms, Mt, C, ld, a_s, a_t, paired, has_t = ctx.meta
+        if g is None:
+            return (None,) * 10
+        sv = ctx.saved_tensors
+        lab, lse = sv[0], sv[1]
+        lab_t = sv[2] if has_t else None
+        ts = sv[3 if has_t else 2:]
+        gs = g.detach().to(dtype=torch.float32).reshape(1)
+        d = torch.empty(2, Ms + Mt, C, dtype=torch.float32, device=lse.device)
+        check(lib().sug_mcd_loss_bwd(_p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), ld, _p(lab), _p(lab_t), Ms, Mt, C, a_s, a_t, _p(gs),
+                                     _p(lse), _p(d[0]), _p(d[1]), _p(d[0, Ms:]), _p(d[1, Ms:]), _st()), 'sug_mcd_loss_bwd')
+        if paired:
+            return (d[0], d[1]) + (None,) * 8
+        return (d[0, :Ms], d[1, :Ms], d[0, Ms:], d[1, Ms:]) + (None,) * 6
+
+
+def mcd_loss_supported(ys1, ys2, yt1=None, yt2=None, label=None, a_t=0.0):
+    """Can sug_mcd_loss_* take these logits?  (fp32, C <= 64, at most 1024 rows per domain; the target cross entropy is taken
+    against the SOURCE labels by its caller, so a_t != 0 needs Ms == Mt.)  False is not an error: the caller composes the ops."""
+    ts = [t for t in (ys1, ys2, yt1, yt2) if t is not None]
+    if len(ts) not in (2, 4) or any(not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 for t in ts):
+        return False
+    C = ys1.shape[1]
+    if any(t.shape[1] != C for t in ts) or not 2 <= C <= MCD_MAX_CLASSES or ys1.shape != ys2.shape:
+        return False
+    if yt1 is None:
+        if label is None:
+            return False
+        Ms, Mt = label.numel(), ys1.shape[0] - label.numel()
+    else:
+        Ms, Mt = ys1.shape[0], yt1.shape[0]
+        if yt1.shape != yt2.shape or (label is not None and label.numel() != Ms):
+            return False
+    return 1 <= Ms <= MCD_MAX_ROWS and 1 <= Mt <= MCD_MAX_ROWS and (a_t == 0 or Ms == Mt)
+
+
+def mcd_loss(ys1, ys2, yt1, yt2, label, label_t=None, a_s=1.0, a_t=0.0, r_s=1.0, totals=None):
+    """a_s*(CE(ys1) + CE(ys2)) + a_t*(CE(yt1, label_t) + CE(yt2, label_t)) - mean|softmax(yt1) - softmax(yt2)| in one launch each
+    way -> (loss, r_s*CEs, -D, a_t*CEt), 0-d; only `loss` is differentiable, the others are the values the trainers report.
+    yt1 = yt2 = None: ys1, ys2 are the paired [Ms + Mt, C] logits of Net_MDA.forward_pair(paired_out=True), Ms = len(label).
+    A label outside [0, C) -> NaN (no ignore_index).  totals: None or a device float64 [4], advanced by
+    (r_s*CEs*Ms, -D*Ms, Ms, Mt) in the same launch -- the books of train_uda.py:180-184."""
+    return _MCDLoss.apply(ys1, ys2, yt1, yt2, label, label_t, a_s, a_t, r_s, totals)
+
+
 # ----------------------------------------------------------------------------- evaluation metrics (sug_eval_accumulate)
 EVAL_MAX_ROWS, EVAL_MAX_CLASSES = 4096, 64              # SUG_EVAL_MAX_ROWS, SUG_EVAL_MAX_CLASSES
 EVAL_BATCH_COUNT, EVAL_DATA_TOTAL, EVAL_CORRECT_TOTAL, EVAL_ERROR, EVAL_LOSS_TOTAL = 0, 1, 2, 3, 4
