@@ -1,13 +1,17 @@
-"""What the three hipGraph front ends share (SUGStep's graph step, call_graphs.CallGraphs, eval_graphs.EvalRunner).
+"""What the hipGraph front ends share: the three that replay a forward or SUGStep's own step (SUGStep's graph step,
+call_graphs.CallGraphs, eval_graphs.EvalRunner) and the step classes built on `ReplayedStep` (SourceStep, UDAStep).
 
 Each of them runs a key eagerly once under `StartFeeder.recording()`, captures it under `StartFeeder.providing()` and from
 then on copies the inputs, calls `refill()` and replays.  The capture itself stays written out at each site, as
-`with feeder.providing(), ops.capture_guard(), torch.cuda.graph(...)`; no context manager is entered on a replay path.
+`with feeder.providing(), ops.capture_guard(), torch.cuda.graph(...)`; no context manager is entered and nothing new is
+allocated on a replay path.  The small choices every step class makes the same way (Adam class, by-value hyper key, plan
+generations, weight caches, the plain-CE predicate) are the functions at the end.
 """
 import collections
 import contextlib
 
 import torch
+import torch.nn as nn
 
 from . import ops
 
@@ -106,3 +110,125 @@ def tensor_outputs(out):
     """(outs, single): one tensor or a tuple of tensors (or None) as a list, and whether it was the single tensor."""
     single = isinstance(out, torch.Tensor)
     return ([out] if single else list(out if out is not None else ())), single
+
+
+def adam_choice(on_gpu, fused_adam, use_graph):
+    """(Adam class, keyword arguments).  fused_adam None/True -> sug_amd.optim.Adam (one launch per optimizer) on a HIP
+    device, with step count / bias corrections / lr on the device; False, or a CPU -> torch.optim.Adam, capturable under
+    `use_graph` only."""
+    if on_gpu and (fused_adam is None or fused_adam):
+        from .optim import Adam
+        return Adam, {'graph_capturable': True}
+    return torch.optim.Adam, ({'capturable': True, 'fused': True} if use_graph else {})
+
+
+def hyper_key(opt):
+    """What a captured step bakes in of an optimizer by value.  sug_amd.optim.Adam keeps lr on the device (one graph serves
+    a whole schedule); any other optimizer takes it by value, so there the lr of every group is part of the key."""
+    if hasattr(opt, 'graph_key'):
+        return opt.graph_key()
+    return tuple((g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']) for g in opt.param_groups)
+
+
+def plan_generations(opts):
+    """The device-side plan generation of every optimizer-like object (0 for one without, None included): a captured graph
+    holds raw pointers into those plans and must not outlive them."""
+    return tuple(getattr(o, 'plan_generation', 0) for o in opts)
+
+
+def drop_weight_caches(model, split_layers, prefix):
+    """Nothing computed from the weights outlives the update that follows: the encoder's prefix cache (if `prefix`) and the
+    EdgeConv weight-split cache of every layer in `split_layers`."""
+    if prefix:
+        model.g.clear_prefix_cache()
+    for m in split_layers:
+        m._wcat = None
+
+
+def plain_ce(criterion, smoothing_ok=False):
+    """A criterion the fused CE kernels compute exactly: nn.CrossEntropyLoss itself, no class weights, reduction 'mean' and --
+    unless the caller's kernel takes it (`smoothing_ok`) -- no label smoothing."""
+    c = criterion
+    return type(c) is nn.CrossEntropyLoss and c.weight is None and c.reduction == 'mean' and \
+        (smoothing_ok or c.label_smoothing == 0.0)
+
+
+def _release(st):
+    st['graph'] = st['in'] = st['out'] = None
+    ops.clear_rows_cache()      # may hold a tensor of the freed pool
+
+
+class ReplayedStep:
+    """A training step replayed as ONE hipGraph per key.  The subclass supplies `_opts()` (its optimizers), `_graph_key(...)`
+    (everything a captured step bakes in by value) and `_eager_step(*batch)` -> one tensor or a tuple of tensors; it counts
+    in `_rows_host` what its eager step counts on the host, so that a replay can add the same.  The first step of a key runs
+    eagerly under the feeder's recording(), the second is captured, later ones copy the batch into the static inputs, refill
+    the starts and replay; a key whose capture failed stays eager, with the reason in `why`.  At most `max_graphs` captured
+    steps are kept (least recently used first out)."""
+
+    def __init__(self, max_graphs, rows):
+        self.max_graphs = int(max_graphs)
+        self._graphs = LRU(self.max_graphs, _release)
+        self.stats = {'planned': 0, 'captured': 0, 'replayed': 0, 'refused': 0}
+        self.why = None                                     # reason of the last refusal
+        self._rows_host = [0] * rows
+
+    def _plan_generations(self):
+        return plan_generations(self._opts())
+
+    def _graph_step(self, batch):
+        key = self._graph_key(batch)
+        for o in self._opts():                              # a schedule step since the last replay: new lr -> device
+            if hasattr(o, 'refresh_device_scalars'):
+                o.refresh_device_scalars()
+        self._graphs.limit = self.max_graphs
+        st = self._graphs.get(key)
+        if st is not None and st['gens'] is not None and st['gens'] != self._plan_generations():
+            del self._graphs[key]                           # raw pointers into a freed Adam plan: never replay
+            _release(st)
+            st = None
+        if st is None:                                      # first step of the key: eager, the feeder records the start plan
+            st = self._graphs.put(key, {'feeder': StartFeeder(batch[0].device), 'graph': None, 'in': None, 'out': None,
+                                        'gens': None, 'why': None, 'rows': (), 'single': True})
+            self.stats['planned'] += 1
+            with st['feeder'].recording():
+                out = self._eager_step(*batch)
+            st['feeder'].build()
+            return out
+        if st['why'] is not None:                           # a refused key stays eager, in this process
+            return self._eager_step(*batch)
+        if st['graph'] is None:
+            try:
+                self._capture(st, batch)
+            except Exception as e:
+                _release(st)
+                st['why'] = self.why = refusal_text(e)
+                self.stats['refused'] += 1
+                for o in self._opts():                      # gradients of the aborted capture point into its discarded pool
+                    o.zero_grad(set_to_none=True)
+                return self._eager_step(*batch)
+            st['gens'] = self._plan_generations()
+            self.stats['captured'] += 1
+        for dst, src in zip(st['in'], batch):
+            if dst.data_ptr() != src.data_ptr():
+                dst.copy_(src, non_blocking=True)
+        st['feeder'].refill()
+        st['graph'].replay()
+        self.stats['replayed'] += 1
+        for i, n in enumerate(st['rows']):                  # rows the captured step counts on the host
+            self._rows_host[i] += n
+        out = st['out'].clone()                             # the caller's own: the next replay overwrites the static tensor
+        return out if st['single'] else out.unbind(0)
+
+    def _capture(self, st, batch):
+        st['in'] = [t.clone() for t in batch]
+        for o in self._opts():
+            o.zero_grad(set_to_none=True)
+        st['graph'] = torch.cuda.CUDAGraph()
+        rows0 = list(self._rows_host)
+        with st['feeder'].providing(), ops.capture_guard(), torch.cuda.graph(st['graph']):
+            outs, st['single'] = tensor_outputs(self._eager_step(*st['in']))
+            st['out'] = outs[0] if st['single'] else torch.stack(outs)     # a tuple: one static tensor, one clone per replay
+        st['rows'] = tuple(a - b for a, b in zip(self._rows_host, rows0))
+        self._rows_host[:] = rows0                          # (a capture runs nothing: its host count is taken back)
+        ops.clear_rows_cache()

@@ -1791,6 +1791,21 @@ def w16_prefill(plan):
     return {key: (p._version, buf, p) for key, p, buf in plan}
 
 
+@contextlib.contextmanager
+def w16_scope(holder, slot):
+    """The forwards of one step (or of one phase of it) share their 16-bit weight copies; `holder[slot]` keeps the plan from
+    one block to the next, so that from the second on all copies are refreshed by one multi-tensor copy into the first's
+    buffers.  Off (no cache) outside the Point Transformer's 16-bit mode."""
+    from .model import Ptran_transformer as _PT
+    CTX.w16_cache = w16_prefill(holder[slot] or []) if _PT.GEMM_DTYPE is not None else None
+    try:
+        yield
+    finally:
+        if CTX.w16_cache is not None:
+            holder[slot] = w16_plan(CTX.w16_cache)
+        CTX.w16_cache = None
+
+
 def _dweight(gy, x):
     """gy^T . x over the R rows in row chunks (batched GEMM = split-K: one [M,K] product alone fills few
     workgroups), chunk results summed in fp32; 16-bit operands give fp32 products straight out of the GEMM."""

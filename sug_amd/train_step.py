@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .graph_replay import LRU, StartFeeder
+from .graph_replay import LRU, StartFeeder, adam_choice, drop_weight_caches, hyper_key, plain_ce, plan_generations
 from .model import mmd
 
 GEO_MMD = {'NAME': 'SOFT_MMD', 'LABEL_SCALE': 50, 'GEO_SCALE': 1}
@@ -79,18 +79,19 @@ def gather_rows_ddp(x):
     return _all_gather_rows(x)
 
 
-def gather_rows_packed(tensors):
-    """gather_rows_ddp of several [m, w_i] tensors with ONE collective (one all-gather forward, one
-    reduce-scatter backward): the columns are packed side by side, gathered, and split again.
-    Integer tensors ride along as exact small floats.  Returns the gathered [world*m, w_i] tensors."""
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return list(tensors)
+def pack_columns(tensors):
+    """(packed, meta): several [m, ...] tensors side by side as the columns of one [m, W] fp32 tensor.  Integer tensors ride
+    along as exact small floats (values only: they carry no gradient)."""
     cols, meta = [], []
     for t in tensors:
         t2 = t.reshape(t.shape[0], -1)
         meta.append((t2.shape[1], t.dtype, tuple(t.shape[1:])))
         cols.append(t2 if t2.dtype == torch.float32 else t2.detach().to(torch.float32))
-    G = gather_rows_ddp(torch.cat(cols, dim=1))
+    return torch.cat(cols, dim=1), meta
+
+
+def unpack_columns(G, meta):
+    """The tensors of pack_columns again, with the rows G has (those of every rank after a gather)."""
     out, off = [], 0
     for w, dt, tail in meta:
         g = G[:, off:off + w]
@@ -99,6 +100,25 @@ def gather_rows_packed(tensors):
             g = g.round().to(dt)
         out.append(g.reshape((G.shape[0],) + tail))
     return out
+
+
+def gather_rows_packed(tensors):
+    """gather_rows_ddp of several [m, w_i] tensors with ONE collective (one all-gather forward, one
+    reduce-scatter backward): the columns are packed side by side, gathered, and split again.
+    Integer tensors ride along as exact small floats.  Returns the gathered [world*m, w_i] tensors."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return list(tensors)
+    packed, meta = pack_columns(tensors)
+    return unpack_columns(gather_rows_ddp(packed), meta)
+
+
+def _grads_as_views(params, flat):
+    """Every p.grad becomes a view of its stretch of `flat`: the averaged gradients stay in the flat buffer, no copy back."""
+    off = 0
+    for p in params:
+        n = p.numel()
+        p.grad = flat[off:off + n].view_as(p)
+        off += n
 
 
 def allreduce_grads_(params, world):
@@ -111,11 +131,7 @@ def allreduce_grads_(params, world):
     flat = torch.cat([p.grad.reshape(-1) for p in ps])
     dist.all_reduce(flat)
     flat.div_(world)
-    off = 0
-    for p in ps:                    # the averaged gradients stay in the flat buffer: no copy back
-        n = p.numel()
-        p.grad = flat[off:off + n].view_as(p)
-        off += n
+    _grads_as_views(ps, flat)
 
 
 class GradReducer:
@@ -183,14 +199,15 @@ class GradReducer:
             if flat is None:
                 continue
             flat.div_(self.world)
-            off = 0
-            for p in self.members[bi]:            # the averaged gradients stay in the flat buffer
-                n = p.numel()
-                p.grad = flat[off:off + n].view_as(p)
-                off += n
+            _grads_as_views(self.members[bi], flat)
         if self.key not in self.expected:
             self.expected[self.key] = [set(s) for s in self.seen]
         self.flats = self.members = self.handles = None
+
+
+def _params_above_encoder(model):
+    """The parameters above the encoder (heads, attention layers): their gradients are ready first in a backward."""
+    return [p for m in (model.c1, model.c2, model.attention_s, model.attention_t) for p in m.parameters()]
 
 
 class SUGStep:
@@ -230,13 +247,8 @@ class SUGStep:
         self.global_mmd = global_mmd and (self.world > 1 or force_segmented)
         self.reducer = None
         if self.world > 1 and not use_graph:     # eager multi-rank steps: bucketed all-reduce from autograd hooks
-            early = [p for m in (model.c1, model.c2, model.attention_s, model.attention_t) for p in m.parameters()]
-            self.reducer = GradReducer([early, list(model.g.parameters())], self.world)
-        # fused_adam: None/True -> sug_amd.optim.Adam (one launch per optimizer) on a HIP device;
-        # False -> torch.optim.Adam's default path (the parity tests' reference update)
-        kw = {}
+            self.reducer = GradReducer([_params_above_encoder(model), list(model.g.parameters())], self.world)
         on_gpu = next(model.parameters()).is_cuda
-        own_adam = on_gpu and (fused_adam is None or fused_adam)
         # hipGraph mode: the whole step (forwards, losses, backward, 3 Adam updates) is captured once and replayed, FPS
         # start indices fed through a static buffer.  One rank: one graph per configuration key;
         # more ranks: five captured segments around the four collectives (_capture_segments).
@@ -244,6 +256,7 @@ class SUGStep:
         self.segmented = self.use_graph and (self.world > 1 or force_segmented)
         self._graphs = None
         self._total = None
+        self._w16_plan = None                           # ops.w16_scope's slot: the 16-bit weight copies of the last step
         self._combine_tail = os.environ.get('SUG_FUSED_LOSS', '1') != '0'
         self._mmd_multi = os.environ.get('SUG_MMD_MULTI', '1') != '0'   # the step's MMD terms stage by stage in one launch
         self.max_graphs = 4                             # captured steps kept (each owns a private memory pool)
@@ -253,8 +266,11 @@ class SUGStep:
         # SUG_GRAPH_GUARD=1 restores the historical guard (one eager op between two replays)
         self._tick = torch.zeros(1, device=next(model.parameters()).device) \
             if (self.use_graph and os.environ.get('SUG_GRAPH_GUARD') == '1') else None
-        from .optim import Adam as _SugAdam
-        AdamCls = _SugAdam if own_adam else torch.optim.Adam
+        # fused_adam=False: torch.optim.Adam's default path (the parity tests' reference update)
+        AdamCls, kw = adam_choice(on_gpu, fused_adam, self.use_graph)
+        if not self.use_graph:
+            kw = {}                                     # (eager steps: sug_amd.optim.Adam with its scalars on the host)
+        own_adam = AdamCls is not torch.optim.Adam
         # fused small ops (LayerNorm + activation of the heads in one launch); scoped to this trainer's forwards (set and
         # restored around self.losses()).  On in eager AND in graph mode since round 4: both modes then run the same kernels,
         # and a captured step equals its eager twin bit for bit (tests/test_gpu_determinism.py)
@@ -263,12 +279,6 @@ class SUGStep:
         # streams inside the captured graph.  Measured SLOWER on ROCm 7.2 / MI355X (5.35 vs 5.26 ms per step: a cross-stream
         # edge of a hipGraph costs more than the ~5 us kernels it lets overlap), hence off.
         self.parallel_branches = self.use_graph and os.environ.get('SUG_PARALLEL_BRANCHES', '0') == '1'
-        if self.use_graph:
-            if own_adam:
-                kw['graph_capturable'] = True           # step count / bias corrections / lr on the device
-            else:
-                kw['capturable'] = True
-                kw['fused'] = True
         # train_dg_single_gpu.py:191-203
         params = [{'params': v} for k, v in model.g.named_parameters() if 'pred_offset' not in k]
         self.optimizer_g = AdamCls(params, lr=lr, weight_decay=weight_decay, **kw)
@@ -348,6 +358,7 @@ class SUGStep:
         """(loss_cls, loss_geo, loss_sem), each differentiable.  combine=True (the step's own call): the total is formed in
         one launch each way and kept in self._total; the returned geo / sem parts are then values for reporting only."""
         M = self.methods
+        ce_only = plain_ce(self.criterion) and M['ADV_WEIGHT'] <= 0 and M['TARGET_LOSS'] <= 0    # what ops.ce_pair computes
         model = self.model
         pair = None
         fused_ce = None
@@ -358,10 +369,7 @@ class SUGStep:
             if mmd_on and M['MMD_WEIGHT'] > 0 and not dual and hasattr(model, 'plan_pair_geometry') \
                     and os.environ.get('SUG_PLAN_GEOMETRY', '1') != '0':
                 model.plan_pair_geometry(pair, passes=2)    # FPS / ball query of the semantic AND the node pass in one set of launches
-            plain_ce = isinstance(self.criterion, nn.CrossEntropyLoss) and self.criterion.weight is None \
-                and self.criterion.reduction == 'mean' and self.criterion.label_smoothing == 0.0 \
-                and M['ADV_WEIGHT'] <= 0 and M['TARGET_LOSS'] <= 0
-            if plain_ce and os.environ.get('SUG_FUSED_LOSS', '1') != '0':
+            if ce_only and os.environ.get('SUG_FUSED_LOSS', '1') != '0':
                 # the paired logits / mid features stay paired: CE of both heads in one launch each way (ops.ce_pair writes the
                 # whole pair's gradient), the halves of the mid features split with a copy-free backward
                 if dual:
@@ -393,9 +401,7 @@ class SUGStep:
         # and one backward (0.5*a + 0.5*b = 0.5*(a + b) exactly; the folded weights differ from the reference's
         # left-to-right products by an ulp at most)
         if fused_ce is None and pair is None and self._combine_tail and model.training and pred_s1.is_cuda \
-                and isinstance(self.criterion, nn.CrossEntropyLoss) and self.criterion.weight is None \
-                and self.criterion.reduction == 'mean' and self.criterion.label_smoothing == 0.0 \
-                and M['ADV_WEIGHT'] <= 0 and M['TARGET_LOSS'] <= 0 and pred_s1.dim() == 2 \
+                and ce_only and pred_s1.dim() == 2 \
                 and ops.ce_pair_supported(pred_s1, pred_s2, label):
             # the separate-calls form (the four model(...) calls of an unchanged caller): CE of both heads in one launch each
             # way as well (ops.ce_pair scores the first len(label) rows: here all of them)
@@ -481,16 +487,10 @@ class SUGStep:
     def _graph_key(self, mmd_on, tensors):
         """Everything a captured step bakes in by value.  sug_amd.optim.Adam keeps lr on the device (one graph serves a
         whole schedule); any other optimizer takes lr by value, so its lr of every group is part of the key."""
-        hyp = []
-        for o in self._opts():
-            if hasattr(o, 'graph_key'):
-                hyp.append(o.graph_key())
-            else:
-                hyp.append(tuple((g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']) for g in o.param_groups))
-        return (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyp))
+        return (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()))
 
     def _plan_generations(self):
-        return tuple(getattr(o, 'plan_generation', 0) for o in self._opts() + (self._adam_chain,))
+        return plan_generations(self._opts() + (self._adam_chain,))
 
     def _optimizers_step(self):
         if self._adam_chain is not None:
@@ -622,13 +622,7 @@ class SUGStep:
                                 f_t2.detach(), p_s1.detach(), p_t1.detach(), p_s2.detach(), p_t2.detach()]
                         if geo.get('GEO_WEIGHTS'):
                             vals.append(mmd.chamfer_distances(data, data_t).reshape(-1, 1))
-                        cols, meta = [], []
-                        for t in vals:
-                            t2 = t.reshape(t.shape[0], -1)
-                            meta.append((t2.shape[1], t.dtype, tuple(t.shape[1:])))
-                            cols.append(t2 if t2.dtype == torch.float32 else t2.to(torch.float32))
-                        S['meta'] = meta
-                        S['packed'] = torch.cat(cols, dim=1)
+                        S['packed'], S['meta'] = pack_columns(vals)
                 finally:
                     model._cuts = None
 
@@ -644,13 +638,7 @@ class SUGStep:
         def seg_b(S):
             if not mmd_on:
                 return
-            G, off, g = S['static']['G'], 0, []
-            for w, dt, tail in S['meta']:
-                t = G[:, off:off + w]
-                off += w
-                if dt != torch.float32:
-                    t = t.round().to(dt)
-                g.append(t.reshape((G.shape[0],) + tail))
+            g = unpack_columns(S['static']['G'], S['meta'])
             label_g, label_tg, fn_s, fn_t, g_s1, g_t1, g_s2, g_t2, g_p1s, g_p1t, g_p2s, g_p2t = g[:12]
             node_s, node_t, f_s1, f_t1, f_s2, f_t2 = S['loc']
             M_all, row0 = label_g.shape[0], rank * mloc
@@ -694,8 +682,7 @@ class SUGStep:
             st_ = S['static']
             early = st_.get('early')
             if early is None:                             # (planning step) the parameters above the cut
-                early = [p for m in (model.c1, model.c2, model.attention_s, model.attention_t) for p in m.parameters()
-                         if p.requires_grad]
+                early = [p for p in _params_above_encoder(model) if p.requires_grad]
             grads = torch.autograd.grad(loss, early + cuts, allow_unused=True)
             ge, gc = grads[:len(early)], grads[len(early):]
             if 'early' not in st_:
@@ -718,10 +705,7 @@ class SUGStep:
             cg = S['cut_grads']
             torch.autograd.backward([t for t, _ in cg], [g for _, g in cg])
             ops.clear_rows_cache()
-            if self.share_prefix:
-                model.g.clear_prefix_cache()
-            for m in self._split_layers:
-                m._wcat = None
+            drop_weight_caches(model, self._split_layers, self.share_prefix)
             st_ = S['static']
             if 'late' not in st_:
                 st_['late'] = [p for p in model.g.parameters() if p.grad is not None]
@@ -749,11 +733,7 @@ class SUGStep:
             st_ = S['static']
             for ps, flat in ((st_['early'], st_['flat1']), (st_['late'], st_['flat2'])):
                 flat.div_(world)
-                off = 0
-                for p in ps:                              # the averaged gradients stay in the flat buffers
-                    n = p.numel()
-                    p.grad = flat[off:off + n].view_as(p)
-                    off += n
+                _grads_as_views(ps, flat)
             self._optimizers_step()
             self.optimizer_g.zero_grad()
             self.optimizer_c.zero_grad()
@@ -817,8 +797,7 @@ class SUGStep:
             self._graphs.pop(key, None)
             for o in self._opts():                        # gradients of the aborted capture point into its discarded pool
                 o.zero_grad(set_to_none=True)
-            if self.share_prefix:
-                self.model.g.clear_prefix_cache()
+            drop_weight_caches(self.model, (), self.share_prefix)      # (the prefix cache only)
             raise RuntimeError('segmented hipGraph capture failed on %s: %s' % (
                 'this rank' if err is not None else 'another rank', str(err).splitlines()[0] if err is not None else ''))
         st['graphs'], st['segs'], st['out'] = graphs, segs, S['out']
@@ -862,16 +841,10 @@ class SUGStep:
         """The forwards of one step: the trainer's `fused_heads` / `parallel_branches` switched on (if it or the context
         asks), and 16-bit weight copies shared by them -- from the second step on refreshed by one multi-tensor copy into the
         first step's buffers (`_w16_plan`)."""
-        from .model import Ptran_transformer as _PT
-        ops.CTX.w16_cache = ops.w16_prefill(getattr(self, '_w16_plan', None) or []) if _PT.GEMM_DTYPE is not None else None
-        try:
-            with ops.CTX.scoped(fused_heads=self.fused_heads or ops.CTX.fused_heads,
-                                parallel_branches=self.parallel_branches or ops.CTX.parallel_branches):
-                yield
-        finally:
-            if ops.CTX.w16_cache is not None:
-                self._w16_plan = ops.w16_plan(ops.CTX.w16_cache)
-            ops.CTX.w16_cache = None
+        with ops.w16_scope(self.__dict__, '_w16_plan'), \
+                ops.CTX.scoped(fused_heads=self.fused_heads or ops.CTX.fused_heads,
+                               parallel_branches=self.parallel_branches or ops.CTX.parallel_branches):
+            yield
 
     def _eager_step(self, data, label, data_t, label_t, epoch=0):
         mmd_on = epoch >= self.methods['PURE_CLS_EPOCH']
@@ -886,16 +859,12 @@ class SUGStep:
             if loss_sem is not None:
                 loss = loss + loss_sem
         if self.world > 1 and self.reducer is None:      # a graph-mode trainer switched to eager launches
-            early = [p for m in (self.model.c1, self.model.c2, self.model.attention_s, self.model.attention_t) for p in m.parameters()]
-            self.reducer = GradReducer([early, list(self.model.g.parameters())], self.world)
+            self.reducer = GradReducer([_params_above_encoder(self.model), list(self.model.g.parameters())], self.world)
         if self.reducer is not None:
             self.reducer.begin(mmd_on)
         loss.backward()
         ops.clear_rows_cache()                           # the [2B,N,3] rows of this step's batch: not kept beyond the step
-        if self.share_prefix:
-            self.model.g.clear_prefix_cache()
-        for m in self._split_layers:
-            m._wcat = None
+        drop_weight_caches(self.model, self._split_layers, self.share_prefix)
         if self.reducer is not None:
             self.reducer.finish()
         self._optimizers_step()

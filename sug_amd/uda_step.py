@@ -13,11 +13,11 @@ Two quirks of the reference survive because the loop is taken literally: the `pr
 of optimizer_g, so the gradient phase 1 gives them is not cleared by optimizer_g.zero_grad() and is applied, added to phase 2's, by
 optimizer_dis; and the encoder's parameters keep separate Adam moments in optimizer_g and optimizer_dis.
 
-Launch forms, as SourceStep: the first step of a key runs eagerly under the FPS start feeder's recording(), the second is captured
-(ONE graph: both phases, all three updates, one stream), later ones copy the batch into the static inputs, refill the starts and
-replay.  With a plain nn.CrossEntropyLoss the scalar tail of phase 1 is ops.mcd_loss (one launch each way, which also keeps four of
-the five books); any other criterion, or fused_loss=False, composes it from torch ops and keeps the books by in-place adds.  Nothing
-waits for the device until `epoch_totals()`.  `use_graph=False` launches the same ops eagerly: the graph's bit-for-bit twin.
+Launch forms, as SourceStep: the step is a graph_replay.ReplayedStep, planned, captured (ONE graph: both phases, all three
+updates, one stream) and replayed by that class's protocol.  With a plain nn.CrossEntropyLoss the scalar tail of phase 1 is
+ops.mcd_loss (one launch each way, which also keeps four of the five books); any other criterion, or fused_loss=False, composes
+it from torch ops and keeps the books by in-place adds.  Nothing waits for the device until `epoch_totals()`.
+`use_graph=False` launches the same ops eagerly: the graph's bit-for-bit twin.
 
 What is shared "per step" elsewhere is per PHASE here, because the weights change in between: the 16-bit weight copies of the Point
 Transformer's fp16 mode are refreshed at the start of each phase (phase 2: after the g / c update), the encoder's prefix cache and
@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .graph_replay import LRU, StartFeeder, refusal_text
+from .graph_replay import ReplayedStep, adam_choice, drop_weight_caches, hyper_key, plain_ce
 from .model import mmd
 from .train_step import discrepancy
 
@@ -56,12 +56,7 @@ def _draw(B, N):
     return torch.randint(0, N, (B,), dtype=torch.long)
 
 
-def _release(st):
-    st['graph'] = st['in'] = st['out'] = None
-    ops.clear_rows_cache()      # may hold a tensor of the freed pool
-
-
-class UDAStep:
+class UDAStep(ReplayedStep):
     def __init__(self, model, recipe='uda', lr=1e-3, weight_decay=5e-5, lr_scaler=1.0, src_weight=1.0, target_loss=0.0,
                  class_mmd=None, criterion=None, use_graph=True, fused_adam=None, fused_loss=True, pair_domains=True,
                  max_graphs=4):
@@ -78,8 +73,8 @@ class UDAStep:
         self.device = p0.device
         on_gpu = p0.is_cuda
         capturable = getattr(getattr(model, 'g', None), 'graph_capturable', True)
+        super().__init__(max_graphs, rows=2)
         self.use_graph = bool(use_graph) and on_gpu
-        self.why = None                                 # reason of the last refusal
         if self.use_graph and not capturable:           # Net_MDA('KPConv'): no static launch sequence, always eager
             self.use_graph = False
             self.why = '%s: level sizes depend on the data' % type(model.g).__name__
@@ -87,17 +82,7 @@ class UDAStep:
         # fused_loss=False is the plain composition throughout: the loss tail from torch ops and the heads' LayerNorm +
         # activation unfused, i.e. exactly what an unchanged caller's model(...) calls launch
         self.fused_loss = bool(fused_loss) and on_gpu
-        # fused_adam: None/True -> sug_amd.optim.Adam (one launch per optimizer) on a HIP device; False -> torch.optim.Adam
-        own_adam = on_gpu and (fused_adam is None or fused_adam)
-        kw = {}
-        if own_adam:
-            from .optim import Adam as AdamCls
-            kw['graph_capturable'] = True               # step count / bias corrections / lr on the device, in both launch modes
-        else:
-            AdamCls = torch.optim.Adam
-            if self.use_graph:
-                kw['capturable'] = True
-                kw['fused'] = True
+        AdamCls, kw = adam_choice(on_gpu, fused_adam, self.use_graph)
         params = [{'params': v} for k, v in model.g.named_parameters() if 'pred_offset' not in k]
         self.optimizer_g = AdamCls(params, lr=lr, weight_decay=weight_decay, **kw)
         self.optimizer_c = AdamCls([{'params': model.c1.parameters()}, {'params': model.c2.parameters()}], lr=self.c_lr,
@@ -105,13 +90,9 @@ class UDAStep:
         self.optimizer_dis = AdamCls([{'params': model.g.parameters()}, {'params': model.attention_s.parameters()},
                                       {'params': model.attention_t.parameters()}], lr=lr * lr_scaler, weight_decay=weight_decay,
                                      **kw)
-        self.max_graphs = int(max_graphs)
-        self._graphs = LRU(self.max_graphs, _release)
-        self.stats = {'planned': 0, 'captured': 0, 'replayed': 0, 'refused': 0}
         # the books of train_uda.py:130-135, :180-184: [loss_s*B, loss_adv*B, rows, target rows, loss_node*B]; the rows of steps
         # whose loss tail is composed are counted on the host (their number is known there)
         self._books = torch.zeros(5, dtype=torch.float64, device=self.device) if on_gpu else None
-        self._rows_host = [0, 0]
         self._w16_plans = [None, None]
         self._split_layers = [m for m in model.modules() if hasattr(m, 'cache_weight_split')]
 
@@ -148,7 +129,7 @@ class UDAStep:
         rows_t += self._rows_host[1]
         if reset:
             self._books.zero_()
-            self._rows_host = [0, 0]
+            self._rows_host[:] = (0, 0)
         return float(ls), float(adv), float(node), float(rows), float(rows_t)
 
     # ------------------------------------------------------------------ step
@@ -164,80 +145,15 @@ class UDAStep:
             return self._graph_step((data, label, data_t, label_t))
         return self._eager_step(data, label, data_t, label_t)
 
-    def _plain_ce(self):
-        c = self.criterion
-        return type(c) is nn.CrossEntropyLoss and c.weight is None and c.reduction == 'mean' and c.label_smoothing == 0.0
-
     def _graph_key(self, batch):
-        """Everything a captured step bakes in by value (`cons` is not: GradReverse is the identity).  sug_amd.optim.Adam keeps
-        lr on the device; torch's takes it by value, so there it is part of the key."""
+        """Everything a captured step bakes in by value (`cons` is not: GradReverse is the identity)."""
         from .model import Ptran_transformer as PT
         c = self.criterion
-        crit = ('ce', int(c.ignore_index)) if self._plain_ce() else ('call', id(c), repr(c))
-        hyp = tuple(o.graph_key() if hasattr(o, 'graph_key') else
-                    tuple((g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']) for g in o.param_groups) for o in self._opts())
+        crit = ('ce', int(c.ignore_index)) if plain_ce(c) else ('call', id(c), repr(c))
+        hyp = tuple(hyper_key(o) for o in self._opts())
         return (tuple(tuple(t.shape) for t in batch), self.recipe, self.a_s, self.a_t, self.r_s, self.src_weight, self.target_loss,
                 repr(sorted(self.class_mmd.items())), crit, self.model.training, self.fused_loss, self.pair_domains,
                 PT.GEMM_DTYPE, getattr(PT, 'PROJ_16BIT', None), hyp)
-
-    def _plan_generations(self):
-        return tuple(getattr(o, 'plan_generation', 0) for o in self._opts())
-
-    def _graph_step(self, batch):
-        key = self._graph_key(batch)
-        for o in self._opts():                              # a schedule step since the last replay: new lr -> device
-            if hasattr(o, 'refresh_device_scalars'):
-                o.refresh_device_scalars()
-        self._graphs.limit = self.max_graphs
-        st = self._graphs.get(key)
-        if st is not None and st['gens'] is not None and st['gens'] != self._plan_generations():
-            del self._graphs[key]                           # raw pointers into a freed Adam plan: never replay
-            _release(st)
-            st = None
-        if st is None:                                      # first step of the key: eager, the feeder records the start plan
-            st = self._graphs.put(key, {'feeder': StartFeeder(batch[0].device), 'graph': None, 'in': None, 'out': None,
-                                        'gens': None, 'why': None, 'rows': (0, 0)})
-            self.stats['planned'] += 1
-            with st['feeder'].recording():
-                out = self._eager_step(*batch)
-            st['feeder'].build()
-            return out
-        if st['why'] is not None:                           # a refused key stays eager, in this process
-            return self._eager_step(*batch)
-        if st['graph'] is None:
-            try:
-                self._capture(st, batch)
-            except Exception as e:
-                _release(st)
-                st['why'] = self.why = refusal_text(e)
-                self.stats['refused'] += 1
-                for o in self._opts():                      # gradients of the aborted capture point into its discarded pool
-                    o.zero_grad(set_to_none=True)
-                return self._eager_step(*batch)
-            st['gens'] = self._plan_generations()
-            self.stats['captured'] += 1
-        for dst, src in zip(st['in'], batch):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src, non_blocking=True)
-        st['feeder'].refill()
-        st['graph'].replay()
-        self.stats['replayed'] += 1
-        self._rows_host[0] += st['rows'][0]                 # rows the captured step counts on the host (composed loss tail)
-        self._rows_host[1] += st['rows'][1]
-        out = st['out'].clone()                             # the caller's own: the next replay overwrites the static tensor
-        return out[0], out[1], out[2]
-
-    def _capture(self, st, batch):
-        st['in'] = [t.clone() for t in batch]
-        for o in self._opts():
-            o.zero_grad(set_to_none=True)
-        st['graph'] = torch.cuda.CUDAGraph()
-        rows0 = list(self._rows_host)
-        with st['feeder'].providing(), ops.capture_guard(), torch.cuda.graph(st['graph']):
-            st['out'] = torch.stack(self._eager_step(*st['in']))
-        st['rows'] = (self._rows_host[0] - rows0[0], self._rows_host[1] - rows0[1])
-        self._rows_host = rows0                             # (a capture runs nothing: its host count is taken back)
-        ops.clear_rows_cache()
 
     @contextlib.contextmanager
     def _step_scope(self):
@@ -255,22 +171,12 @@ class UDAStep:
         """The forwards of one PHASE: 16-bit weight copies (Point Transformer, fp16 mode) made from the weights as they are
         NOW -- from the second step on by one multi-tensor copy into the first step's buffers -- and every num_batches_tracked
         increment in one launch."""
-        from .model import Ptran_transformer as _PT
-        ops.CTX.w16_cache = ops.w16_prefill(self._w16_plans[phase] or []) if _PT.GEMM_DTYPE is not None else None
-        try:
-            with ops.deferred_bn_counts():
-                yield
-        finally:
-            if ops.CTX.w16_cache is not None:
-                self._w16_plans[phase] = ops.w16_plan(ops.CTX.w16_cache)
-            ops.CTX.w16_cache = None
+        with ops.w16_scope(self._w16_plans, phase), ops.deferred_bn_counts():
+            yield
 
     def _after_backward(self):
         """Nothing computed from the weights outlives the update that follows."""
-        if hasattr(self.model.g, 'clear_prefix_cache'):
-            self.model.g.clear_prefix_cache()
-        for m in self._split_layers:
-            m._wcat = None
+        drop_weight_caches(self.model, self._split_layers, hasattr(self.model.g, 'clear_prefix_cache'))
 
     def _eager_step(self, data, label, data_t, label_t):
         model, B, Bt = self.model, data.shape[0], data_t.shape[0]
@@ -279,7 +185,7 @@ class UDAStep:
             pair = torch.cat((data, data_t), dim=0)
         with self._step_scope():
             # ---- phase 1 (train_uda.py:149-166)
-            fused = self.fused_loss and self._plain_ce()
+            fused = self.fused_loss and plain_ce(self.criterion)
             out = None
             with self._phase_scope(0):
                 if pair is not None:
