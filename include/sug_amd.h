@@ -409,7 +409,7 @@ int sug_node_offset_bwd(const float* proj, const float* loc, const int32_t* fidx
                         const int32_t* gidx, const float* goff, int B, int N, int S, int ns,
                         float* dproj, void* stream);
 /* out[b,n,:] = [ fea[b,n,0:C1] | sum_t w_t * node[b, idx3[b,n,t], 0:C2] ] with the inverse-distance
- * weights of upsample_inter (model/point_utils.py:156-162) from the 3-NN distances d3.
+ * weights of upsample_inter (model/point_utils.py:156-162) from the 3-NN distances d3 (C1 == 0: fea may be null).
  * Backward (g = d out): dnode [B,S,C2] and dnloc [B,S,3] (both zero-initialised by the caller,
  * atomics); dnloc carries d3's gradient through d = |xyz - nloc|^2; d fea is g[:, :, 0:C1]. */
 int sug_interp3_cat_fwd(const float* fea, int64_t ldf, int C1, const float* node,
@@ -424,6 +424,9 @@ int sug_interp3_cat_bwd_lists(const float* g, int64_t ldg, int C1, const float* 
                               const float* d3, const float* xyz, const float* nloc, int B, int N, int S, int C2,
                               int32_t* rev_off, int32_t* rev_ent, float* ddw, float* dnode, float* dnloc,
                               void* stream);
+/* 1 when the reverse lists of idx3 (3N entries per cloud) fit the LDS-resident build sug_interp3_cat_bwd_lists needs;
+ * 0: zero-fill dnode / dnloc and call sug_interp3_cat_bwd (float atomics: not reproducible bit for bit). */
+int sug_interp3_cat_bwd_lists_supported(int B, int N, int S);
 
 /* ---- BatchNorm(+act) on rows: backward, and the fused DGCNN tail ----------------------------
  * Exact train-mode BN gradient for a per-point layer (conv_2d on [B,C,N,1],

@@ -545,7 +545,7 @@ extern "C" int sug_node_offset_bwd(const float* proj, const float* loc, const in
 extern "C" int sug_interp3_cat_fwd(const float* fea, int64_t ldf, int C1, const float* node,
                                    const int32_t* idx3, const float* d3, int B, int N, int S, int C2,
                                    float* out, int64_t ldo, void* stream) {
-  SUG_REQUIRE(fea && node && idx3 && d3 && out, "sug_interp3_cat_fwd: null pointer");
+  SUG_REQUIRE((fea || C1 == 0) && node && idx3 && d3 && out, "sug_interp3_cat_fwd: null pointer");
   SUG_REQUIRE(B > 0 && N > 0 && S >= 3 && C1 >= 0 && C2 > 0 && C1 % 4 == 0 && C2 % 4 == 0 && ldf % 4 == 0 &&
                   ldo % 4 == 0 && ldo >= C1 + C2 && ldf >= C1,
               "sug_interp3_cat_fwd: bad shape (channel counts and strides must be multiples of 4)");
@@ -575,6 +575,16 @@ extern "C" int sug_interp3_cat_bwd(const float* g, int64_t ldg, int C1, const fl
                      idx3, d3, xyz, nloc, N, S, C2, chunks, dnode, dnloc);
   SUG_LAUNCH_CHECK("sug_interp3_cat_bwd");
   return SUG_OK;
+}
+
+// knn.hip: LDS bytes of sug_reverse_lists for this shape (declared here as in group.hip, not in common.h)
+size_t sug_reverse_lists_lds_bytes(int B, int E, int N, int* ranges);
+
+// Do the reverse lists of idx3 (3N entries per cloud into S nodes) fit the LDS-resident build that
+// sug_interp3_cat_bwd_lists needs?  0: the caller zero-fills dnode / dnloc and takes sug_interp3_cat_bwd.
+extern "C" int sug_interp3_cat_bwd_lists_supported(int B, int N, int S) {
+  return (B > 0 && N > 0 && S >= 3 && (int64_t)3 * N <= INT32_MAX &&
+          sug_reverse_lists_lds_bytes(B, 3 * N, S, nullptr) <= 160 * 1024) ? 1 : 0;
 }
 
 // The same gradient without LDS accumulation: scratch rev_off [B,S+1], rev_ent [B,3N] (ints), ddw [B,N,6] (floats);

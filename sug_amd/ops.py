@@ -637,8 +637,8 @@ class _Interp3Cat(torch.autograd.Function):
         S, C2 = node.shape[1], node.shape[2]
         idx3, d3 = three_nn_raw(xyz, nlocd)
         out = torch.empty(B, N, C1 + C2, dtype=torch.float32, device=fea.device)
-        check(lib().sug_interp3_cat_fwd(_p(fea), ldf, C1, _p(node), _p(idx3), _p(d3), B, N, S, C2, _p(out),
-                                        C1 + C2, _st()), 'sug_interp3_cat_fwd')
+        check(lib().sug_interp3_cat_fwd(_p(fea) if C1 else None, ldf if C1 else 0, C1, _p(node), _p(idx3), _p(d3), B, N, S,
+                                        C2, _p(out), C1 + C2, _st()), 'sug_interp3_cat_fwd')
         ctx.save_for_backward(node, idx3, d3, xyz, nlocd)
         ctx.meta = (B, N, S, C1, C2)
         return out
@@ -648,14 +648,24 @@ class _Interp3Cat(torch.autograd.Function):
         node, idx3, d3, xyz, nloc = ctx.saved_tensors
         B, N, S, C1, C2 = ctx.meta
         g = g.contiguous()
-        dnode = torch.empty_like(node)
-        dnloc = torch.empty_like(nloc)
-        off = torch.empty(B, S + 1, dtype=torch.int32, device=g.device)
-        ent = torch.empty(B, 3 * N, dtype=torch.int32, device=g.device)
-        ddw = torch.empty(B, N, 6, dtype=torch.float32, device=g.device)
-        check(lib().sug_interp3_cat_bwd_lists(_p(g), C1 + C2, C1, _p(node), _p(idx3), _p(d3), _p(xyz), _p(nloc), B, N, S,
+        L = lib()
+        if L.sug_interp3_cat_bwd_lists_supported(B, N, S):
+            # fixed summation order (sorted reverse lists of idx3): reproducible bit for bit
+            dnode = torch.empty_like(node)
+            dnloc = torch.empty_like(nloc)
+            off = torch.empty(B, S + 1, dtype=torch.int32, device=g.device)
+            ent = torch.empty(B, 3 * N, dtype=torch.int32, device=g.device)
+            ddw = torch.empty(B, N, 6, dtype=torch.float32, device=g.device)
+            check(L.sug_interp3_cat_bwd_lists(_p(g), C1 + C2, C1, _p(node), _p(idx3), _p(d3), _p(xyz), _p(nloc), B, N, S,
                                               C2, _p(off), _p(ent), _p(ddw), _p(dnode), _p(dnloc), _st()),
-              'sug_interp3_cat_bwd_lists')
+                  'sug_interp3_cat_bwd_lists')
+        else:
+            # 3N entries per cloud do not fit the LDS-resident reverse-list build: the LDS-accumulating form (float
+            # atomics into zero-filled gradients; raises when its own [S, C2 + 3] accumulator does not fit either)
+            dnode = torch.zeros_like(node)
+            dnloc = torch.zeros_like(nloc)
+            check(L.sug_interp3_cat_bwd(_p(g), C1 + C2, C1, _p(node), _p(idx3), _p(d3), _p(xyz), _p(nloc), B, N, S, C2,
+                                        _p(dnode), _p(dnloc), _st()), 'sug_interp3_cat_bwd')
         return g[:, :, :C1], dnode, None, dnloc
 
 

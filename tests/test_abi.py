@@ -54,6 +54,22 @@ def test_version_and_error_string():
     assert rc == -1 and b'k' in L.sug_last_error()
 
 
+def test_interp3_cat_bwd_lists_supported_is_the_reverse_list_limit():
+    """sug_interp3_cat_bwd_lists_supported says beforehand what sug_interp3_cat_bwd_lists would refuse (host-side checks,
+    before any launch: safe without a GPU)."""
+    from sug_amd import _lib
+    L = _lib.lib()
+    assert L.sug_interp3_cat_bwd_lists_supported(2, 12288, 8) == 1
+    assert L.sug_interp3_cat_bwd_lists_supported(64, 1024, 64) == 1
+    assert L.sug_interp3_cat_bwd_lists_supported(2, 13637, 8) == 1       # (2*8 + 32 + 3N) * 4 <= 160 KB
+    assert L.sug_interp3_cat_bwd_lists_supported(2, 13638, 8) == 0
+    assert L.sug_interp3_cat_bwd_lists_supported(2, 16384, 8) == 0
+    assert L.sug_interp3_cat_bwd_lists_supported(0, 64, 8) == 0 and L.sug_interp3_cat_bwd_lists_supported(2, 64, 2) == 0
+    p = ctypes.c_void_p(16)
+    rc = L.sug_interp3_cat_bwd_lists(p, 12, 4, p, p, p, p, p, 2, 16384, 8, 8, p, p, p, p, p, None)
+    assert rc == -1 and b'too many for the LDS-resident build' in L.sug_last_error()
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from sug_amd import ops
