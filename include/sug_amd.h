@@ -812,6 +812,37 @@ int sug_mcd_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const
 int sug_mcd_loss_bwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
                      const int64_t* label_t, int Ms, int Mt, int C, float a_s, float a_t, const float* g, const float* lse,
                      float* ds1, float* ds2, float* dt1, float* dt2, void* stream);
+/* The classification loss of the shipped configurations (CLS_LOSS: ClassWeighting / FocalLoss, TARGET_LOSS, ADV_WEIGHT:
+ * train_dg_single_gpu.py:163-180, :269-292; train_dg_naive_mmd.py:156-165, :225-241) in one launch: sug_mcd_loss_fwd generalised.
+ * Logits and labels as sug_mcd_loss_fwd takes them (four blocks with ONE row stride ld >= C).  Per row
+ *   L(z, y) = alpha[y] * m(q) * (-log p_y),  p = softmax(z),  q = 1 - p_y,  m(q) = 1 if gamma == 0, else q^gamma
+ * (model_utils.focal_loss.forward); alpha: device fp32 [>= C], null = all ones.  With R = the mean over the rows, or their sum
+ * when reduce_sum != 0:
+ *   Ls = R(L(ys1, label)) + R(L(ys2, label)),  Lt = R(L(yt1, label_t)) + R(L(yt2, label_t)),
+ *   D  = mean over Mt*C of |softmax(yt1) - softmax(yt2)|,
+ *   out4 = { a_s*Ls + a_t*Lt - a_d*D, r_s*Ls, -a_d*D, a_t*Lt }.
+ * alpha == null and gamma == 0 is nn.CrossEntropyLoss: only then rows labelled ignore_index are skipped and left out of the mean,
+ * exactly as sug_ce_pair_fwd does; with alpha given, or gamma != 0, there is no ignore label.  Any other label outside [0, C)
+ * makes the loss and that row's gradient NaN.  a_t == 0 and a_d == 0: the target rows are not read (yt1, yt2 may be null) and their
+ * gradient is exact zeros; label_t may be null when a_t == 0.  save [2*(2*Ms + 2*Mt) + 2] floats, kept for the backward: the rows'
+ * max, then their sums of exp(z - max) (rows in the order ys1, ys2, yt1, yt2), then the divisors of R for source and target.
+ * totals (device double[4], may be null) += { (double)out4[1]*Ms, (double)out4[2]*Ms, Ms, Mt } in the same launch.
+ * Numerics: p = exp(z - max)/sum; q is the sum of the OTHER classes' probabilities (not 1 - p_y); log p_y = (z_y - max) - log(sum).
+ * 1 <= Ms, Mt <= 1024, 2 <= C <= 64, gamma == 0 or gamma >= 1 (for 0 < gamma < 1 the derivative is unbounded at p_y = 1): checked
+ * on the host before any launch (-1, sug_last_error()).  One workgroup, a wave per row; the rows' terms are summed in fp64 in one
+ * fixed order; no atomics, no memset node: capturable, bit-reproducible. */
+int sug_cls_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
+                     const int64_t* label_t, int Ms, int Mt, int C, const float* alpha, float gamma, int reduce_sum,
+                     int64_t ignore_index, float a_s, float a_t, float a_d, float r_s, float* out4, float* save, double* totals,
+                     void* stream);
+/* Its gradient for the upstream scalar g[0], four dense blocks ds1, ds2 [Ms, C] and dt1, dt2 [Mt, C].  A source row, with
+ * f = g*a_s/Ms (g*a_s for the sum):  dz_j = f * alpha_y * [m(q) - gamma*q^(gamma-1)*p_y*log p_y] * (p_j - delta_jy), p_y - 1 taken as
+ * -q; the second term is absent for gamma == 0.  A target row: the same with a_t and Mt, plus the discrepancy gradient of
+ * sug_mcd_loss_bwd scaled by a_d. */
+int sug_cls_loss_bwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
+                     const int64_t* label_t, int Ms, int Mt, int C, const float* alpha, float gamma, int reduce_sum,
+                     int64_t ignore_index, float a_s, float a_t, float a_d, float r_s, const float* g, const float* save,
+                     float* ds1, float* ds2, float* dt1, float* dt2, void* stream);
 /* out3 = { loss_cls + wg*v_geo + ws*(v_sem1 + v_sem2), wg*v_geo, ws*(v_sem1 + v_sem2) } (train_dg_single_gpu.py:314-324; the
  * weights MMD_WEIGHT * GEO_SCALE and 0.5 * MMD_WEIGHT * SEM_SCALE folded by the caller); null v_* = term absent.
  * Backward: out4 = g[0] * {1, wg, ws, ws}. */

@@ -140,6 +140,10 @@ SIGNATURES = {
     'sug_ce_bwd': [_vp, _i64, _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _vp],
     'sug_mcd_loss_fwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp],
     'sug_mcd_loss_bwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'sug_cls_loss_fwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _f32, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp,
+                         _vp, _vp],
+    'sug_cls_loss_bwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _f32, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp,
+                         _vp, _vp, _vp, _vp, _vp],
     'sug_loss_combine_fwd': [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp],
     'sug_loss_combine_bwd': [_vp, _f32, _f32, _vp, _vp],
     'sug_eval_accumulate': [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _i32, _vp, _i32, _vp],

@@ -282,6 +282,207 @@ __global__ __launch_bounds__(256) void mcd_loss_bwd_kernel(const float* __restri
     dt2[(int64_t)r * C + lane] = v2;
   }
 }
+// ---- classification loss of the shipped configurations (train_dg_single_gpu.py:163-180, :269-292; train_dg_naive_mmd.py:156-165,
+// :225-241): focal / class-weighted loss of both heads on source and target rows and the heads' discrepancy ---------------------
+//   L(z, y) = alpha[y] * m(q) * (-log p_y),  p = softmax(z),  q = 1 - p_y,  m(q) = 1 (gamma == 0) or q^gamma
+//   loss = a_s * (R(L(ys1)) + R(L(ys2))) + a_t * (R(L(yt1)) + R(L(yt2))) - a_d * mean |softmax(yt1) - softmax(yt2)|
+// (R: mean over the rows, or their sum) in one launch each way.  The shape of mcd_loss_fwd_kernel: one workgroup, a WAVE per row,
+// a LANE per class; the rows' terms meet in LDS, wave 0 folds them in fp64 in one fixed order, thread 0 writes the four scalars and
+// keeps the books.  Numerics: p = exp(z - max) / sum; q is the SUM OF THE OTHER classes' probabilities (1 - p_y cancels once
+// p_y rounds to 1, which is the normal state of a trained row); log p_y = (z_y - max) - log(sum).  alpha == null: alpha = 1, and
+// with gamma == 0 that is nn.CrossEntropyLoss, ignore_index honoured as ce_pair_fwd_kernel does (`ign`).
+struct ClsRow {
+  float mx, sum, e, q, logp;       // row max, sum of exp(z - max), this lane's exp(z - max), 1 - p_y, log p_y
+};
+
+__device__ __forceinline__ ClsRow cls_row(float z, bool in, int lane, int yi) {
+  ClsRow r;
+  r.mx = wave_max_f(z);
+  r.e = in ? expf(z - r.mx) : 0.f;
+  r.sum = wave_sum_f(r.e);
+  r.q = wave_sum_f(lane != yi ? r.e : 0.f) / r.sum;
+  r.logp = (__shfl(z, yi) - r.mx) - logf(r.sum);
+  return r;
+}
+__device__ __forceinline__ ClsRow cls_row_saved(float z, bool in, int lane, int yi, float mx, float sum) {
+  ClsRow r;
+  r.mx = mx;
+  r.sum = sum;
+  r.e = in ? expf(z - mx) : 0.f;
+  r.q = wave_sum_f(lane != yi ? r.e : 0.f) / sum;
+  r.logp = (__shfl(z, yi) - mx) - logf(sum);
+  return r;
+}
+__device__ __forceinline__ float cls_term(const ClsRow& r, float gamma) {
+  return (gamma == 0.f ? 1.f : powf(r.q, gamma)) * (-r.logp);
+}
+// d L / d z_j over alpha_y: [m(q) - gamma q^(gamma-1) p_y log p_y] * (p_j - delta_jy), with p_y - 1 = -q; the second term is
+// dropped for gamma == 0 (torch's pow backward returns zero for exponent 0)
+__device__ __forceinline__ float cls_grad(const ClsRow& r, float gamma, int lane, int yi) {
+  float c = 1.f;
+  if (gamma != 0.f) c = powf(r.q, gamma - 1.f) * (r.q - gamma * (__shfl(r.e, yi) / r.sum) * r.logp);
+  return c * (lane == yi ? -r.q : r.e / r.sum);
+}
+
+// save: [2R] floats for the R = 2*Ms + 2*Mt rows in the order ys1, ys2, yt1, yt2 -- the rows' max, then their sums -- and the two
+// divisors of the reduction (source, target) behind them.
+__global__ __launch_bounds__(1024) void cls_loss_fwd_kernel(const float* __restrict__ ys1, const float* __restrict__ ys2,
+                                                            const float* __restrict__ yt1, const float* __restrict__ yt2, int64_t ld,
+                                                            const int64_t* __restrict__ label, const int64_t* __restrict__ label_t,
+                                                            int Ms, int Mt, int C, const float* __restrict__ alpha, float gamma,
+                                                            int reduce_sum, int ign, int64_t ignore_index, float a_s, float a_t,
+                                                            float a_d, float r_s, float* __restrict__ out, float* __restrict__ save,
+                                                            double* __restrict__ totals) {
+  __shared__ float s_ls[MCD_MAXROWS], s_lt[MCD_MAXROWS], s_dis[MCD_MAXROWS];
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nwave = blockDim.x / WAVE;
+  const bool in = lane < C;
+  const int R = 2 * Ms + 2 * Mt;
+  const bool target = a_t != 0.f || a_d != 0.f;
+  for (int r = wave; r < Ms; r += nwave) {                // source rows (wave-uniform trips)
+    const int64_t y = label[r];
+    const bool skip = ign && y == ignore_index, bad = !skip && (y < 0 || y >= C);
+    const int yi = (skip || bad) ? 0 : (int)y;
+    const ClsRow r1 = cls_row(in ? ys1[(int64_t)r * ld + lane] : -INFINITY, in, lane, yi);
+    const ClsRow r2 = cls_row(in ? ys2[(int64_t)r * ld + lane] : -INFINITY, in, lane, yi);
+    if (lane == 0) {
+      save[r] = r1.mx;
+      save[Ms + r] = r2.mx;
+      save[R + r] = r1.sum;
+      save[R + Ms + r] = r2.sum;
+      float t = 0.f;
+      if (!skip) t = bad ? NAN : (alpha ? alpha[yi] : 1.f) * (cls_term(r1, gamma) + cls_term(r2, gamma));
+      s_ls[r] = t;
+    }
+  }
+  for (int r = wave; r < Mt && target; r += nwave) {      // target rows: the discrepancy, and the loss when a_t != 0
+    const int64_t y = a_t != 0.f ? label_t[r] : 0;
+    const bool skip = a_t == 0.f || (ign && y == ignore_index), bad = !skip && (y < 0 || y >= C);
+    const int yi = (skip || bad) ? 0 : (int)y;
+    const ClsRow r1 = cls_row(in ? yt1[(int64_t)r * ld + lane] : -INFINITY, in, lane, yi);
+    const ClsRow r2 = cls_row(in ? yt2[(int64_t)r * ld + lane] : -INFINITY, in, lane, yi);
+    const float d = wave_sum_f(in ? fabsf(r1.e / r1.sum - r2.e / r2.sum) : 0.f);
+    if (lane == 0) {
+      save[2 * Ms + r] = r1.mx;
+      save[2 * Ms + Mt + r] = r2.mx;
+      save[R + 2 * Ms + r] = r1.sum;
+      save[R + 2 * Ms + Mt + r] = r2.sum;
+      s_dis[r] = d;
+      float t = 0.f;
+      if (!skip) t = bad ? NAN : (alpha ? alpha[yi] : 1.f) * (cls_term(r1, gamma) + cls_term(r2, gamma));
+      s_lt[r] = t;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    double a = 0.0, b = 0.0, d = 0.0;
+    int cs = 0, ct = 0;
+    for (int i = lane; i < Ms; i += WAVE) {
+      a += (double)s_ls[i];
+      cs += !(ign && label[i] == ignore_index);
+    }
+    for (int i = lane; i < Mt && target; i += WAVE) {
+      b += (double)s_lt[i];
+      d += (double)s_dis[i];
+      ct += !(ign && a_t != 0.f && label_t[i] == ignore_index);
+    }
+    a = wave_sum_d(a);
+    b = wave_sum_d(b);
+    d = wave_sum_d(d);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      cs += __shfl_xor(cs, o);
+      ct += __shfl_xor(ct, o);
+    }
+    if (lane == 0) {
+      const float ds = reduce_sum ? 1.f : (float)cs, dt = reduce_sum ? 1.f : (float)ct;   // no row counts -> 0 / 0 = NaN, as torch
+      save[2 * R] = ds;
+      save[2 * R + 1] = dt;
+      const float Ls = (float)(a / (double)ds);
+      const float lt = a_t != 0.f ? a_t * (float)(b / (double)dt) : 0.f;
+      const float adv = a_d != 0.f ? -(a_d * (float)(d / ((double)Mt * (double)C))) : 0.f;
+      float loss = a_s * Ls;
+      if (a_t != 0.f) loss += lt;
+      if (a_d != 0.f) loss += adv;
+      const float ls = r_s * Ls;
+      out[0] = loss; out[1] = ls; out[2] = adv; out[3] = lt;
+      if (totals) {                                       // train_uda.py:180-184
+        totals[0] += (double)ls * (double)Ms;
+        totals[1] += (double)adv * (double)Ms;
+        totals[2] += (double)Ms;
+        totals[3] += (double)Mt;
+      }
+    }
+  }
+}
+
+// A wave per row of the Ms + Mt rows (source rows first), a lane per class; the four gradient blocks are dense [rows, C].
+__global__ __launch_bounds__(256) void cls_loss_bwd_kernel(const float* __restrict__ ys1, const float* __restrict__ ys2,
+                                                           const float* __restrict__ yt1, const float* __restrict__ yt2, int64_t ld,
+                                                           const int64_t* __restrict__ label, const int64_t* __restrict__ label_t,
+                                                           int Ms, int Mt, int C, const float* __restrict__ alpha, float gamma,
+                                                           int ign, int64_t ignore_index, float a_s, float a_t, float a_d,
+                                                           const float* __restrict__ g, const float* __restrict__ save,
+                                                           float* __restrict__ ds1, float* __restrict__ ds2, float* __restrict__ dt1,
+                                                           float* __restrict__ dt2) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int row = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;    // wave-uniform
+  if (row >= Ms + Mt) return;
+  const bool in = lane < C;
+  const int R = 2 * Ms + 2 * Mt;
+  const float gv = g[0];
+  if (row < Ms) {
+    const int64_t y = label[row];
+    const bool skip = ign && y == ignore_index, bad = !skip && (y < 0 || y >= C);
+    const int yi = (skip || bad) ? 0 : (int)y;
+    const int64_t o = (int64_t)row * ld + lane;
+    const ClsRow r1 = cls_row_saved(in ? ys1[o] : -INFINITY, in, lane, yi, save[row], save[R + row]);
+    const ClsRow r2 = cls_row_saved(in ? ys2[o] : -INFINITY, in, lane, yi, save[Ms + row], save[R + Ms + row]);
+    const float f = gv * a_s / save[2 * R] * (alpha ? alpha[yi] : 1.f);
+    float v1 = f * cls_grad(r1, gamma, lane, yi), v2 = f * cls_grad(r2, gamma, lane, yi);
+    if (skip) v1 = v2 = 0.f;
+    if (bad) v1 = v2 = NAN;
+    if (in) {
+      ds1[(int64_t)row * C + lane] = v1;
+      ds2[(int64_t)row * C + lane] = v2;
+    }
+    return;
+  }
+  const int r = row - Ms;
+  if (a_t == 0.f && a_d == 0.f) {                         // the target rows were not read: exact zeros
+    if (in) dt1[(int64_t)r * C + lane] = dt2[(int64_t)r * C + lane] = 0.f;
+    return;
+  }
+  const int64_t y = a_t != 0.f ? label_t[r] : 0;
+  const bool skip = a_t == 0.f || (ign && y == ignore_index), bad = !skip && (y < 0 || y >= C);
+  const int yi = (skip || bad) ? 0 : (int)y;
+  const int64_t o = (int64_t)r * ld + lane;
+  const ClsRow r1 = cls_row_saved(in ? yt1[o] : -INFINITY, in, lane, yi, save[2 * Ms + r], save[R + 2 * Ms + r]);
+  const ClsRow r2 = cls_row_saved(in ? yt2[o] : -INFINITY, in, lane, yi, save[2 * Ms + Mt + r], save[R + 2 * Ms + Mt + r]);
+  float v1 = 0.f, v2 = 0.f;
+  if (a_d != 0.f) {                                       // mcd_loss_bwd_kernel's form, scaled by a_d
+    const float p1 = r1.e / r1.sum, p2 = r2.e / r2.sum;
+    const float df = p1 - p2;
+    const float s = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);               // sign(0) = 0, as the backward of torch.abs
+    // s_j - <s,p> written as sum_c p_c (s_j - s_c): with P+ / P0 / P- the probability mass of the classes with s = +1 / 0 / -1,
+    // s_j = +1 -> P0 + 2 P-,  s_j = -1 -> -(P0 + 2 P+),  s_j = 0 -> P- - P+ (no cancellation for a class of probability ~ 1)
+    const float up1 = wave_sum_f(s > 0.f ? p1 : 0.f), eq1 = wave_sum_f(s == 0.f ? p1 : 0.f), dn1 = wave_sum_f(s < 0.f ? p1 : 0.f);
+    const float up2 = wave_sum_f(s > 0.f ? p2 : 0.f), eq2 = wave_sum_f(s == 0.f ? p2 : 0.f), dn2 = wave_sum_f(s < 0.f ? p2 : 0.f);
+    const float t1 = s > 0.f ? eq1 + 2.f * dn1 : (s < 0.f ? -(eq1 + 2.f * up1) : dn1 - up1);
+    const float t2 = s > 0.f ? eq2 + 2.f * dn2 : (s < 0.f ? -(eq2 + 2.f * up2) : dn2 - up2);
+    const float k = gv * a_d / ((float)Mt * (float)C);
+    v1 = -k * (p1 * t1);
+    v2 = k * (p2 * t2);
+  }
+  if (!skip) {
+    const float f = gv * a_t / save[2 * R + 1] * (alpha ? alpha[yi] : 1.f);
+    v1 = bad ? NAN : v1 + f * cls_grad(r1, gamma, lane, yi);
+    v2 = bad ? NAN : v2 + f * cls_grad(r2, gamma, lane, yi);
+  }
+  if (in) {
+    dt1[(int64_t)r * C + lane] = v1;
+    dt2[(int64_t)r * C + lane] = v2;
+  }
+}
 }  // namespace
 
 extern "C" int sug_ce_pair_fwd(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int M, int C,
@@ -362,6 +563,48 @@ extern "C" int sug_mcd_loss_bwd(const float* ys1, const float* ys2, const float*
   hipLaunchKernelGGL(mcd_loss_bwd_kernel, dim3((unsigned)sug_divup((int64_t)(Ms + Mt), 4)), dim3(256), 0, (hipStream_t)stream, ys1, ys2,
                      yt1, yt2, ld, label, label_t, Ms, Mt, C, a_s, a_t, g, lse, ds1, ds2, dt1, dt2);
   SUG_LAUNCH_CHECK("sug_mcd_loss_bwd");
+  return SUG_OK;
+}
+
+static int cls_check(const char* who, int Ms, int Mt, int C, int64_t ld, float gamma, float a_s, float a_t, float a_d) {
+  SUG_REQUIRE(Ms >= 1 && Ms <= MCD_MAXROWS && Mt >= 1 && Mt <= MCD_MAXROWS && C >= 2 && C <= CE1_MAXC && ld >= C,
+              "%s: unsupported shape Ms=%d, Mt=%d rows, C=%d classes, ld=%lld (1 <= Ms, Mt <= %d, 2 <= C <= %d, ld >= C)", who, Ms, Mt,
+              C, (long long)ld, MCD_MAXROWS, CE1_MAXC);
+  SUG_REQUIRE(gamma == 0.f || (gamma >= 1.f && gamma < INFINITY),
+              "%s: gamma=%g (0, or >= 1: for 0 < gamma < 1 the derivative is unbounded at p_y = 1)", who, (double)gamma);
+  SUG_REQUIRE(a_s == a_s && a_t == a_t && a_d == a_d, "%s: a coefficient is NaN", who);
+  return SUG_OK;
+}
+
+extern "C" int sug_cls_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld,
+                                const int64_t* label, const int64_t* label_t, int Ms, int Mt, int C, const float* alpha, float gamma,
+                                int reduce_sum, int64_t ignore_index, float a_s, float a_t, float a_d, float r_s, float* out4,
+                                float* save, double* totals, void* stream) {
+  SUG_REQUIRE(ys1 && ys2 && label && out4 && save && ((yt1 && yt2) || (a_t == 0.f && a_d == 0.f)) && (label_t || a_t == 0.f),
+              "sug_cls_loss_fwd: null pointer");
+  if (cls_check("sug_cls_loss_fwd", Ms, Mt, C, ld, gamma, a_s, a_t, a_d) != SUG_OK) return SUG_ERR_ARG;
+  const int rows = Ms > Mt ? Ms : Mt, waves = rows < 16 ? rows : 16;
+  const int ign = !alpha && gamma == 0.f;                 // nn.CrossEntropyLoss: the one case with an ignore label
+  hipLaunchKernelGGL(cls_loss_fwd_kernel, dim3(1), dim3(WAVE * waves), 0, (hipStream_t)stream, ys1, ys2, yt1, yt2, ld, label, label_t,
+                     Ms, Mt, C, alpha, gamma, reduce_sum != 0, ign, ignore_index, a_s, a_t, a_d, r_s, out4, save, totals);
+  SUG_LAUNCH_CHECK("sug_cls_loss_fwd");
+  return SUG_OK;
+}
+
+extern "C" int sug_cls_loss_bwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld,
+                                const int64_t* label, const int64_t* label_t, int Ms, int Mt, int C, const float* alpha, float gamma,
+                                int reduce_sum, int64_t ignore_index, float a_s, float a_t, float a_d, float r_s, const float* g,
+                                const float* save, float* ds1, float* ds2, float* dt1, float* dt2, void* stream) {
+  (void)reduce_sum;                                       // (the divisors are in `save`)
+  (void)r_s;
+  SUG_REQUIRE(ys1 && ys2 && label && g && save && ds1 && ds2 && dt1 && dt2 && ((yt1 && yt2) || (a_t == 0.f && a_d == 0.f)) &&
+              (label_t || a_t == 0.f), "sug_cls_loss_bwd: null pointer");
+  if (cls_check("sug_cls_loss_bwd", Ms, Mt, C, ld, gamma, a_s, a_t, a_d) != SUG_OK) return SUG_ERR_ARG;
+  const int ign = !alpha && gamma == 0.f;
+  hipLaunchKernelGGL(cls_loss_bwd_kernel, dim3((unsigned)sug_divup((int64_t)(Ms + Mt), 4)), dim3(256), 0, (hipStream_t)stream, ys1, ys2,
+                     yt1, yt2, ld, label, label_t, Ms, Mt, C, alpha, gamma, ign, ignore_index, a_s, a_t, a_d, g, save, ds1, ds2, dt1,
+                     dt2);
+  SUG_LAUNCH_CHECK("sug_cls_loss_bwd");
   return SUG_OK;
 }
 

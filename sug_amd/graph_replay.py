@@ -153,6 +153,70 @@ def plain_ce(criterion, smoothing_ok=False):
         (smoothing_ok or c.label_smoothing == 0.0)
 
 
+FusedCriterion = collections.namedtuple('FusedCriterion', 'kind alpha gamma reduction ignore_index')
+
+
+def fused_criterion(criterion, C):
+    """None, or what ops.cls_loss needs to compute `criterion` on C classes, by value: (kind, alpha as a host tuple | None, gamma,
+    reduction, ignore_index).  Recognised: a plain nn.CrossEntropyLoss (kind 'ce') and an object whose type is exactly
+    model_utils.focal_loss (kind 'focal': CLS_LOSS FocalLoss, and ClassWeighting = gamma 0) with a 1-D alpha of at least C
+    entries, on either device, and gamma == 0 or gamma >= 1.  Reading a device alpha waits for the device: the steps ask through a
+    CriterionState, which reads it again only when the tensor was replaced or written to."""
+    from .model.model_utils import focal_loss
+    c = criterion
+    if plain_ce(c):
+        return FusedCriterion('ce', None, 0.0, 'mean', int(c.ignore_index))
+    if type(c) is not focal_loss:
+        return None
+    a, gamma = getattr(c, 'alpha', None), getattr(c, 'gamma', None)
+    if not isinstance(a, torch.Tensor) or a.dim() != 1 or a.numel() < C or not a.is_floating_point():
+        return None
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not (gamma == 0 or 1 <= gamma < float('inf')):
+        return None
+    alpha = tuple(a.detach().to(dtype=torch.float32).tolist())
+    return FusedCriterion('focal', alpha, float(gamma), 'mean' if c.size_average else 'sum', -100)
+
+
+class CriterionState:
+    """A step's view of its criterion: the FusedCriterion record of the criterion as it is NOW (a host compare per step: the alpha
+    tensor's identity and version, gamma, size_average; the record is formed again when one of them changed) and, per record, a
+    device copy of alpha that belongs to the step.  A record is part of the step's graph key, and a captured step holds the raw
+    pointer of its record's copy: the copies are kept least recently used first out, `limit` >= the number of captured steps
+    kept and every step touches its record, so a copy outlives every graph captured with it."""
+
+    def __init__(self, limit=4):
+        self.limit = int(limit)
+        self._seen = self._record = None
+        self._dev = LRU(self.limit)
+
+    def record(self, criterion, limit=None):
+        c = criterion
+        if type(c) is nn.CrossEntropyLoss:                  # (no failing attribute look-ups on a Module: this runs every step)
+            a, seen = None, (c, c.ignore_index, c.weight is None, c.reduction, c.label_smoothing)
+        else:
+            a = getattr(c, 'alpha', None)
+            seen = (c, type(c), getattr(a, '_version', None), getattr(c, 'gamma', None), getattr(c, 'size_average', None))
+        if self._seen is None or self._seen[1] is not a or self._seen[0] != seen:
+            self._seen, self._record = (seen, a), fused_criterion(c, 0)
+        if limit is not None:
+            self._dev.limit = self.limit = max(int(limit), 1)
+        if self._record is not None and self._record in self._dev:
+            self._dev.move_to_end(self._record)
+        return self._record
+
+    def alpha_on(self, record, device):
+        """The device copy of record.alpha (None for a record without).  A new record is uploaded here, which is why the first
+        step of a graph key -- the key holds the record -- runs outside any capture."""
+        if record is None or record.alpha is None:
+            return None
+        t = self._dev.get(record)
+        if t is None or t.device != device:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('CriterionState: alpha of a new criterion record must be uploaded outside a capture')
+            t = self._dev.put(record, torch.tensor(record.alpha, dtype=torch.float32, device=device))
+        return t
+
+
 def _release(st):
     st['graph'] = st['in'] = st['out'] = None
     ops.clear_rows_cache()      # may hold a tensor of the freed pool

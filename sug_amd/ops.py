@@ -2434,6 +2434,119 @@ def mcd_loss(ys1, ys2, yt1, yt2, label, label_t=None, a_s=1.0, a_t=0.0, r_s=1.0,
     return _MCDLoss.apply(ys1, ys2, yt1, yt2, label, label_t, a_s, a_t, r_s, totals)
 
 
+def _cls_gamma_ok(gamma):
+    return gamma == 0 or 1 <= gamma < float('inf')
+
+
+class _ClsLoss(torch.autograd.Function):
+    """The classification loss of the shipped configurations -- focal / class-weighted loss of both heads on source and target
+    rows and the heads' discrepancy -- in one launch each way (sug_cls_loss_fwd / sug_cls_loss_bwd); the forward's launch also
+    advances the caller's `totals`.  yt1 is None: ys1, ys2 are the PAIRED logits [Ms + Mt, C], source rows first (Ms = the number
+    of labels), and the backward writes the pair's dense gradient."""
+
+    @staticmethod
+    def forward(ctx, ys1, ys2, yt1, yt2, label, label_t, alpha, gamma, reduction, ignore_index, a_s, a_t, a_d, r_s, totals):
+        _need_gpu(ys1, ys2, yt1, yt2, label, label_t, alpha, totals)
+        paired = yt1 is None
+        Ms, C = label.numel(), ys1.shape[1]
+        Mt = ys1.shape[0] - Ms if paired else yt1.shape[0]
+        ts = [ys1, ys2] if paired else [ys1, ys2, yt1, yt2]
+        if any(t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != C for t in ts) or ys1.shape != ys2.shape or \
+                (not paired and (yt1.shape != yt2.shape or ys1.shape[0] != Ms)) or Mt < 1:
+            raise RuntimeError('ops.cls_loss: fp32 logits [Ms, C] x 2 and [Mt, C] x 2 (or two paired [Ms + Mt, C]) and Ms labels '
+                               '(got %s, %d labels)' % ([tuple(t.shape) for t in ts], Ms))
+        if a_t != 0 and (label_t is None or label_t.numel() != Mt):
+            raise RuntimeError('ops.cls_loss: a_t != 0 needs Mt = %d target labels' % Mt)
+        if alpha is not None and (alpha.dim() != 1 or alpha.dtype != torch.float32 or alpha.numel() < C or not alpha.is_contiguous()):
+            raise RuntimeError('ops.cls_loss: alpha is a contiguous fp32 tensor of at least C = %d entries' % C)
+        if reduction not in ('mean', 'sum'):
+            raise RuntimeError("ops.cls_loss: reduction is 'mean' or 'sum' (got %r)" % (reduction,))
+        if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 4 or not totals.is_contiguous()):
+            raise RuntimeError('ops.cls_loss: totals is a contiguous float64 tensor of 4 elements')
+        ld = ts[0].stride(0)
+        if any(t.stride(1) != 1 or t.stride(0) != ld for t in ts) or ld < C:      # one leading dimension for the four blocks
+            ts = [t.contiguous() for t in ts]
+            ld = C
+        if paired:
+            ts = [ts[0], ts[1], ts[0][Ms:], ts[1][Ms:]]
+        lab = label.reshape(-1).long().contiguous()
+        lab_t = label_t.reshape(-1).long().contiguous() if (a_t != 0 and label_t is not None) else None
+        out = torch.empty(4, dtype=torch.float32, device=ys1.device)
+        save = torch.empty(4 * (Ms + Mt) + 2, dtype=torch.float32, device=ys1.device)
+        rs = int(reduction == 'sum')
+        check(lib().sug_cls_loss_fwd(_p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), ld, _p(lab), _p(lab_t), Ms, Mt, C, _p(alpha),
+                                     float(gamma), rs, int(ignore_index), float(a_s), float(a_t), float(a_d), float(r_s), _p(out),
+                                     _p(save), _p(totals), _st()), 'sug_cls_loss_fwd')
+        opt = [t for t in (lab_t, alpha) if t is not None]
+        ctx.save_for_backward(lab, save, *opt, *ts)
+        ctx.meta = (Ms, Mt, C, ld, float(gamma), rs, int(ignore_index), float(a_s), float(a_t), float(a_d), float(r_s), paired,
+                    lab_t is not None, alpha is not None)
+        loss, ls, adv, lt = out[0], out[1], out[2], out[3]
+        ctx.mark_non_differentiable(ls, adv, lt)
+        ctx.set_materialize_grads(False)          # no zero-filled scalars for the three reporting outputs (a launch each)
+        return loss, ls, adv, lt
+
+    @staticmethod
+    def backward(ctx, g, _g1, _g2, _g3):
+        Ms, Mt, C, ld, gamma, rs, ign, a_s, a_t, a_d, r_s, paired, has_t, has_a = ctx.meta
+        if g is None:
+            return (None,) * 15
+        sv = list(ctx.saved_tensors)
+        lab, save = sv[0], sv[1]
+        k = 2
+        lab_t = alpha = None
+        if has_t:
+            lab_t, k = sv[k], k + 1
+        if has_a:
+            alpha, k = sv[k], k + 1
+        ts = sv[k:]
+        gs = g.detach().to(dtype=torch.float32).reshape(1)
+        d = torch.empty(2, Ms + Mt, C, dtype=torch.float32, device=save.device)
+        check(lib().sug_cls_loss_bwd(_p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), ld, _p(lab), _p(lab_t), Ms, Mt, C, _p(alpha), gamma,
+                                     rs, ign, a_s, a_t, a_d, r_s, _p(gs), _p(save), _p(d[0]), _p(d[1]), _p(d[0, Ms:]), _p(d[1, Ms:]),
+                                     _st()), 'sug_cls_loss_bwd')
+        if paired:
+            return (d[0], d[1]) + (None,) * 13
+        return (d[0, :Ms], d[1, :Ms], d[0, Ms:], d[1, Ms:]) + (None,) * 11
+
+
+def cls_loss_supported(ys1, ys2, yt1=None, yt2=None, label=None, label_t=None, alpha=None, gamma=0.0, reduction='mean', a_t=0.0):
+    """Can sug_cls_loss_* take this?  (fp32 logits, C <= 64, at most 1024 rows per domain, gamma == 0 or >= 1, alpha a device fp32
+    vector of at least C entries, Mt target labels when a_t != 0.)  False is not an error: the caller composes the ops."""
+    ts = [t for t in (ys1, ys2, yt1, yt2) if t is not None]
+    if len(ts) not in (2, 4) or any(not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 for t in ts):
+        return False
+    C = ys1.shape[1]
+    if any(t.shape[1] != C for t in ts) or not 2 <= C <= MCD_MAX_CLASSES or ys1.shape != ys2.shape:
+        return False
+    if not _cls_gamma_ok(gamma) or reduction not in ('mean', 'sum'):
+        return False
+    if alpha is not None and not (alpha.is_cuda and alpha.dtype == torch.float32 and alpha.dim() == 1 and alpha.numel() >= C
+                                  and alpha.is_contiguous()):
+        return False
+    if yt1 is None:
+        if label is None:
+            return False
+        Ms, Mt = label.numel(), ys1.shape[0] - label.numel()
+    else:
+        Ms, Mt = ys1.shape[0], yt1.shape[0]
+        if yt1.shape != yt2.shape or (label is not None and label.numel() != Ms):
+            return False
+    return 1 <= Ms <= MCD_MAX_ROWS and 1 <= Mt <= MCD_MAX_ROWS and (a_t == 0 or (label_t is not None and label_t.numel() == Mt))
+
+
+def cls_loss(ys1, ys2, yt1, yt2, label, label_t=None, alpha=None, gamma=0.0, reduction='mean', ignore_index=-100, a_s=1.0, a_t=0.0,
+             a_d=0.0, r_s=1.0, totals=None):
+    """a_s*Ls + a_t*Lt - a_d*D in one launch each way -> (loss, r_s*Ls, -a_d*D, a_t*Lt), 0-d; only `loss` is differentiable.
+    Ls = R(L(ys1, label)) + R(L(ys2, label)), Lt the same on yt1, yt2 against label_t, L = alpha[y] * (1 - p_y)^gamma * (-log p_y)
+    (model_utils.focal_loss; alpha None = ones; gamma 0 or >= 1), R = `reduction` over the rows ('mean' or 'sum'),
+    D = mean|softmax(yt1) - softmax(yt2)|.  alpha None and gamma 0 is nn.CrossEntropyLoss with its `ignore_index`; otherwise there
+    is no ignore label.  Any other label outside [0, C) -> NaN.  yt1 = yt2 = None: ys1, ys2 are the paired [Ms + Mt, C] logits of
+    Net_MDA.forward_pair(paired_out=True), Ms = len(label).  a_t = a_d = 0: the target rows are not read and get zero gradient.
+    totals: None or a device float64 [4], advanced by (r_s*Ls*Ms, -a_d*D*Ms, Ms, Mt) in the same launch."""
+    return _ClsLoss.apply(ys1, ys2, yt1, yt2, label, label_t, alpha, gamma, reduction, ignore_index, a_s, a_t, a_d, r_s, totals)
+
+
 # ----------------------------------------------------------------------------- evaluation metrics (sug_eval_accumulate)
 EVAL_MAX_ROWS, EVAL_MAX_CLASSES = 4096, 64              # SUG_EVAL_MAX_ROWS, SUG_EVAL_MAX_CLASSES
 EVAL_BATCH_COUNT, EVAL_DATA_TOTAL, EVAL_CORRECT_TOTAL, EVAL_ERROR, EVAL_LOSS_TOTAL = 0, 1, 2, 3, 4

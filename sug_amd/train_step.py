@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .graph_replay import LRU, StartFeeder, adam_choice, drop_weight_caches, hyper_key, plain_ce, plan_generations
+from .graph_replay import LRU, CriterionState, StartFeeder, adam_choice, drop_weight_caches, hyper_key, plain_ce, plan_generations
 from .model import mmd
 
 GEO_MMD = {'NAME': 'SOFT_MMD', 'LABEL_SCALE': 50, 'GEO_SCALE': 1}
@@ -210,6 +210,19 @@ def _params_above_encoder(model):
     return [p for m in (model.c1, model.c2, model.attention_s, model.attention_t) for p in m.parameters()]
 
 
+def cls_loss_coefficients(methods):
+    """(a_s, a_t, a_d) with which a_s*Ls + a_t*Lt - a_d*D (Ls, Lt: the criterion of both heads summed, on source and target
+    rows; D: the heads' discrepancy) is the composed classification loss of SUGStep.losses (train_dg_single_gpu.py:269-292):
+        TARGET_LOSS > 0:  CLS_WEIGHT * 0.5 * ((0.5*Ls - ADV_WEIGHT*D) + 0.5*Lt)
+        otherwise:        CLS_WEIGHT * SRC_LOSS_WEIGHT * (0.5*Ls - ADV_WEIGHT*D)
+    (ADV_WEIGHT <= 0: no discrepancy term)."""
+    M = methods
+    adv = M['ADV_WEIGHT'] if M['ADV_WEIGHT'] > 0 else 0.0
+    if M['TARGET_LOSS'] > 0:
+        return 0.25 * M['CLS_WEIGHT'], 0.25 * M['CLS_WEIGHT'], 0.5 * M['CLS_WEIGHT'] * adv
+    return 0.5 * M['CLS_WEIGHT'] * M['SRC_LOSS_WEIGHT'], 0.0, M['CLS_WEIGHT'] * M['SRC_LOSS_WEIGHT'] * adv
+
+
 class SUGStep:
     def __init__(self, model, lr=1e-3, weight_decay=5e-5, lr_scaler=1.0, methods=None, criterion=None,
                  global_mmd=True, fused_adam=None, share_prefix=True, use_graph=False, pair_domains=True,
@@ -258,6 +271,8 @@ class SUGStep:
         self._total = None
         self._w16_plan = None                           # ops.w16_scope's slot: the 16-bit weight copies of the last step
         self._combine_tail = os.environ.get('SUG_FUSED_LOSS', '1') != '0'
+        self._crit = CriterionState()                   # the criterion by value, and the step's device copy of its alpha
+        self.loss_form = None                           # the classification tail of the last losses(): 'ce_pair' | 'cls_loss' | 'composed'
         self._mmd_multi = os.environ.get('SUG_MMD_MULTI', '1') != '0'   # the step's MMD terms stage by stage in one launch
         self.max_graphs = 4                             # captured steps kept (each owns a private memory pool)
         # segmented steps: {collective name: [(event before, event after), ...]} when a dict is assigned (bench.py
@@ -354,11 +369,28 @@ class SUGStep:
                                               float(sem['LABEL_SCALE']), row0, w, self.world))
         return loss_geo, (0.5 * M_['MMD_WEIGHT'] * sem['SEM_SCALE']) * (terms[0] + terms[1])
 
+    def _cls_loss_tail(self, rec, ys1, ys2, yt1, yt2, label):
+        """The classification loss of the composed block in losses() as ops.cls_loss (one launch each way), or None where the
+        kernel does not take it.  yt1 = yt2 = None: ys1, ys2 are the paired logits.  With TARGET_LOSS > 0 the target rows are
+        scored against the SOURCE labels, as the reference does (train_dg_single_gpu.py:285-286)."""
+        if ys1.dim() != 2 or (rec.alpha is not None and len(rec.alpha) < ys1.shape[1]):
+            return None
+        a_s, a_t, a_d = cls_loss_coefficients(self.methods)
+        label_t = label if a_t != 0 else None
+        alpha = self._crit.alpha_on(rec, ys1.device) if ys1.is_cuda else None
+        if not ops.cls_loss_supported(ys1, ys2, yt1, yt2, label, label_t, alpha, rec.gamma, rec.reduction, a_t):
+            return None
+        return ops.cls_loss(ys1, ys2, yt1, yt2, label, label_t, alpha, rec.gamma, rec.reduction, rec.ignore_index, a_s, a_t, a_d)[0]
+
     def losses(self, data, label, data_t, label_t, mmd_on=True, combine=False):
         """(loss_cls, loss_geo, loss_sem), each differentiable.  combine=True (the step's own call): the total is formed in
         one launch each way and kept in self._total; the returned geo / sem parts are then values for reporting only."""
         M = self.methods
         ce_only = plain_ce(self.criterion) and M['ADV_WEIGHT'] <= 0 and M['TARGET_LOSS'] <= 0    # what ops.ce_pair computes
+        # any other recognised criterion / METHODS (the shipped configurations: focal or class-weighted loss, TARGET_LOSS,
+        # ADV_WEIGHT): ops.cls_loss
+        rec = None if ce_only else self._crit.record(self.criterion, self.max_graphs)
+        self.loss_form = 'composed'
         model = self.model
         pair = None
         fused_ce = None
@@ -369,16 +401,22 @@ class SUGStep:
             if mmd_on and M['MMD_WEIGHT'] > 0 and not dual and hasattr(model, 'plan_pair_geometry') \
                     and os.environ.get('SUG_PLAN_GEOMETRY', '1') != '0':
                 model.plan_pair_geometry(pair, passes=2)    # FPS / ball query of the semantic AND the node pass in one set of launches
-            if ce_only and os.environ.get('SUG_FUSED_LOSS', '1') != '0':
+            if (ce_only or rec is not None) and os.environ.get('SUG_FUSED_LOSS', '1') != '0':
                 # the paired logits / mid features stay paired: CE of both heads in one launch each way (ops.ce_pair writes the
                 # whole pair's gradient), the halves of the mid features split with a copy-free backward
                 if dual:
                     y1, y2, f1, f2, nodes = model.forward_pair(pair, paired_out=True, dual=True)
                 else:
                     y1, y2, f1, f2 = model.forward_pair(pair, paired_out=True)
-                if y1.dim() == 2 and ops.ce_pair_supported(y1, y2, label):
-                    Bs = label.shape[0]
+                if ce_only and y1.dim() == 2 and ops.ce_pair_supported(y1, y2, label):
                     fused_ce = ops.ce_pair(y1, y2, label, 0.5 * M['SRC_LOSS_WEIGHT'] * M['CLS_WEIGHT'], self.criterion.ignore_index)
+                    self.loss_form = 'ce_pair'
+                elif rec is not None:
+                    fused_ce = self._cls_loss_tail(rec, y1, y2, None, None, label)
+                    if fused_ce is not None:
+                        self.loss_form = 'cls_loss'
+                if fused_ce is not None:
+                    Bs = label.shape[0]
                     (sem_s1, sem_t1), (sem_s2, sem_t2) = ops.split_halves(f1), ops.split_halves(f2)
                     yd1, yd2 = y1.detach(), y2.detach()            # the SDA weights read the logits' values only
                     pred_s1, pred_t1, pred_s2, pred_t2 = yd1[:Bs], yd1[Bs:], yd2[:Bs], yd2[Bs:]
@@ -406,6 +444,11 @@ class SUGStep:
             # the separate-calls form (the four model(...) calls of an unchanged caller): CE of both heads in one launch each
             # way as well (ops.ce_pair scores the first len(label) rows: here all of them)
             fused_ce = ops.ce_pair(pred_s1, pred_s2, label, 0.5 * M['SRC_LOSS_WEIGHT'] * M['CLS_WEIGHT'], self.criterion.ignore_index)
+            self.loss_form = 'ce_pair'
+        elif fused_ce is None and pair is None and self._combine_tail and model.training and pred_s1.is_cuda and rec is not None:
+            fused_ce = self._cls_loss_tail(rec, pred_s1, pred_s2, pred_t1, pred_t2, label)      # the same for the other criteria
+            if fused_ce is not None:
+                self.loss_form = 'cls_loss'
         if fused_ce is not None:
             loss_cls = fused_ce
         elif M['ADV_WEIGHT'] > 0 or M['TARGET_LOSS'] > 0:
@@ -487,7 +530,9 @@ class SUGStep:
     def _graph_key(self, mmd_on, tensors):
         """Everything a captured step bakes in by value.  sug_amd.optim.Adam keeps lr on the device (one graph serves a
         whole schedule); any other optimizer takes lr by value, so its lr of every group is part of the key."""
-        return (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()))
+        c = self.criterion
+        crit = ('ce', int(c.ignore_index)) if plain_ce(c) else (self._crit.record(c, self.max_graphs) or ('call', id(c), repr(c)))
+        return (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()), crit)
 
     def _plan_generations(self):
         return plan_generations(self._opts() + (self._adam_chain,))

@@ -15,8 +15,10 @@ optimizer_dis; and the encoder's parameters keep separate Adam moments in optimi
 
 Launch forms, as SourceStep: the step is a graph_replay.ReplayedStep, planned, captured (ONE graph: both phases, all three
 updates, one stream) and replayed by that class's protocol.  With a plain nn.CrossEntropyLoss the scalar tail of phase 1 is
-ops.mcd_loss (one launch each way, which also keeps four of the five books); any other criterion, or fused_loss=False, composes
-it from torch ops and keeps the books by in-place adds.  Nothing waits for the device until `epoch_totals()`.
+ops.mcd_loss (one launch each way, which also keeps four of the five books), with a model_utils.focal_loss (CLS_LOSS FocalLoss /
+ClassWeighting of the shipped configurations) it is ops.cls_loss, which does the same; any other criterion, or fused_loss=False,
+composes it from torch ops and keeps the books by in-place adds (`loss_form` says which ran).  Nothing waits for the device
+until `epoch_totals()`.
 `use_graph=False` launches the same ops eagerly: the graph's bit-for-bit twin.
 
 What is shared "per step" elsewhere is per PHASE here, because the weights change in between: the 16-bit weight copies of the Point
@@ -30,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .graph_replay import ReplayedStep, adam_choice, drop_weight_caches, hyper_key, plain_ce
+from .graph_replay import CriterionState, ReplayedStep, adam_choice, drop_weight_caches, hyper_key, plain_ce
 from .model import mmd
 from .train_step import discrepancy
 
@@ -94,6 +96,8 @@ class UDAStep(ReplayedStep):
         # whose loss tail is composed are counted on the host (their number is known there)
         self._books = torch.zeros(5, dtype=torch.float64, device=self.device) if on_gpu else None
         self._w16_plans = [None, None]
+        self._crit = CriterionState(max_graphs)         # the criterion by value, and the step's device copy of its alpha
+        self.loss_form = None                           # phase 1's loss tail in the last step: 'mcd_loss' | 'cls_loss' | 'composed'
         self._split_layers = [m for m in model.modules() if hasattr(m, 'cache_weight_split')]
 
     def _opts(self):
@@ -149,7 +153,7 @@ class UDAStep(ReplayedStep):
         """Everything a captured step bakes in by value (`cons` is not: GradReverse is the identity)."""
         from .model import Ptran_transformer as PT
         c = self.criterion
-        crit = ('ce', int(c.ignore_index)) if plain_ce(c) else ('call', id(c), repr(c))
+        crit = ('ce', int(c.ignore_index)) if plain_ce(c) else (self._crit.record(c, self.max_graphs) or ('call', id(c), repr(c)))
         hyp = tuple(hyper_key(o) for o in self._opts())
         return (tuple(tuple(t.shape) for t in batch), self.recipe, self.a_s, self.a_t, self.r_s, self.src_weight, self.target_loss,
                 repr(sorted(self.class_mmd.items())), crit, self.model.training, self.fused_loss, self.pair_domains,
@@ -178,6 +182,19 @@ class UDAStep(ReplayedStep):
         """Nothing computed from the weights outlives the update that follows."""
         drop_weight_caches(self.model, self._split_layers, hasattr(self.model.g, 'clear_prefix_cache'))
 
+    def _cls_loss_tail(self, rec, ys1, ys2, yt1, yt2, label):
+        """Phase 1's loss for a recognised criterion other than the plain cross entropy as ops.cls_loss (a_d = 1: the
+        discrepancy enters as it is), books included; None where the kernel does not take it."""
+        if ys1.dim() != 2 or (rec.alpha is not None and len(rec.alpha) < ys1.shape[1]):
+            return None
+        label_t = label if self.a_t else None               # (the target rows are scored against the SOURCE labels)
+        alpha = self._crit.alpha_on(rec, ys1.device)
+        if not ops.cls_loss_supported(ys1, ys2, yt1, yt2, label, label_t, alpha, rec.gamma, rec.reduction, self.a_t):
+            return None
+        self.loss_form = 'cls_loss'
+        return ops.cls_loss(ys1, ys2, yt1, yt2, label, label_t, alpha, rec.gamma, rec.reduction, rec.ignore_index, self.a_s,
+                            self.a_t, 1.0, self.r_s, totals=self._books[:4])
+
     def _eager_step(self, data, label, data_t, label_t):
         model, B, Bt = self.model, data.shape[0], data_t.shape[0]
         pair = None
@@ -186,14 +203,19 @@ class UDAStep(ReplayedStep):
         with self._step_scope():
             # ---- phase 1 (train_uda.py:149-166)
             fused = self.fused_loss and plain_ce(self.criterion)
+            rec = self._crit.record(self.criterion, self.max_graphs) if (self.fused_loss and not fused) else None
             out = None
+            self.loss_form = 'composed'
             with self._phase_scope(0):
                 if pair is not None:
                     y1, y2, _, _ = model.forward_pair(pair, paired_out=True)
                     if fused and ops.mcd_loss_supported(y1, y2, None, None, label, self.a_t):
                         out = ops.mcd_loss(y1, y2, None, None, label, label if self.a_t else None, self.a_s, self.a_t, self.r_s,
                                            totals=self._books[:4])
-                    else:
+                        self.loss_form = 'mcd_loss'
+                    elif rec is not None:
+                        out = self._cls_loss_tail(rec, y1, y2, None, None, label)
+                    if out is None:
                         (pred_s1, pred_t1), (pred_s2, pred_t2) = ops.split_halves(y1), ops.split_halves(y2)
                 else:
                     pred_s1, pred_s2 = model(data)
@@ -202,6 +224,9 @@ class UDAStep(ReplayedStep):
                         # (the target rows are scored against the SOURCE labels, train_dg_naive_mmd.py:236-237)
                         out = ops.mcd_loss(pred_s1, pred_s2, pred_t1, pred_t2, label, label if self.a_t else None, self.a_s,
                                            self.a_t, self.r_s, totals=self._books[:4])
+                        self.loss_form = 'mcd_loss'
+                    elif rec is not None:
+                        out = self._cls_loss_tail(rec, pred_s1, pred_s2, pred_t1, pred_t2, label)
             if out is not None:
                 loss, loss_s, loss_adv = out[0], out[1], out[2]
             else:
