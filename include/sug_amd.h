@@ -741,6 +741,30 @@ int sug_soft_mmd_multi_fwd(int n, const void* const* feat_s, const int64_t* lds,
 int sug_soft_mmd_multi_bwd(int n, const void* const* z, const int32_t* D, const void* const* wt,
                            const void* const* gscale, int m, int num_class, void* const* dz, void* stream);
 
+/* Class-aligned MMD (hard_mmd / max_hard_mmd, model/mmd.py:69-104) with the row selection and its size n on the device:
+ * no host wait, no data-dependent shape, one launch sequence for every batch.
+ * sug_mmd_select (one workgroup): label_* int64 [m], 1 <= m <= 1024, 1 <= num_class <= 64.
+ *   mode 0 (hard): the rows with label_s[i] == label_t[i], ascending i; idx_s == idx_t.
+ *   mode 1 (stable max-overlap): for c = 0 .. num_class-1 the first min(a_c, b_c) rows of class c of each domain, lowest
+ *   index first, the classes in ascending order (a_c, b_c: rows of class c in label_s, label_t).  A label outside
+ *   [0, num_class) is never paired, on either side, and is no error.
+ *   idx_s / idx_t int32 [m]: the selected rows (first n entries; -1 after them); pos_s / pos_t int32 [m]: a row's position
+ *   in the selection or -1; count int32 [1]: n.  Fixed order, no atomics.
+ * sug_class_mmd_fwd: z [2m, D] (first 2n rows written) = [feat_s[idx_s[0..n)] ; feat_t[idx_t[0..n)]]; sug_mmd_rbf_value of
+ *   those rows with m := n (the kernel form by that function's rule applied to n; wt [2m, 2m] or null, used with row
+ *   stride 2n; sums: 3 doubles of scratch, cleared here); value[0] = (S_XX + S_YY - 2 S_XY) / n^2, NaN when n == 0.
+ *   feat_* fp32 [m, D] with row strides lds / ldt; 1 <= D <= 2^20; nsigma <= 8.
+ * sug_class_mmd_bwd: sug_mmd_rbf_bwd with m := n into dz [2m, D] scratch, then EVERY row of dfeat_s / dfeat_t [m, D] (row
+ *   strides ldds / lddt) is written: a selected row's gradient, exact zeros elsewhere (all rows when n == 0). */
+int sug_mmd_select(const int64_t* label_s, const int64_t* label_t, int m, int num_class, int mode, int32_t* idx_s,
+                   int32_t* idx_t, int32_t* pos_s, int32_t* pos_t, int32_t* count, void* stream);
+int sug_class_mmd_fwd(const float* feat_s, int64_t lds, const float* feat_t, int64_t ldt, int m, int D,
+                      const int32_t* idx_s, const int32_t* idx_t, const int32_t* count, const float* neg_gamma,
+                      int nsigma, float* z, float* wt, double* sums, float* value, void* stream);
+int sug_class_mmd_bwd(const float* z, const float* wt, int m, int D, const int32_t* count, const int32_t* pos_s,
+                      const int32_t* pos_t, const float* gscale, float* dz, float* dfeat_s, int64_t ldds,
+                      float* dfeat_t, int64_t lddt, void* stream);
+
 /* The EdgeConv GEMM operand of a conv_2d weight W [Co, 2C] (get_graph_feature's cat(x_j - x_i, x_i) folded into
  * the weights, model/model_utils.py:188-210): backward = 0: in = W, out [2Co, C] = [W[:, :C] ; W[:, C:] - W[:, :C]];
  * backward = 1: in = d out [2Co, C], out = dW [Co, 2C]. */

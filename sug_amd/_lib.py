@@ -86,6 +86,9 @@ SIGNATURES = {
     'sug_edge_weight_split_multi': [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
     'sug_soft_mmd_multi_fwd': [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     'sug_soft_mmd_multi_bwd': [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    'sug_mmd_select': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    'sug_class_mmd_fwd': [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    'sug_class_mmd_bwd': [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
     'sug_sda_prob_weights': [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp],
     'sug_sda_prob_weights_multi': [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp],
     'sug_adam_step': [_vp, _vp, _vp, _i32, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp],

@@ -787,3 +787,195 @@ extern "C" int sug_chamfer_weights(const float* a, const float* b, int B, int N,
   SUG_LAUNCH_CHECK("sug_chamfer_weights");
   return SUG_OK;
 }
+
+// ---- class-aligned MMD (hard_mmd / max_hard_mmd, model/mmd.py:69-104) without a host wait: which rows take part, and
+// how many (n), is decided on the device.  sug_mmd_select leaves the row lists and n in device memory; the kernels after it
+// are launched for the capacity m, load n and run the bodies above with m := n; workgroups whose tile lies outside 2n
+// return as a whole BEFORE they enter a body (the bodies contain __syncthreads).  One captured launch sequence therefore
+// serves every batch.  n == 0: no workgroup enters a body, the sums stay 0 and the value is 0/0 = NaN as in the reference;
+// the gradients are exact zeros.
+namespace {
+
+constexpr int SEL_MAX_M = 1024, SEL_MAX_CLASSES = 64, SEL_MAX_D = 1 << 20;
+
+// One workgroup.  A row's key: mode 0 (hard) 0 where label_s[i] == label_t[i], else none (one "class": the matching rows,
+// the same list for both domains); mode 1 (stable max-overlap) its label where that lies in [0, num_class), else none.
+// Class c pairs its first k_c = min(a_c, b_c) rows of each domain, lowest index first; the classes' blocks follow each
+// other in ascending order.  Fixed order, no atomics; m <= 1024, so a row's rank in its class is a count over LDS.
+__global__ __launch_bounds__(256) void mmd_select_kernel(const int64_t* __restrict__ ls, const int64_t* __restrict__ lt, int m,
+                                                         int num_class, int mode, int* __restrict__ idx_s,
+                                                         int* __restrict__ idx_t, int* __restrict__ pos_s,
+                                                         int* __restrict__ pos_t, int* __restrict__ count) {
+  __shared__ short s_ks[SEL_MAX_M], s_kt[SEL_MAX_M];
+  __shared__ int s_k[SEL_MAX_CLASSES], s_off[SEL_MAX_CLASSES + 1];
+  const int nc = mode == 0 ? 1 : num_class;
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const int64_t a = ls[i], b = lt[i];
+    if (mode == 0) {
+      s_ks[i] = s_kt[i] = (a == b) ? 0 : -1;
+    } else {
+      s_ks[i] = (a >= 0 && a < num_class) ? (short)a : (short)-1;
+      s_kt[i] = (b >= 0 && b < num_class) ? (short)b : (short)-1;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nc) {
+    const int c = threadIdx.x;
+    int a = 0, b = 0;
+    for (int j = 0; j < m; ++j) {
+      a += s_ks[j] == c;
+      b += s_kt[j] == c;
+    }
+    s_k[c] = a < b ? a : b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int o = 0;
+    for (int c = 0; c < nc; ++c) {
+      s_off[c] = o;
+      o += s_k[c];
+    }
+    s_off[nc] = o;
+    count[0] = o;
+  }
+  __syncthreads();
+  const int n = s_off[nc];
+  for (int i = threadIdx.x; i < m; i += 256) {
+    if (i >= n) idx_s[i] = idx_t[i] = -1;                    // past the selection (no row below writes there: p < n)
+  }
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const int cs = s_ks[i], ct = s_kt[i];
+    int rs = 0, rt = 0;
+    for (int j = 0; j < i; ++j) {
+      rs += s_ks[j] == cs;
+      rt += s_kt[j] == ct;
+    }
+    const int ps = (cs >= 0 && rs < s_k[cs]) ? s_off[cs] + rs : -1;
+    const int pt = (ct >= 0 && rt < s_k[ct]) ? s_off[ct] + rt : -1;
+    pos_s[i] = ps;
+    pos_t[i] = pt;
+    if (ps >= 0) idx_s[ps] = i;
+    if (pt >= 0) idx_t[pt] = i;
+  }
+}
+
+// Z = [feat_s[idx_s[0..n)] ; feat_t[idx_t[0..n)]] (row stride D, the Y block at row n) in a buffer of 2m rows; the three
+// sums of the launch that follows in stream order are cleared here (a kernel, not a memset node: see sug_mmd_rbf_value)
+__global__ __launch_bounds__(256) void mmd_gather_sel_kernel(const float* __restrict__ fs, int64_t lds,
+                                                             const float* __restrict__ ft, int64_t ldt,
+                                                             const int* __restrict__ idx_s, const int* __restrict__ idx_t,
+                                                             const int* __restrict__ count, int m, int D,
+                                                             float* __restrict__ z, double* __restrict__ sums) {
+  if (blockIdx.x == 0 && threadIdx.x < 3) sums[threadIdx.x] = 0.0;
+  const int n = count[0] < m ? count[0] : m;
+  const int r = blockIdx.x;
+  if (r >= 2 * n) return;
+  const int row = r < n ? idx_s[r] : idx_t[r - n];
+  if (row < 0 || row >= m) return;                            // (lists that sug_mmd_select did not write)
+  const float* src = r < n ? fs + (int64_t)row * lds : ft + (int64_t)row * ldt;
+  float* dst = z + (int64_t)r * D;
+  for (int c = threadIdx.x; c < D; c += 256) dst[c] = src[c];
+}
+
+// sug_mmd_rbf_rows with m := n read from the device: the form by that function's own rule applied to n, the grid sized by
+// the host for the capacity m (and for the 4 x 4 tiles where the small form can occur)
+__global__ __launch_bounds__(256) void mmd_rbf_sel_kernel(const float* __restrict__ z, int D, const int* __restrict__ count,
+                                                          int m, const float* __restrict__ neg_gamma, int ns,
+                                                          double* __restrict__ sums, float* __restrict__ wt) {
+  const int n = count[0] < m ? count[0] : m;
+  const bool small = 2 * n <= 128 && D >= 256;
+  const int tile = small ? 4 : TI;
+  const int nb = (2 * n + tile - 1) / tile;
+  if ((int)blockIdx.x >= nb || (int)blockIdx.y >= nb) return;   // the whole workgroup: n is uniform
+  if (small)
+    mmd_rbf_small_body(blockIdx.x, blockIdx.y, z, D, n, D, nullptr, neg_gamma, ns, 0, n, sums, wt);
+  else
+    mmd_rbf_body(blockIdx.x, blockIdx.y, z, D, n, D, nullptr, neg_gamma, ns, 0, n, sums, wt);
+}
+
+__global__ void mmd_value_sel_kernel(const double* __restrict__ sums, const int* __restrict__ count, float* __restrict__ out) {
+  if (threadIdx.x == 0) {
+    const double n = (double)count[0];
+    out[0] = (float)((sums[0] + sums[1] - 2.0 * sums[2]) / (n * n));     // n == 0: 0 / 0 = NaN (model/mmd.py:300-303)
+  }
+}
+
+// sug_mmd_rbf_bwd with m := n: dz [2n, D] dense
+__global__ __launch_bounds__(256) void mmd_bwd_sel_kernel(const float* __restrict__ z, int D, const float* __restrict__ wt,
+                                                          const int* __restrict__ count, int m, const float* __restrict__ gscale,
+                                                          float* __restrict__ dz) {
+  const int n = count[0] < m ? count[0] : m;
+  if ((int)blockIdx.y * 32 >= 2 * n) return;                   // the whole workgroup
+  mmd_bwd_body(blockIdx.x, blockIdx.y, z, D, wt, n, D, 0, n, gscale, 1.0f, dz, D);
+}
+
+// every row of d feat_s / d feat_t [m, D]: the selected row's gradient from dz, exact zeros elsewhere (a row is selected at
+// most once: plain stores)
+__global__ __launch_bounds__(256) void mmd_scatter_sel_kernel(const float* __restrict__ dz, int D, const int* __restrict__ pos_s,
+                                                              const int* __restrict__ pos_t, const int* __restrict__ count,
+                                                              int m, float* __restrict__ dfs, int64_t ldds,
+                                                              float* __restrict__ dft, int64_t lddt) {
+  const int n = count[0] < m ? count[0] : m;
+  const int r = blockIdx.x;
+  const int p = r < m ? pos_s[r] : pos_t[r - m];
+  float* dst = r < m ? dfs + (int64_t)r * ldds : dft + (int64_t)(r - m) * lddt;
+  if (p >= 0 && p < n) {
+    const float* src = dz + (int64_t)(r < m ? p : n + p) * D;
+    for (int c = threadIdx.x; c < D; c += 256) dst[c] = src[c];
+  } else {
+    for (int c = threadIdx.x; c < D; c += 256) dst[c] = 0.f;
+  }
+}
+
+}  // namespace
+
+extern "C" int sug_mmd_select(const int64_t* label_s, const int64_t* label_t, int m, int num_class, int mode, int32_t* idx_s,
+                              int32_t* idx_t, int32_t* pos_s, int32_t* pos_t, int32_t* count, void* stream) {
+  SUG_REQUIRE(label_s && label_t && idx_s && idx_t && pos_s && pos_t && count, "sug_mmd_select: null pointer");
+  SUG_REQUIRE(m >= 1 && m <= SEL_MAX_M, "sug_mmd_select: m=%d (1..%d)", m, SEL_MAX_M);
+  SUG_REQUIRE(num_class >= 1 && num_class <= SEL_MAX_CLASSES, "sug_mmd_select: num_class=%d (1..%d)", num_class, SEL_MAX_CLASSES);
+  SUG_REQUIRE(mode == 0 || mode == 1, "sug_mmd_select: mode %d (0 hard, 1 stable max-overlap)", mode);
+  hipLaunchKernelGGL(mmd_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, label_s, label_t, m, num_class, mode, idx_s,
+                     idx_t, pos_s, pos_t, count);
+  SUG_LAUNCH_CHECK("sug_mmd_select");
+  return SUG_OK;
+}
+
+extern "C" int sug_class_mmd_fwd(const float* feat_s, int64_t lds, const float* feat_t, int64_t ldt, int m, int D,
+                                 const int32_t* idx_s, const int32_t* idx_t, const int32_t* count, const float* neg_gamma,
+                                 int nsigma, float* z, float* wt, double* sums, float* value, void* stream) {
+  SUG_REQUIRE(feat_s && feat_t && idx_s && idx_t && count && neg_gamma && z && sums && value, "sug_class_mmd_fwd: null pointer");
+  SUG_REQUIRE(m >= 1 && m <= SEL_MAX_M, "sug_class_mmd_fwd: m=%d (1..%d)", m, SEL_MAX_M);
+  SUG_REQUIRE(D >= 1 && D <= SEL_MAX_D && lds >= D && ldt >= D, "sug_class_mmd_fwd: bad shape D=%d (1..%d, row strides >= D)", D,
+              SEL_MAX_D);
+  SUG_REQUIRE(nsigma >= 1 && nsigma <= 8, "sug_class_mmd_fwd: nsigma=%d", nsigma);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mmd_gather_sel_kernel, dim3(2 * m), dim3(256), 0, st, feat_s, lds, feat_t, ldt, idx_s, idx_t, count, m, D, z,
+                     sums);
+  // the tiled form needs ceil(2m / 16) tiles a side; the small form (2n <= 128, D >= 256) ceil(2 min(m, 64) / 4)
+  int nb = sug_divup(2 * m, TI);
+  if (D >= 256) {
+    const int nbs = sug_divup(2 * (m < 64 ? m : 64), 4);
+    if (nbs > nb) nb = nbs;
+  }
+  hipLaunchKernelGGL(mmd_rbf_sel_kernel, dim3(nb, nb), dim3(256), 0, st, z, D, count, m, neg_gamma, nsigma, sums, wt);
+  hipLaunchKernelGGL(mmd_value_sel_kernel, dim3(1), dim3(64), 0, st, sums, count, value);
+  SUG_LAUNCH_CHECK("sug_class_mmd_fwd");
+  return SUG_OK;
+}
+
+extern "C" int sug_class_mmd_bwd(const float* z, const float* wt, int m, int D, const int32_t* count, const int32_t* pos_s,
+                                 const int32_t* pos_t, const float* gscale, float* dz, float* dfeat_s, int64_t ldds,
+                                 float* dfeat_t, int64_t lddt, void* stream) {
+  SUG_REQUIRE(z && wt && count && pos_s && pos_t && gscale && dz && dfeat_s && dfeat_t, "sug_class_mmd_bwd: null pointer");
+  SUG_REQUIRE(m >= 1 && m <= SEL_MAX_M, "sug_class_mmd_bwd: m=%d (1..%d)", m, SEL_MAX_M);
+  SUG_REQUIRE(D >= 1 && D <= SEL_MAX_D && ldds >= D && lddt >= D, "sug_class_mmd_bwd: bad shape D=%d (1..%d, row strides >= D)", D,
+              SEL_MAX_D);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mmd_bwd_sel_kernel, dim3(sug_divup(D, 64), sug_divup(2 * m, 32)), dim3(256), 0, st, z, D, wt, count, m, gscale,
+                     dz);
+  hipLaunchKernelGGL(mmd_scatter_sel_kernel, dim3(2 * m), dim3(256), 0, st, dz, D, pos_s, pos_t, count, m, dfeat_s, ldds, dfeat_t,
+                     lddt);
+  SUG_LAUNCH_CHECK("sug_class_mmd_bwd");
+  return SUG_OK;
+}

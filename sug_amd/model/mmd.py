@@ -28,7 +28,7 @@ def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=No
     elif args["NAME"] == "HARD_MMD":
         return hard_mmd(label_s, feat_s, label_t, feat_t)
     elif args["NAME"] == "MAX_HARD_MMD":
-        return max_hard_mmd(label_s, feat_s, label_t, feat_t)
+        return max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing=args.get("PAIRING", "sorted"))
     elif args["NAME"] == "OFF":
         return mix_rbf_mmd2(feat_s, feat_t, sigma_list)
     raise RuntimeError("Not Supported MMD Method")
@@ -102,16 +102,55 @@ def soft_mmd_sharded(label_s, feat_s, label_t, feat_t, label_g, feat_g_s, label_
 
 
 def hard_mmd(label_s, feat_s, label_t, feat_t):
-    """model/mmd.py:69-77."""
+    """model/mmd.py:69-77: MMD of the rows whose two labels agree.  On the device the rows are chosen there
+    (ops.class_mmd, mode 0): no host wait, and a batch without such a row gives NaN with zero gradients as in the
+    reference; otherwise (CPU tensors, beyond ops.class_mmd_supported's limits, SUG_CLASS_MMD=0) the composed lines."""
+    if ops.class_mmd_supported(label_s, feat_s, label_t, feat_t, sigma_list):
+        return ops.class_mmd(label_s, feat_s, label_t, feat_t, 0, sigma_list)
     same = torch.eq(label_s, label_t)
     return mix_rbf_mmd2(feat_s[same], feat_t[same], sigma_list)
 
 
-def max_hard_mmd(label_s, feat_s, label_t, feat_t):
-    """model/mmd.py:96-104."""
+def max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing='sorted'):
+    """model/mmd.py:96-104.  pairing 'sorted' (the default) pairs the rows get_most_overlapped_element picks on the host:
+    which members of an over-represented class those are follows from torch.sort's unstable order once m > 16.  pairing
+    'stable' (args['PAIRING'] = 'stable') pairs the same NUMBER of rows per class but always the lowest indices
+    (class_pairs_host, mode 1), chosen on the device (ops.class_mmd, mode 1: no host wait, capturable); it needs what
+    ops.class_mmd_supported states.  Labels outside [0, 10) are never paired there and raise nothing."""
+    if pairing == 'stable':
+        if not ops.class_mmd_supported(label_s, feat_s, label_t, feat_t, sigma_list):
+            raise RuntimeError("max_hard_mmd(pairing='stable') runs on the HIP device within ops.class_mmd_supported's limits "
+                               "(and not with SUG_CLASS_MMD=0)")
+        return ops.class_mmd(label_s, feat_s, label_t, feat_t, 1, sigma_list)
+    if pairing != 'sorted':
+        raise RuntimeError("max_hard_mmd: pairing 'sorted' or 'stable' (got %r)" % (pairing,))
     ind_s, ind_t = get_most_overlapped_element(label_s.cpu(), label_t.cpu())
     assert len(ind_s) == len(ind_t), "The feature shape mis-matched"
     return mix_rbf_mmd2(feat_s[ind_s], feat_t[ind_t], sigma_list)
+
+
+def class_pairs_host(label_s, label_t, mode, num_class=10):
+    """The rows a class-aligned MMD pairs, as two Python index lists (ind_s, ind_t) from CPU label tensors: the rule that
+    ops.class_pairs implements on the device, restated plainly.
+      mode 0 (hard_mmd): every i with label_s[i] == label_t[i], ascending; ind_s == ind_t.
+      mode 1 (max_hard_mmd, pairing 'stable'): for c = 0 .. num_class-1 in order, the first min(a_c, b_c) rows of class c of
+      the source paired with the first min(a_c, b_c) rows of class c of the target, lowest index first.  Labels outside
+      [0, num_class) are never paired."""
+    ls, lt = [int(v) for v in label_s.reshape(-1).tolist()], [int(v) for v in label_t.reshape(-1).tolist()]
+    assert len(ls) == len(lt)
+    if mode == 0:
+        ind = [i for i in range(len(ls)) if ls[i] == lt[i]]
+        return ind, list(ind)
+    if mode != 1:
+        raise RuntimeError('class_pairs_host: mode 0 (hard) or 1 (stable max-overlap)')
+    ind_s, ind_t = [], []
+    for c in range(num_class):
+        rows_s = [i for i, v in enumerate(ls) if v == c]
+        rows_t = [i for i, v in enumerate(lt) if v == c]
+        k = min(len(rows_s), len(rows_t))
+        ind_s += rows_s[:k]
+        ind_t += rows_t[:k]
+    return ind_s, ind_t
 
 
 def chamfer_distances(pc_s, pc_t):

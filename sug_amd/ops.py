@@ -2939,6 +2939,108 @@ def soft_mmd_multi(label_s, label_t, terms, sigmas=SIGMA_LIST, num_class=10):
     return out
 
 
+CLASS_MMD = _os.environ.get('SUG_CLASS_MMD', '1') != '0'      # A/B knob: 0 = hard_mmd as boolean indexing + mix_rbf_mmd2 (host waits)
+CLASS_MMD_MAX_ROWS, CLASS_MMD_MAX_CLASSES, CLASS_MMD_MAX_D = 1024, 64, 1 << 20
+_CLASS_MMD_MODES = {0: 0, 1: 1, 'hard': 0, 'stable': 1}
+
+
+def _class_select(label_s, label_t, mode, num_class):
+    """sug_mmd_select: (idx_s, idx_t, pos_s, pos_t, count), all int32 on the labels' device."""
+    _need_gpu(label_s, label_t)
+    if mode not in _CLASS_MMD_MODES:
+        raise RuntimeError("sug_amd.ops: class pairing mode %r (0 / 'hard', 1 / 'stable')" % (mode,))
+    ls, lt = label_s.reshape(-1).long().contiguous(), label_t.reshape(-1).long().contiguous()
+    m = ls.numel()
+    if lt.numel() != m:
+        raise RuntimeError('sug_amd.ops: %d source labels, %d target labels' % (m, lt.numel()))
+    buf = torch.empty(4 * m + 1, dtype=torch.int32, device=ls.device)
+    idx_s, idx_t, pos_s, pos_t, count = buf[:m], buf[m:2 * m], buf[2 * m:3 * m], buf[3 * m:4 * m], buf[4 * m:]
+    check(lib().sug_mmd_select(_p(ls), _p(lt), m, int(num_class), _CLASS_MMD_MODES[mode], _p(idx_s), _p(idx_t), _p(pos_s),
+                               _p(pos_t), _p(count), _st()), 'sug_mmd_select')
+    return idx_s, idx_t, pos_s, pos_t, count
+
+
+def class_pairs(label_s, label_t, mode, num_class=10):
+    """The rows that the class-aligned MMD pairs, chosen on the device: (idx_s, idx_t, n) -- int32 [m] row lists whose first
+    n entries are valid (-1 after them) and the 0-d int32 count n; nothing is read back.  mode 0 / 'hard' (hard_mmd,
+    model/mmd.py:69-77): the rows with label_s[i] == label_t[i] in ascending order, idx_s == idx_t.  mode 1 / 'stable': for
+    every class c in ascending order the first min(a_c, b_c) rows of class c of each domain, lowest index first -- the
+    counts of get_most_overlapped_element (utils/common_utils.py), with a defined choice of members.  A label outside
+    [0, num_class) is never paired, on either side, and raises nothing (the reference asserts on a large source label and
+    silently ignores the others).  1 <= m <= 1024, 1 <= num_class <= 64.  mmd.class_pairs_host restates the rules."""
+    idx_s, idx_t, _, _, count = _class_select(label_s, label_t, mode, num_class)
+    return idx_s, idx_t, count.reshape(())
+
+
+class _ClassMMD(torch.autograd.Function):
+    """mix_rbf_mmd2(feat_s[idx_s[:n]], feat_t[idx_t[:n]]) for the rows of class_pairs, with n left on the device: every
+    buffer is sized by m, the kernels read n (sug_class_mmd_*).  Per-pair arithmetic and backward body are those of
+    mix_rbf_mmd2_rows on the gathered rows; unselected rows get exact zeros; n == 0 gives NaN with zero gradients."""
+
+    @staticmethod
+    def forward(ctx, feat_s, feat_t, label_s, label_t, mode, sigmas, num_class):
+        _need_gpu(feat_s, feat_t, label_s, label_t)
+        m, D = feat_s.shape
+        dev = feat_s.device
+        fs = feat_s if (feat_s.stride(1) == 1 and feat_s.stride(0) >= D) else feat_s.contiguous()
+        ft = feat_t if (feat_t.stride(1) == 1 and feat_t.stride(0) >= D) else feat_t.contiguous()
+        idx_s, idx_t, pos_s, pos_t, count = _class_select(label_s, label_t, mode, num_class)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        Z = torch.empty(2 * m, D, dtype=torch.float32, device=dev)
+        wt = torch.empty(2 * m, 2 * m, dtype=torch.float32, device=dev) if need else None
+        sums = torch.empty(3, dtype=torch.float64, device=dev)
+        val = torch.empty((), dtype=torch.float32, device=dev)
+        ng = _neg_gammas(sigmas, dev)
+        check(lib().sug_class_mmd_fwd(_p(fs), fs.stride(0), _p(ft), ft.stride(0), m, D, _p(idx_s), _p(idx_t), _p(count), _p(ng),
+                                      len(sigmas), _p(Z), _p(wt), _p(sums), _p(val), _st()), 'sug_class_mmd_fwd')
+        if need:
+            ctx.save_for_backward(Z, wt, count, pos_s, pos_t)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        Z, wt, count, pos_s, pos_t = ctx.saved_tensors
+        m, D = Z.shape[0] // 2, Z.shape[1]
+        gs = g.detach().to(device=Z.device, dtype=torch.float32).reshape(1)
+        dZ = torch.empty(2 * m, D, dtype=torch.float32, device=Z.device)
+        dF = torch.empty(2 * m, D, dtype=torch.float32, device=Z.device)      # [d feat_s ; d feat_t], written entirely
+        check(lib().sug_class_mmd_bwd(_p(Z), _p(wt), m, D, _p(count), _p(pos_s), _p(pos_t), _p(gs), _p(dZ), _p(dF), D, _p(dF[m:]),
+                                      D, _st()), 'sug_class_mmd_bwd')
+        return (dF[:m] if ctx.needs_input_grad[0] else None, dF[m:] if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None)
+
+
+def class_mmd_supported(label_s, feat_s, label_t, feat_t, sigmas=SIGMA_LIST, num_class=10):
+    """What class_mmd takes (and sug_class_mmd_* would otherwise refuse), and the SUG_CLASS_MMD knob: two fp32 [m, D] feature
+    blocks of one shape and m integer labels per domain on the HIP device, 1 <= m <= 1024, 1 <= D <= 2^20,
+    1 <= num_class <= 64, 1 to 8 sigmas."""
+    if not CLASS_MMD:
+        return False
+    ts = (label_s, feat_s, label_t, feat_t)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        return False
+    if feat_s.dtype != torch.float32 or feat_t.dtype != torch.float32 or feat_s.dim() != 2 or feat_s.shape != feat_t.shape:
+        return False
+    m, D = feat_s.shape
+    for lab in (label_s, label_t):
+        if lab.numel() != m or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            return False
+    return 1 <= m <= CLASS_MMD_MAX_ROWS and 1 <= D <= CLASS_MMD_MAX_D and 1 <= int(num_class) <= CLASS_MMD_MAX_CLASSES \
+        and 1 <= len(sigmas) <= 8
+
+
+def class_mmd(label_s, feat_s, label_t, feat_t, mode, sigmas=SIGMA_LIST, num_class=10):
+    """Class-aligned MMD^2 (0-d fp32 tensor, differentiable in both feature blocks) of the rows class_pairs selects: mode 0 /
+    'hard' is hard_mmd (model/mmd.py:69-77), mode 1 / 'stable' max_hard_mmd (:96-104) with the stable pairing.  No host
+    read, no boolean indexing: a step that calls it can be captured, and one captured step serves batches with different
+    n.  No pair (n == 0): NaN, and both gradients exact zeros, as the reference has it."""
+    if feat_s.dtype != torch.float32 or feat_t.dtype != torch.float32 or feat_s.shape != feat_t.shape or feat_s.dim() != 2:
+        raise RuntimeError('sug_amd.ops.class_mmd: two fp32 [m, D] feature blocks of one shape')
+    if not 1 <= len(sigmas) <= 8:
+        raise RuntimeError('sug_amd.ops.class_mmd: 1 to 8 sigmas (got %d)' % len(sigmas))
+    return _ClassMMD.apply(feat_s, feat_t, label_s, label_t, mode, tuple(sigmas), int(num_class))
+
+
 def colsum(x2, sign=1.0):
     """fp32 column sums [C] of a [R, C] fp32 / fp16 matrix (sug_colsum: no memset, fixed order)."""
     _need_gpu(x2)
