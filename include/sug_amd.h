@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -743,7 +743,8 @@ int sug_soft_mmd_multi_bwd(int n, const void* const* z, const int32_t* D, const 
 
 /* Class-aligned MMD (hard_mmd / max_hard_mmd, model/mmd.py:69-104) with the row selection and its size n on the device:
  * no host wait, no data-dependent shape, one launch sequence for every batch.
- * sug_mmd_select (one workgroup): label_* int64 [m], 1 <= m <= 1024, 1 <= num_class <= 64.
+ * sug_mmd_select (one workgroup): label_* int64 [m], 1 <= m <= SUG_CLASS_MMD_MAX_ROWS, 1 <= num_class <=
+ *   SUG_CLASS_MMD_MAX_CLASSES.
  *   mode 0 (hard): the rows with label_s[i] == label_t[i], ascending i; idx_s == idx_t.
  *   mode 1 (stable max-overlap): for c = 0 .. num_class-1 the first min(a_c, b_c) rows of class c of each domain, lowest
  *   index first, the classes in ascending order (a_c, b_c: rows of class c in label_s, label_t).  A label outside
@@ -753,9 +754,12 @@ int sug_soft_mmd_multi_bwd(int n, const void* const* z, const int32_t* D, const 
  * sug_class_mmd_fwd: z [2m, D] (first 2n rows written) = [feat_s[idx_s[0..n)] ; feat_t[idx_t[0..n)]]; sug_mmd_rbf_value of
  *   those rows with m := n (the kernel form by that function's rule applied to n; wt [2m, 2m] or null, used with row
  *   stride 2n; sums: 3 doubles of scratch, cleared here); value[0] = (S_XX + S_YY - 2 S_XY) / n^2, NaN when n == 0.
- *   feat_* fp32 [m, D] with row strides lds / ldt; 1 <= D <= 2^20; nsigma <= 8.
+ *   feat_* fp32 [m, D] with row strides lds / ldt; 1 <= D <= SUG_CLASS_MMD_MAX_D; nsigma <= 8.
  * sug_class_mmd_bwd: sug_mmd_rbf_bwd with m := n into dz [2m, D] scratch, then EVERY row of dfeat_s / dfeat_t [m, D] (row
  *   strides ldds / lddt) is written: a selected row's gradient, exact zeros elsewhere (all rows when n == 0). */
+#define SUG_CLASS_MMD_MAX_ROWS 1024
+#define SUG_CLASS_MMD_MAX_CLASSES 64
+#define SUG_CLASS_MMD_MAX_D 1048576
 int sug_mmd_select(const int64_t* label_s, const int64_t* label_t, int m, int num_class, int mode, int32_t* idx_s,
                    int32_t* idx_t, int32_t* pos_s, int32_t* pos_t, int32_t* count, void* stream);
 int sug_class_mmd_fwd(const float* feat_s, int64_t lds, const float* feat_t, int64_t ldt, int m, int D,
@@ -791,9 +795,11 @@ int sug_chamfer_weights(const float* a, const float* b, int B, int N, int M, int
  * nn.CrossEntropyLoss(), :167): loss[0] = w * (CE(logits1[:M], label) + CE(logits2[:M], label)), CE = mean over the M
  * rows of -log_softmax(row)[label]; w = 0.5 * SRC_LOSS_WEIGHT * CLS_WEIGHT folded by the caller.  logits* [>= M, C] with
  * row stride ld, label int64 [M], lse [2M + 1] (saved log-sum-exp of the rows; lse[2M] = number of rows that count).
- * 2M <= 512, C <= 32.  Labels as nn.CrossEntropyLoss takes them: a row whose label == ignore_index (-100 by default in
- * torch) contributes nothing and is left out of the mean; any other label outside [0, C) -- where torch raises -- makes
- * the loss (and the gradient) NaN: never scored as some class. */
+ * 2M <= SUG_CE_PAIR_MAX_ROWS, C <= SUG_CE_PAIR_MAX_CLASSES.  Labels as nn.CrossEntropyLoss takes them: a row whose label ==
+ * ignore_index (-100 by default in torch) contributes nothing and is left out of the mean; any other label outside [0, C) --
+ * where torch raises -- makes the loss (and the gradient) NaN: never scored as some class. */
+#define SUG_CE_PAIR_MAX_ROWS 512      /* source rows x 2 heads */
+#define SUG_CE_PAIR_MAX_CLASSES 32
 int sug_ce_pair_fwd(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int M, int C, float w,
                     int64_t ignore_index, float* loss, float* lse, void* stream);
 /* Its gradient for the WHOLE paired logits: d1, d2 [Mtot, C] = g[0] * w * (softmax - onehot) / lse[2M] in the counting rows
@@ -808,8 +814,10 @@ int sug_ce_pair_bwd(const float* logits1, const float* logits2, int64_t ld, cons
  * skipped and left out of the mean; any other label outside [0, C) makes loss and gradient NaN; no counting row: NaN, as
  * torch).  totals (device double[2], may be null) keeps the epoch's books in the same launch, train_source.py:130-131 without
  * the .item(): totals[0] += (double)loss * M, totals[1] += M (M, not the counting rows, as the reference).
- * 1 <= M <= 1024, 2 <= C <= 64, checked on the host before any launch (-1, sug_last_error()).  One workgroup, a wave per row;
- * the rows' terms are summed in fp64 in one fixed order; no float atomics, no memset node: capturable. */
+ * 1 <= M <= SUG_CE_MAX_ROWS, 2 <= C <= SUG_CE_MAX_CLASSES, checked on the host before any launch (-1, sug_last_error()).  One
+ * workgroup, a wave per row; the rows' terms are summed in fp64 in one fixed order; no float atomics, no memset node: capturable. */
+#define SUG_CE_MAX_ROWS 1024
+#define SUG_CE_MAX_CLASSES 64
 int sug_ce_fwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index, float label_smoothing,
                float* loss, float* lse, double* totals, void* stream);
 /* Its gradient: dlogits [M, C] (dense) = g[0] * (softmax - target) / lse[M] in the counting rows, target =
@@ -824,8 +832,10 @@ int sug_ce_bwd(const float* logits, int64_t ld, const int64_t* label, int M, int
  * out4 = { a_s*CEs - D + a_t*CEt, r_s*CEs, -D, a_t*CEt };  lse [2*Ms + 2*Mt] = the rows' log-sum-exp (ys1, ys2, yt1, yt2), kept for
  * the backward.  totals (device double[4], may be null) keeps the epoch's books in the same launch, train_uda.py:180-184 without the
  * .item(): += { out4[1]*Ms, out4[2]*Ms, Ms, Mt }.  A label outside [0, C) makes the loss (and that row's gradient) NaN; there is no
- * ignore_index.  1 <= Ms, Mt <= 1024, 2 <= C <= 64, checked on the host before any launch (-1, sug_last_error()).  One workgroup, a
- * wave per row; the rows' terms are summed in fp64 in one fixed order; no atomics, no memset node: capturable, bit-reproducible. */
+ * ignore_index.  1 <= Ms, Mt <= SUG_MCD_MAX_ROWS, 2 <= C <= SUG_CE_MAX_CLASSES, checked on the host before any launch (-1,
+ * sug_last_error()).  One workgroup, a wave per row; the rows' terms are summed in fp64 in one fixed order; no atomics, no memset
+ * node: capturable, bit-reproducible. */
+#define SUG_MCD_MAX_ROWS 1024
 int sug_mcd_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
                      const int64_t* label_t, int Ms, int Mt, int C, float a_s, float a_t, float r_s, float* out4, float* lse,
                      double* totals, void* stream);
@@ -852,9 +862,9 @@ int sug_mcd_loss_bwd(const float* ys1, const float* ys2, const float* yt1, const
  * max, then their sums of exp(z - max) (rows in the order ys1, ys2, yt1, yt2), then the divisors of R for source and target.
  * totals (device double[4], may be null) += { (double)out4[1]*Ms, (double)out4[2]*Ms, Ms, Mt } in the same launch.
  * Numerics: p = exp(z - max)/sum; q is the sum of the OTHER classes' probabilities (not 1 - p_y); log p_y = (z_y - max) - log(sum).
- * 1 <= Ms, Mt <= 1024, 2 <= C <= 64, gamma == 0 or gamma >= 1 (for 0 < gamma < 1 the derivative is unbounded at p_y = 1): checked
- * on the host before any launch (-1, sug_last_error()).  One workgroup, a wave per row; the rows' terms are summed in fp64 in one
- * fixed order; no atomics, no memset node: capturable, bit-reproducible. */
+ * 1 <= Ms, Mt <= SUG_MCD_MAX_ROWS, 2 <= C <= SUG_CE_MAX_CLASSES, gamma == 0 or gamma >= 1 (for 0 < gamma < 1 the derivative is
+ * unbounded at p_y = 1): checked on the host before any launch (-1, sug_last_error()).  One workgroup, a wave per row; the
+ * rows' terms are summed in fp64 in one fixed order; no atomics, no memset node: capturable, bit-reproducible. */
 int sug_cls_loss_fwd(const float* ys1, const float* ys2, const float* yt1, const float* yt2, int64_t ld, const int64_t* label,
                      const int64_t* label_t, int Ms, int Mt, int C, const float* alpha, float gamma, int reduce_sum,
                      int64_t ignore_index, float a_s, float a_t, float a_d, float r_s, float* out4, float* save, double* totals,
@@ -992,8 +1002,9 @@ int sug_ptcls_head_bwd(const float* dlogits, const float* mean, const float* h1,
  * counter may be null only when nothing is drawn.  Debug outputs (each may be null): angles_out [B], noise_out [B, N, 3]
  * (the unit normals used for each output row, zeros for padding), sel_out [B, N] (source point, -1 for padding).
  * An idx entry outside [0, M) or a sel entry outside [0, P) is never dereferenced: the cloud / row is written as NaN.
- * Limits, checked on the host before the launch: B >= 1, 1 <= P <= 4096, N <= 1.5 * P (the reference raises "Too few
- * points" there).  Vector stores only, no atomics; bit-reproducible from (inputs, seed, *counter). */
+ * Limits, checked on the host before the launch: B >= 1, 1 <= P <= SUG_PREP_MAX_POINTS, N <= 1.5 * P (the reference raises
+ * "Too few points" there).  Vector stores only, no atomics; bit-reproducible from (inputs, seed, *counter). */
+#define SUG_PREP_MAX_POINTS 4096
 #define SUG_PREP_NORMALIZE 1
 #define SUG_PREP_ROTATE_Z 2
 #define SUG_PREP_JITTER 4
@@ -1034,8 +1045,9 @@ int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B,
  * column does not vanish exactly), with rank 0 (all correspondences on one point) R = I; never NaN.
  * All sums run in one fixed order without atomics: results are bit-identical from run to run, and a pair's result does
  * not depend on the batch it is launched in.
- * Checked on the host before the launch: no null pointer, B >= 1, 1 <= Ns, Nt <= 1024, 0 <= max_iteration <= 64,
+ * Checked on the host before the launch: no null pointer, B >= 1, 1 <= Ns, Nt <= SUG_ICP_MAX_POINTS, 0 <= max_iteration <= 64,
  * max_corr_dist > 0, src_batch_stride 0 or 3*Ns. */
+#define SUG_ICP_MAX_POINTS 1024
 int sug_icp_fitness(const float* src, int64_t src_batch_stride, const float* tgt, int B, int Ns, int Nt,
                     double max_corr_dist, int max_iteration, double rel_fitness, double rel_rmse, int32_t* count,
                     double* rmse, int32_t* iters, double* transform, void* stream);

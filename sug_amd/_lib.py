@@ -5,6 +5,7 @@ a HIP device, the calling op raises.
 """
 import ctypes
 import os
+import re
 
 # torch must be imported before libsug_amd.so is opened: both need libamdhip64.so.7 and the
 # process must end up with ONE HIP runtime (torch's bundled copy), otherwise launches from this
@@ -13,164 +14,77 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsug_amd.so')
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'sug_amd.h')
 
 _vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 
-# symbol -> argtypes, in the order of include/sug_amd.h (restype int unless noted)
-SIGNATURES = {
-    'sug_knn': [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
-    'sug_knn_reverse': [_vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_fps': [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
-    'sug_ball_query': [_vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
-    'sug_knn_query': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_knn_query_direct': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_three_nn': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_three_nn_direct': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_ball_query_multi': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
-    'sug_fp_interp_fwd': [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
-    'sug_fp_interp_bwd': [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
-    'sug_gather_rows': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    'sug_scatter_add_rows': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    'sug_scatter_rows_ordered_supported': [_i32, _i32, _i32],
-    'sug_scatter_rows_ordered': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
-    'sug_group_max': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_group_max_bwd': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    'sug_edgeconv_fwd': [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_bn_finalize': [_vp, _vp, _vp, _i32, _f64, _f32, _f32, _vp, _vp, _vp, _vp],
-    'sug_affine_act': [_vp, _i64, _vp, _i64, _i32, _f32, _vp, _i64, _vp],
-    'sug_col_stats': [_vp, _i64, _i64, _i32, _vp, _vp, _vp],
-    'sug_edgeconv_bwd_reduce': [_vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp],
-    'sug_edgeconv_bwd_scatter': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
-                                 _vp, _i64, _vp],
-    'sug_edgeconv_layer_fwd': [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp,
-                               _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
-    'sug_edgeconv_fused_layer_fwd': [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32,
-                                     _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
-    'sug_edgeconv_fused_supported': [_i32, _i32, _i32, _i32],
-    'sug_edgeconv_layer_bwd': [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32,
-                               _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
-    'sug_bn_act_rows_fwd': [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _i64,
-                            _vp, _vp, _vp],
-    'sug_bn_act_rows_bwd': [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_bn_act_pool_layer_fwd': [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _f32, _vp, _vp, _vp,
-                                  _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
-    'sug_bn_act_pool_layer_bwd': [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp,
-                                  _i64, _vp, _vp],
-    'sug_fold_groups': [_vp, _i32, _i32, _vp, _vp],
-    'sug_edgeconv_fwd_bn': [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
-                            _vp, _vp],
-    'sug_col_stats_bn': [_vp, _i64, _i64, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
-    'sug_col_stats_bn_grouped': [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
-    'sug_bn_replay': [_vp, _i32, _i32, _f32, _vp, _vp, _vp],
-    'sug_bn_replay_multi': [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_ptran_pos1_fwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
-    'sug_ptran_pos1_bwd': [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
-    'sug_ptran_qk_fwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
-    'sug_ptran_qk_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_ptran_attn_fwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
-    'sug_ptran_fused_supported': [_i32, _i32, _i32, _i32],
-    'sug_ptran_fused_fwd': [_vp] * 13 + [_i32, _i32, _i32, _i32, _f32, _i32] + [_vp] * 9,
-    'sug_ptran_attn_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp,
-                           _vp, _vp, _vp],
-    'sug_ptran_relu_bwd_db': [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
-    'sug_grad_scale16': [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp],
-    'sug_mmd_rbf_value': [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
-    'sug_mmd_rbf_rows': [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_mmd_rbf_rows_bwd': [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _i64, _vp],
-    'sug_mmd_rbf_bwd': [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp],
-    'sug_colsum': [_vp, _i64, _i64, _i32, _i32, _f32, _vp, _vp, _vp],
-    'sug_gate_fwd': [_vp, _vp, _i64, _vp, _vp],
-    'sug_gate_bwd': [_vp, _vp, _vp, _i64, _vp, _vp, _vp],
-    'sug_mmd_assemble': [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp],
-    'sug_edge_weight_split': [_vp, _i32, _i32, _i32, _vp, _vp],
-    'sug_edge_weight_split_multi': [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
-    'sug_soft_mmd_multi_fwd': [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_soft_mmd_multi_bwd': [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
-    'sug_mmd_select': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_class_mmd_fwd': [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_class_mmd_bwd': [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
-    'sug_sda_prob_weights': [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp],
-    'sug_sda_prob_weights_multi': [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp],
-    'sug_adam_step': [_vp, _vp, _vp, _i32, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp],
-    'sug_adam_step_capturable': [_vp, _vp, _vp, _i32, _vp, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp],
-    'sug_adam_chain_step': [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_linear_dw': [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp],
-    'sug_linear_dw_fold': [_vp, _i32, _i64, _vp, _vp],
-    'sug_sa_first_fwd': [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_sa_first_bwd': [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                         _vp, _vp, _vp],
-    'sug_pointmlp_max_bwd_coef': [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_pointmlp_max_bwd_dwfix': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
-    'sug_head_linear_supported': [_i32, _i32, _i32, _i32, _i32],
-    'sug_head_linear_fwd': [_i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
-    'sug_head_ln_bwd': [_i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _vp],
-    'sug_head_linear_bwd': [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp],
-    'sug_gate_bn_fwd': [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp, _vp, _vp],
-    'sug_gate_bn_bwd': [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_copy_rows2d': [_vp, _i64, _vp, _i64, _i64, _i32, _vp],
-    'sug_ln_act_fwd': [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _vp, _vp, _vp],
-    'sug_ln_act_bwd': [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp],
-    'sug_interp3_cat_bwd_lists': [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_interp3_cat_bwd_lists_supported': [_i32, _i32, _i32],
-    'sug_linear_dw_bias': [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp],
-    'sug_node_offset_fwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_node_offset_bwd': [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    'sug_interp3_cat_fwd': [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    'sug_interp3_cat_bwd': [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_bn_bwd_apply': [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp],
-    'sug_bn_act_pool_fwd': [_vp, _i64, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp],
-    'sug_bn_act_pool_bwd': [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _i64, _vp],
-    'sug_rows_gemm': [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp],
-    'sug_pointmlp_max_fwd': [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_pointmlp_max_layer_fwd': [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp,
-                                   _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
-    'sug_pointmlp_max_layer_fwd_xf': [_vp, _i64, _i64, _i32, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32,
-                                      _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
-    'sug_pointmlp_max_bwd_sparse': [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp],
-    'sug_mmd_rbf': [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp],
-    'sug_chamfer': [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_chamfer_weights': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_sa_first_geo_fwd': [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _f32,
-                             _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_sa_first_geo_bwd': [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
-                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_calayer_supported': [_i32, _i32, _i32, _i32],
-    'sug_calayer_fwd': [_i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_calayer_bwd': [_i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    'sug_ce_pair_fwd': [_vp, _vp, _i64, _vp, _i32, _i32, _f32, _i64, _vp, _vp, _vp],
-    'sug_ce_pair_bwd': [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp],
-    'sug_ce_fwd': [_vp, _i64, _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _vp],
-    'sug_ce_bwd': [_vp, _i64, _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _vp],
-    'sug_mcd_loss_fwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp],
-    'sug_mcd_loss_bwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    'sug_cls_loss_fwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _f32, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp,
-                         _vp, _vp],
-    'sug_cls_loss_bwd': [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _f32, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp,
-                         _vp, _vp, _vp, _vp, _vp],
-    'sug_loss_combine_fwd': [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp],
-    'sug_loss_combine_bwd': [_vp, _f32, _f32, _vp, _vp],
-    'sug_eval_accumulate': [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _i32, _i64, _f32, _vp, _vp, _i32, _vp, _i32, _vp],
-    'sug_grid_subsample': [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp],
-    'sug_radius_neighbors': [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp],
-    'sug_radius_reverse': [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_kpconv_fwd': [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp],
-    'sug_kpconv_bwd': [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
-    'sug_seg_instnorm_fwd': [_vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_seg_instnorm_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_seg_max_pool_fwd': [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    'sug_seg_max_pool_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
-    'sug_seg_mean_fwd': [_vp, _vp, _i32, _i32, _vp, _vp],
-    'sug_seg_mean_bwd': [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
-    'sug_ptcls_head_supported': [_i32, _i32, _i32, _i32, _i32, _i32],
-    'sug_ptcls_head_fwd': [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
-    'sug_ptcls_head_bwd': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
-                           _vp, _vp, _vp, _vp, _vp],
-    'sug_prepare_batch': [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _f32, _f32, _vp,
-                          _vp, _vp, _vp, _vp],
-    'sug_icp_fitness': [_vp, _i64, _vp, _i32, _i32, _i32, _f64, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp],
-}
+_SCALARS = {'int': _i32, 'int32_t': _i32, 'int64_t': _i64, 'uint64_t': ctypes.c_uint64, 'float': _f32, 'double': _f64}
+_RESTYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'const char*': ctypes.c_char_p}
 
-STATS_BLOCKS = 1024        # SUG_STATS_BLOCKS
+
+def parse_header(text):
+    """The C ABI from the header's text: ({name: (restype, [argtypes])} for every declaration, {SUG_NAME: int} for every
+    object-like #define with an integer value).  Strict: whatever does not fit raises ValueError, nothing is skipped."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)         # comments hold ';', '(' and function names
+    guard = re.search(r'^[ \t]*#[ \t]*ifndef[ \t]+(\w+)', text, flags=re.M)
+    constants, code = {}, []
+    for line in text.splitlines():
+        if not line.lstrip().startswith('#'):
+            code.append(line)
+            continue
+        if line.rstrip().endswith('\\'):
+            raise ValueError('sug_amd.h: a continued preprocessor line is not supported: %r' % line.strip())
+        m = re.match(r'\s*#\s*define\s+(SUG_\w+)(\(?)(.*)', line)
+        if not m or m.group(2):                                         # not a SUG_* define, or a function-like macro
+            continue
+        name, value = m.group(1), m.group(3).strip()
+        if not value and guard and name == guard.group(1):              # the include guard
+            continue
+        if value.startswith('(') and value.endswith(')'):
+            value = value[1:-1].strip()
+        lit = re.fullmatch(r'(-?)\s*(0[xX][0-9a-fA-F]+|0|[1-9][0-9]*)[uU]?', value)
+        if not lit:
+            raise ValueError('sug_amd.h: #define %s is not an integer literal: %r' % (name, line.strip()))
+        constants[name] = int(lit.group(1) + lit.group(2), 0)
+    code = re.sub(r'extern\s+"C"\s*\{(.*)\}', r'\1', '\n'.join(code), flags=re.S)
+    functions = {}
+    *decls, tail = code.split(';')
+    if tail.strip():
+        raise ValueError('sug_amd.h: text behind the last declaration: %r' % ' '.join(tail.split()))
+    for decl in decls:
+        decl = re.sub(r' ?\* ?', '* ', ' '.join(decl.split()))
+        m =re.fullmatch(r'(const char\*|int64_t|int) (\w+) ?\((.*)\)', decl)
+        if not m or not m.group(2).startswith('sug_') or m.group(2) in functions:
+            raise ValueError('sug_amd.h: not a declaration of a new sug_* function returning int, int64_t or const char*: %r' % decl)
+        args = []
+        for param in ([] if m.group(3).strip() == 'void' else m.group(3).split(',')):
+            words = param.split()
+            if '[' in param or '(' in param:
+                raise ValueError('sug_amd.h: array or function parameter %r in %r' % (param.strip(), decl))
+            if '*' in param:
+                args.append(_vp)
+            elif len(words) == 2 and words[0] in _SCALARS and words[1].isidentifier():
+                args.append(_SCALARS[words[0]])
+            else:
+                raise ValueError('sug_amd.h: parameter %r in %r is neither a pointer nor a known scalar' % (param.strip(), decl))
+        functions[m.group(2)] = (_RESTYPES[m.group(1)], args)
+    return functions, constants
+
+
+def _header_text():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError('sug_amd: %s not found -- the ctypes binding is derived from it; keep include/ beside the '
+                           'package, there is no fallback path' % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return f.read()
+
+
+# Declaring an entry point in the header is its whole registration: DECLARATIONS holds every declaration as
+# name -> (restype, argtypes), CONSTANTS every integer #define; SIGNATURES keeps the argtypes of the status-returning ones.
+DECLARATIONS, CONSTANTS = parse_header(_header_text())
+SIGNATURES = {name: args for name, (res, args) in DECLARATIONS.items() if res is ctypes.c_int and args}
+
+STATS_BLOCKS = CONSTANTS['SUG_STATS_BLOCKS']
 
 _lib = None
 
@@ -185,31 +99,11 @@ def lib():
                 '`python -c "import __graft_entry__ as g; g.build()"`; there is no fallback path'
                 % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
+        for name, (res, args) in DECLARATIONS.items():
             fn = getattr(L, name)
             fn.argtypes = args
-            fn.restype = ctypes.c_int
-        L.sug_linear_dw_workspace.restype = ctypes.c_int64
-        L.sug_linear_dw_workspace.argtypes = [_i64, _i32, _i32]
-        L.sug_pointmlp_max_bwd_workspace.restype = ctypes.c_int64
-        L.sug_pointmlp_max_bwd_workspace.argtypes = [_i64, _i32, _i32, _i32]
-        L.sug_colsum_workspace.restype = ctypes.c_int64
-        L.sug_colsum_workspace.argtypes = [_i64, _i32]
-        L.sug_ptran_colsum_workspace.restype = ctypes.c_int64
-        L.sug_ptran_colsum_workspace.argtypes = [_i64]
-        L.sug_chamfer_workspace.restype = ctypes.c_int64
-        L.sug_scatter_rows_workspace.restype = ctypes.c_int64
-        L.sug_scatter_rows_workspace.argtypes = [_i32, _i32, _i32]
-        L.sug_chamfer_workspace.argtypes = [_i32, _i32, _i32]
-        L.sug_adam_chunk.restype = ctypes.c_int
-        L.sug_adam_chunk.argtypes = []
-        L.sug_adam_chain_chunk.restype = ctypes.c_int
-        L.sug_adam_chain_chunk.argtypes = []
-        L.sug_last_error.restype = ctypes.c_char_p
-        L.sug_last_error.argtypes = []
-        L.sug_abi_version.restype = ctypes.c_int
-        L.sug_abi_version.argtypes = []
-        if L.sug_abi_version() != 7:
+            fn.restype = res
+        if L.sug_abi_version() != CONSTANTS['SUG_ABI_VERSION']:
             raise RuntimeError('sug_amd: ABI version mismatch, rebuild libsug_amd.so')
         _lib = L
     return _lib

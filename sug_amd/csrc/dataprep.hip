@@ -5,7 +5,7 @@
 
 namespace {
 
-constexpr int PREP_MAX_P = 4096;
+constexpr int PREP_MAX_P = SUG_PREP_MAX_POINTS;
 constexpr int PREP_MAX_WAVES = 16;
 
 // Philox4x32-10 (Salmon et al., SC'11): counter c[4], key k[2]

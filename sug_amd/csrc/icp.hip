@@ -14,7 +14,7 @@ namespace {
 
 constexpr int ICP_THREADS = 256;
 constexpr int ICP_WAVES = ICP_THREADS / WAVE;
-constexpr int ICP_MAX_POINTS = 1024;
+constexpr int ICP_MAX_POINTS = SUG_ICP_MAX_POINTS;
 static_assert(ICP_MAX_POINTS <= 4 * ICP_THREADS, "the launcher instantiates 1 .. 4 source points per lane");
 constexpr int ICP_MAX_ITER = 64;
 constexpr int ICP_SUMS = 17;

@@ -11,8 +11,8 @@
 #include "common.h"
 
 namespace {
-constexpr int CE_MAXC = 32;       // classes
-constexpr int CE_MAXROWS = 512;   // source rows x 2 heads
+constexpr int CE_MAXC = SUG_CE_PAIR_MAX_CLASSES;    // classes
+constexpr int CE_MAXROWS = SUG_CE_PAIR_MAX_ROWS;    // source rows x 2 heads
 
 __global__ __launch_bounds__(512) void ce_pair_fwd_kernel(const float* __restrict__ l1, const float* __restrict__ l2, int64_t ld,
                                                           const int64_t* __restrict__ label, int M, int C, float w,
@@ -90,8 +90,8 @@ __global__ void loss_combine_bwd_kernel(const float* __restrict__ g, float wg, f
 // in fp64 -- lane l takes rows l, l + 64, ... in order, then the butterfly -- an order that does not depend on the number of
 // waves launched.  Thread 0 writes the loss and keeps the epoch's books (plain fp64 read-modify-write: one workgroup, stream
 // order).
-constexpr int CE1_MAXC = 64;
-constexpr int CE1_MAXROWS = 1024;
+constexpr int CE1_MAXC = SUG_CE_MAX_CLASSES;
+constexpr int CE1_MAXROWS = SUG_CE_MAX_ROWS;
 
 __global__ __launch_bounds__(1024) void ce_fwd_kernel(const float* __restrict__ logits, int64_t ld,
                                                       const int64_t* __restrict__ label, int M, int C, int64_t ignore_index,
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 // rows' terms meet in LDS and wave 0 folds them in fp64 -- lane l takes rows l, l + 64, ... in order, then the butterfly -- an
 // order that does not depend on the number of waves launched.  Thread 0 writes the four scalars and keeps the epoch's books
 // (plain fp64 read-modify-write: one workgroup, stream order).  Labels outside [0, C) poison the loss with NaN.
-constexpr int MCD_MAXROWS = 1024;
+constexpr int MCD_MAXROWS = SUG_MCD_MAX_ROWS;
 
 __device__ __forceinline__ float row_lse(float z, bool in) {
   const float mx = wave_max_f(z);

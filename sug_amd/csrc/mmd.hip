@@ -796,7 +796,7 @@ extern "C" int sug_chamfer_weights(const float* a, const float* b, int B, int N,
 // the gradients are exact zeros.
 namespace {
 
-constexpr int SEL_MAX_M = 1024, SEL_MAX_CLASSES = 64, SEL_MAX_D = 1 << 20;
+constexpr int SEL_MAX_M = SUG_CLASS_MMD_MAX_ROWS, SEL_MAX_CLASSES = SUG_CLASS_MMD_MAX_CLASSES, SEL_MAX_D = SUG_CLASS_MMD_MAX_D;
 
 // One workgroup.  A row's key: mode 0 (hard) 0 where label_s[i] == label_t[i], else none (one "class": the matching rows,
 // the same list for both domains); mode 1 (stable max-overlap) its label where that lies in [0, num_class), else none.

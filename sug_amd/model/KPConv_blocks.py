@@ -69,8 +69,8 @@ def load_kernels(radius, num_kpoints, dimension, fixed, lloyd=False):
 # ----------------------------------------------------------------------------------------------- helpers
 def _rev_single(neighb_inds, Nq, Ns):
     """Reverse lists of a neighbour table treated as one cloud (a KPConv called outside the preprocessed batch)."""
-    if Ns > 4096:
-        raise NotImplementedError('KPConv outside a preprocessed batch: at most 4096 supports (got %d)' % Ns)
+    if Ns > ops.KPCONV_MAX_CLOUD:
+        raise NotImplementedError('KPConv outside a preprocessed batch: at most %d supports (got %d)' % (ops.KPCONV_MAX_CLOUD, Ns))
     dev = neighb_inds.device
     qoff = torch.tensor([0, Nq], dtype=torch.int32, device=dev)
     soff = torch.tensor([0, Ns], dtype=torch.int32, device=dev)

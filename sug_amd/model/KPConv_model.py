@@ -94,8 +94,8 @@ class PreprocessorGPU(nn.Module):
         dev = points.device
         B = len(lengths)
         cap = max(lengths)
-        if cap > 4096:
-            raise NotImplementedError('KPConv preprocessing: clouds of at most 4096 points (got %d)' % cap)
+        if cap > ops.KPCONV_MAX_CLOUD:
+            raise NotImplementedError('KPConv preprocessing: clouds of at most %d points (got %d)' % (ops.KPCONV_MAX_CLOUD, cap))
         off0 = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int32).to(dev, non_blocking=True)
         bufs, offs = [points], [off0]
         for li, (r, pooled) in enumerate(plan):

@@ -11,7 +11,7 @@ import os as _os
 
 import torch
 
-from ._lib import lib, check, STATS_BLOCKS
+from ._lib import lib, check, STATS_BLOCKS, CONSTANTS as _H      # _H: the #defines of include/sug_amd.h
 
 class StepContext:
     """The mutable state a forward / training step of this package scopes -- ONE object instead of a dozen module globals (round 6,
@@ -2254,9 +2254,12 @@ class _CEPair(torch.autograd.Function):
         return d[0], d[1], None, None, None
 
 
+CE_PAIR_MAX_ROWS, CE_PAIR_MAX_CLASSES = _H['SUG_CE_PAIR_MAX_ROWS'], _H['SUG_CE_PAIR_MAX_CLASSES']
+
+
 def ce_pair_supported(y1, y2, label):
-    return y1.is_cuda and y1.dtype == torch.float32 and y1.dim() == 2 and y1.shape == y2.shape and y1.shape[1] <= 32 \
-        and 2 * label.shape[0] <= 512 and label.shape[0] <= y1.shape[0]
+    return y1.is_cuda and y1.dtype == torch.float32 and y1.dim() == 2 and y1.shape == y2.shape and y1.shape[1] <= CE_PAIR_MAX_CLASSES \
+        and 2 * label.shape[0] <= CE_PAIR_MAX_ROWS and label.shape[0] <= y1.shape[0]
 
 
 def ce_pair(y1, y2, label, w, ignore_index=-100):
@@ -2266,7 +2269,7 @@ def ce_pair(y1, y2, label, w, ignore_index=-100):
     return _CEPair.apply(y1, y2, label, w, ignore_index)
 
 
-CE_MAX_ROWS, CE_MAX_CLASSES = 1024, 64
+CE_MAX_ROWS, CE_MAX_CLASSES = _H['SUG_CE_MAX_ROWS'], _H['SUG_CE_MAX_CLASSES']
 
 
 class _CE(torch.autograd.Function):
@@ -2345,7 +2348,7 @@ def loss_combine(loss_cls, v_geo, v_sem1, v_sem2, wg, ws):
     return _LossCombine.apply(loss_cls, v_geo, v_sem1, v_sem2, wg, ws)
 
 
-MCD_MAX_ROWS, MCD_MAX_CLASSES = 1024, 64
+MCD_MAX_ROWS, MCD_MAX_CLASSES = _H['SUG_MCD_MAX_ROWS'], _H['SUG_CE_MAX_CLASSES']
 
 
 class _MCDLoss(torch.autograd.Function):
@@ -2548,9 +2551,10 @@ def cls_loss(ys1, ys2, yt1, yt2, label, label_t=None, alpha=None, gamma=0.0, red
 
 
 # ----------------------------------------------------------------------------- evaluation metrics (sug_eval_accumulate)
-EVAL_MAX_ROWS, EVAL_MAX_CLASSES = 4096, 64              # SUG_EVAL_MAX_ROWS, SUG_EVAL_MAX_CLASSES
-EVAL_BATCH_COUNT, EVAL_DATA_TOTAL, EVAL_CORRECT_TOTAL, EVAL_ERROR, EVAL_LOSS_TOTAL = 0, 1, 2, 3, 4
-EVAL_CLASS_ACC, EVAL_CLASS_ROWS, EVAL_CLASS_CORRECT, EVAL_BATCH_ACC = 8, 136, 200, 264
+(EVAL_MAX_ROWS, EVAL_MAX_CLASSES, EVAL_BATCH_COUNT, EVAL_DATA_TOTAL, EVAL_CORRECT_TOTAL, EVAL_ERROR, EVAL_LOSS_TOTAL, EVAL_CLASS_ACC,
+ EVAL_CLASS_ROWS, EVAL_CLASS_CORRECT, EVAL_BATCH_ACC) = (_H['SUG_EVAL_' + _n] for _n in (
+     'MAX_ROWS', 'MAX_CLASSES', 'BATCH_COUNT', 'DATA_TOTAL', 'CORRECT_TOTAL', 'ERROR', 'LOSS_TOTAL', 'CLASS_ACC', 'CLASS_ROWS',
+     'CLASS_CORRECT', 'BATCH_ACC'))
 
 
 def eval_state(cap, device):
@@ -2940,7 +2944,7 @@ def soft_mmd_multi(label_s, label_t, terms, sigmas=SIGMA_LIST, num_class=10):
 
 
 CLASS_MMD = _os.environ.get('SUG_CLASS_MMD', '1') != '0'      # A/B knob: 0 = hard_mmd as boolean indexing + mix_rbf_mmd2 (host waits)
-CLASS_MMD_MAX_ROWS, CLASS_MMD_MAX_CLASSES, CLASS_MMD_MAX_D = 1024, 64, 1 << 20
+CLASS_MMD_MAX_ROWS, CLASS_MMD_MAX_CLASSES, CLASS_MMD_MAX_D = (_H['SUG_CLASS_MMD_MAX_' + _n] for _n in ('ROWS', 'CLASSES', 'D'))
 _CLASS_MMD_MODES = {0: 0, 1: 1, 'hard': 0, 'stable': 1}
 
 
@@ -3299,6 +3303,9 @@ def chamfer_weights(a, b, method):
 # ----------------------------------------------------------------------------- KPConv backbone
 # Packed clouds (rows of all clouds of a level back to back) with int32 device offsets off [B+1]; neighbour tables
 # [Nq, H] int32 whose missing slots hold the shadow index Ns (sug_amd/csrc/kpconv.hip).
+KPCONV_MAX_CLOUD = _H['SUG_KPCONV_MAX_CLOUD']          # the largest `cap` sug_grid_subsample / sug_radius_reverse take
+
+
 def kp_grid_subsample(pts, off, B, cap, dl):
     """Grid subsample of packed clouds pts [N,3] (offsets off, every cloud <= cap points) -> (packed voxel points
     [N,3] of which the first sum-of-counts rows are valid, their offsets [B+1]); nothing is synchronised."""
@@ -3469,8 +3476,8 @@ def seg_mean(x, off):
 
 
 # ----------------------------------------------------------------------------- data pipeline
-PREP_NORMALIZE, PREP_ROTATE_Z, PREP_JITTER, PREP_SHUFFLE = 1, 2, 4, 8            # SUG_PREP_* stage bits
-PREP_MAX_POINTS = 4096
+PREP_NORMALIZE, PREP_ROTATE_Z, PREP_JITTER, PREP_SHUFFLE, PREP_MAX_POINTS = (          # the stage bits and the limit on P
+    _H['SUG_PREP_' + _n] for _n in ('NORMALIZE', 'ROTATE_Z', 'JITTER', 'SHUFFLE', 'MAX_POINTS'))
 
 
 def rotation_matrix(axis, angle):
@@ -3533,7 +3540,7 @@ def prepare_batch(pts, idx, num_points, pre_rotate, aug, *, angles=None, noise=N
 
 
 # ----------------------------------------------------------------------------- sub-domain splitter
-ICP_MAX_POINTS = 1024
+ICP_MAX_POINTS = _H['SUG_ICP_MAX_POINTS']
 
 
 def icp_fitness(src, tgt, max_corr_dist=0.15, max_iteration=30, rel_fitness=1e-6, rel_rmse=1e-6):

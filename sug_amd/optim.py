@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, CONSTANTS
 
 
 class _Bucket:
@@ -174,7 +174,7 @@ class Adam(torch.optim.Adam):
         return None
 
 
-CHAIN_SLOTS, CHAIN_BUCKETS = 2, 8          # SUG_ADAM_CHAIN_SLOTS / SUG_ADAM_CHAIN_BUCKETS of include/sug_amd.h
+CHAIN_SLOTS, CHAIN_BUCKETS = CONSTANTS['SUG_ADAM_CHAIN_SLOTS'], CONSTANTS['SUG_ADAM_CHAIN_BUCKETS']
 
 
 class AdamChain:

@@ -2,7 +2,6 @@
 and state_dict layout, accepts the reference's cfg forms, refuses what its kernels cannot run at construction time, and
 the fused head's C entry points are bound with the header's signatures."""
 import os
-import re
 import types
 
 import numpy as np
@@ -81,20 +80,15 @@ def test_cpu_input_raises_gpu_only_message():
 
 
 def test_ptcls_head_ctypes_signatures_match_header():
-    from sug_amd import _lib
-    src = open(os.path.join(ROOT, 'include', 'sug_amd.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    kinds = {'int': 'i32', 'int64_t': 'i64', 'float': 'f32', 'double': 'f64'}
-    for name in ('sug_ptcls_head_supported', 'sug_ptcls_head_fwd', 'sug_ptcls_head_bwd'):
-        m = re.search(r'\bint\s+' + name + r'\s*\((.*?)\)\s*;', src, flags=re.S)
-        assert m, name
-        want = []
-        for arg in m.group(1).split(','):
-            arg = ' '.join(arg.split())
-            want.append('vp' if '*' in arg else kinds[arg.rsplit(' ', 1)[0].replace('const ', '')])
-        got = [{_lib._vp: 'vp', _lib._i32: 'i32', _lib._i64: 'i64', _lib._f32: 'f32', _lib._f64: 'f64'}[t]
-               for t in _lib.SIGNATURES[name]]
-        assert got == want, name
+    """The binding is derived from the header; these lists are written by hand from the three prototypes."""
+    from sug_amd._lib import SIGNATURES, _vp, _i32
+    assert SIGNATURES['sug_ptcls_head_supported'] == [_i32] * 6                                          # B P K N1 N2 NC
+    assert SIGNATURES['sug_ptcls_head_fwd'] == (
+        [_vp, _i32, _i32, _i32] + [_vp, _vp, _i32] * 3          # points B P K, then (W, b, N) of the three layers
+        + [_vp] * 5)                                            # mean h1 h2 logits stream
+    assert SIGNATURES['sug_ptcls_head_bwd'] == (
+        [_vp] * 4 + [_i32, _i32, _i32] + [_vp, _i32] * 3        # dlogits mean h1 h2, B P K, then (W, N) of the three layers
+        + [_vp] * 3 + [_vp] * 6 + [_vp])                        # dz1 dz2 dpoints, dW1 db1 dW2 db2 dW3 db3, stream
 
 
 def test_ptcls_head_supported_range():

@@ -187,9 +187,9 @@ def test_symbol_declared_and_bound():
     from sug_amd import _lib
     header = open(os.path.join(ROOT, 'include', 'sug_amd.h')).read()
     assert 'int sug_icp_fitness(const float* src, int64_t src_batch_stride, const float* tgt, int B, int Ns, int Nt,' in header
-    assert len(_lib.SIGNATURES['sug_icp_fitness']) == 15
+    assert _lib.DECLARATIONS['sug_icp_fitness'][0] is ctypes.c_int and len(_lib.SIGNATURES['sug_icp_fitness']) == 15
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), 'sug_icp_fitness')
-    assert not any(name.startswith('sug_icp') and name.endswith('workspace') for name in _lib.SIGNATURES)
+    assert not any(name.startswith('sug_icp') and name.endswith('workspace') for name in _lib.DECLARATIONS)
 
 
 def test_host_side_refusals_before_any_launch():
