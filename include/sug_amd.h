@@ -769,6 +769,37 @@ int sug_class_mmd_bwd(const float* z, const float* wt, int m, int D, const int32
                       const int32_t* pos_t, const float* gscale, float* dz, float* dfeat_s, int64_t ldds,
                       float* dfeat_t, int64_t lddt, void* stream);
 
+/* The MMD^2 / variance / ratio estimator (mix_rbf_mmd2_and_ratio, model/mmd.py:263-266, :315-373) and the linear-time
+ * estimators over adjacent rows (linear_mmd2 / poly_mmd2, :211-236).  No host read, no atomics, no memset: capturable,
+ * bit-reproducible.  Limits (checked before any launch): 2 <= m <= SUG_MMD_EST_MAX_ROWS rows per domain,
+ * 1 <= D <= SUG_MMD_EST_MAX_D, 1 <= nsigma <= SUG_MMD_EST_MAX_SIGMAS, poly degree 1 .. SUG_MMD_POLY_MAX_DEGREE.
+ * sug_mmd_ratio_fwd: z = [X ; Y] fp32 [2m, D], row stride ldz.  K, G: fp32 [2m, 2m] scratch (kernel matrix and its
+ *   derivative sums, the pair arithmetic of sug_mmd_rbf); rows: fp64 [SUG_MMD_RATIO_ROW_FIELDS * m] scratch (row sums);
+ *   stats: fp64 [SUG_MMD_RATIO_STATS] scratch; out3 = {loss, mmd2, var_est} fp32 with loss = mmd2 / sqrt(max(var_est, 1e-8)),
+ *   mmd2 biased (biased != 0) or unbiased.  wt_m, wt_v: fp32 [2m, 2m] (d mmd2 / dK . G and d var_est / dK . G, symmetrised,
+ *   zero diagonal) for the backward, or both null.
+ * sug_mmd_ratio_bwd: g3 = the upstream gradients of {loss, mmd2, var_est} (device); dz [2m, D] (row stride lddz) =
+ *   2 sum_j (f_m wt_m + f_v wt_v)[i,j] (z_i - z_j), f_m = g3[1] + g3[0] / sqrt(v_c), f_v = g3[2] - g3[0] mmd2 v_c^(-3/2) / 2
+ *   (that term only while var_est >= 1e-8), v_c = max(var_est, 1e-8), read from out3 on the device.
+ * sug_mmd_adjacent_fwd: x, y fp32 [m, D] (row strides ldx, ldy); mode 0 (linear): value = mean_i <x_i - y_i, x_{i+1} -
+ *   y_{i+1}>; mode 1 (poly): mean_i of kxx^d + kyy^d - kxy^d - kyx^d, k = alpha <., .> + c over rows i, i+1.  part: fp64
+ *   [m - 1] scratch; coef: fp32 [4, m - 1] for the backward (mode 1; may be null); value: fp32 device scalar.
+ * sug_mmd_adjacent_bwd: dx, dy [m, D] written entirely; gscale = upstream gradient (device scalar). */
+#define SUG_MMD_EST_MAX_ROWS 1024
+#define SUG_MMD_EST_MAX_D 1048576
+#define SUG_MMD_EST_MAX_SIGMAS 8
+#define SUG_MMD_POLY_MAX_DEGREE 8
+#define SUG_MMD_RATIO_ROW_FIELDS 9
+#define SUG_MMD_RATIO_STATS 16
+int sug_mmd_ratio_fwd(const float* z, int64_t ldz, int m, int D, const float* neg_gamma, int nsigma, int biased, float* K,
+                      float* G, double* rows, double* stats, float* out3, float* wt_m, float* wt_v, void* stream);
+int sug_mmd_ratio_bwd(const float* z, int64_t ldz, int m, int D, const float* wt_m, const float* wt_v, const float* out3,
+                      const float* g3, float* dz, int64_t lddz, void* stream);
+int sug_mmd_adjacent_fwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int m, int D, int mode, int degree,
+                         double alpha, double c, double* part, float* coef, float* value, void* stream);
+int sug_mmd_adjacent_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int m, int D, int mode, const float* coef,
+                         const float* gscale, float* dx, int64_t lddx, float* dy, int64_t lddy, void* stream);
+
 /* The EdgeConv GEMM operand of a conv_2d weight W [Co, 2C] (get_graph_feature's cat(x_j - x_i, x_i) folded into
  * the weights, model/model_utils.py:188-210): backward = 0: in = W, out [2Co, C] = [W[:, :C] ; W[:, C:] - W[:, :C]];
  * backward = 1: in = d out [2Co, C], out = dW [Co, 2C]. */

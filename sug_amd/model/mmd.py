@@ -3,7 +3,9 @@ reference's model/mmd.py: same function names, arguments and `args` dict keys).
 
 The (2m x 2m) kernel-matrix reduction runs in one HIP kernel (sug_mmd_rbf); the SDA
 weights are computed on the device (the reference round-trips them through the CPU,
-model/mmd.py:138-142, :295)."""
+model/mmd.py:138-142, :295).  The variance / ratio estimator and the linear-time estimators
+(mix_rbf_mmd2_and_ratio, linear_mmd2, poly_mmd2) run in their own kernels (ops.mmd_ratio,
+ops.linear_mmd2 / poly_mmd2)."""
 from copy import deepcopy
 
 import torch
@@ -262,3 +264,74 @@ def mix_rbf_mmd2(X, Y, sigma_list, biased=True, sample_weights=None):
     """model/mmd.py:257-260 with _mmd2, :274-312: biased (the estimator every caller of the reference uses) or unbiased."""
     assert X.size(0) == Y.size(0)
     return ops.mix_rbf_mmd2_rows(torch.cat((X, Y), 0), X.size(0), sample_weights, sigma_list, biased=biased)
+
+
+def linear_mmd2(f_of_X, f_of_Y):
+    """model/mmd.py:211-216: the linear-time estimator with the linear kernel, the mean over adjacent rows of
+    <x_i - y_i, x_{i+1} - y_{i+1}>.  fp32 HIP tensors with at least two rows go through ops.linear_mmd2; anything else
+    (CPU tensors, other dtypes, one row: the mean of nothing, NaN as in the reference) through the composed lines."""
+    if ops.adjacent_mmd_supported(f_of_X, f_of_Y):
+        return ops.linear_mmd2(f_of_X, f_of_Y)
+    delta = f_of_X - f_of_Y
+    return torch.mean((delta[:-1] * delta[1:]).sum(1))
+
+
+def poly_mmd2(f_of_X, f_of_Y, d=2, alpha=1.0, c=2.0):
+    """model/mmd.py:223-236: the linear-time estimator with the kernel (alpha <x, y> + c)^d over adjacent rows.  An integer
+    d in 1..8 on fp32 HIP tensors goes through ops.poly_mmd2; a non-integer or larger d and everything linear_mmd2 lists
+    through the composed lines."""
+    if ops.adjacent_mmd_supported(f_of_X, f_of_Y, d):
+        return ops.poly_mmd2(f_of_X, f_of_Y, d, alpha, c)
+
+    def mean_k(A, B):
+        return torch.mean((alpha * (A[:-1] * B[1:]).sum(1) + c).pow(d))
+
+    return mean_k(f_of_X, f_of_X) + mean_k(f_of_Y, f_of_Y) - mean_k(f_of_X, f_of_Y) - mean_k(f_of_Y, f_of_X)
+
+
+def mix_rbf_mmd2_and_ratio(X, Y, sigma_list, biased=True):
+    """model/mmd.py:263-266 with _mmd2_and_ratio / _mmd2_and_variance (const_diagonal=False), :315-373: (loss, mmd2, var_est)
+    with loss = mmd2 / sqrt(max(var_est, 1e-8)), the t-statistic objective.  fp32 HIP tensors within
+    ops.mmd_ratio_supported's limits go through ops.mmd_ratio; anything else (CPU tensors, other dtypes, and m = 1, where
+    the reference divides by m - 1 = 0 in Python and raises ZeroDivisionError, as these lines do) through the composed lines
+    _mix_rbf_kernel / _mmd2_and_variance below."""
+    assert X.size(0) == Y.size(0)
+    m = X.size(0)
+    if ops.mmd_ratio_supported(X, Y, sigma_list):
+        return ops.mmd_ratio(torch.cat((X, Y), 0), m, sigma_list, biased=biased)
+    mmd2, var_est = _mmd2_and_variance(*_mix_rbf_kernel(X, Y, sigma_list), biased=biased)
+    return mmd2 / torch.sqrt(torch.clamp(var_est, min=min_var_est)), mmd2, var_est
+
+
+def _mix_rbf_kernel(X, Y, sigma_list):
+    """model/mmd.py:239-254: the blocks K_XX, K_XY, K_YY of the Gaussian multi-kernel matrix of [X ; Y], composed."""
+    m = X.size(0)
+    Z = torch.cat((X, Y), 0)
+    ZZT = torch.mm(Z, Z.t())
+    n = torch.diag(ZZT).unsqueeze(1).expand_as(ZZT)
+    e = n - 2 * ZZT + n.t()
+    K = 0.0
+    for sigma in sigma_list:
+        K = K + torch.exp(-(1.0 / (2 * sigma ** 2)) * e)
+    return K[:m, :m], K[:m, m:], K[m:, m:]
+
+
+def _mmd2_and_variance(K_XX, K_XY, K_YY, biased=False):
+    """model/mmd.py:321-373 with const_diagonal=False: (mmd2, var_est) from the three blocks, composed."""
+    m = K_XX.size(0)
+    dX, dY = torch.diag(K_XX), torch.diag(K_YY)
+    a, b = K_XX.sum(dim=1) - dX, K_YY.sum(dim=1) - dY           # Kt_XX e, Kt_YY e (Kt: without the diagonal)
+    c, r = K_XY.sum(dim=0), K_XY.sum(dim=1)                     # K_XY^T e, K_XY e
+    A, B, C = a.sum(), b.sum(), c.sum()
+    FXX, FYY, FXY = (K_XX ** 2).sum() - dX.dot(dX), (K_YY ** 2).sum() - dY.dot(dY), (K_XY ** 2).sum()
+    if biased:
+        mmd2 = (A + dX.sum()) / (m * m) + (B + dY.sum()) / (m * m) - 2.0 * C / (m * m)
+    else:
+        mmd2 = A / (m * (m - 1)) + B / (m * (m - 1)) - 2.0 * C / (m * m)
+    var_est = (2.0 / (m ** 2 * (m - 1.0) ** 2) * (2 * a.dot(a) - FXX + 2 * b.dot(b) - FYY)
+               - (4.0 * m - 6.0) / (m ** 3 * (m - 1.0) ** 3) * (A ** 2 + B ** 2)
+               + 4.0 * (m - 2.0) / (m ** 3 * (m - 1.0) ** 2) * (r.dot(r) + c.dot(c))
+               - 4.0 * (m - 3.0) / (m ** 3 * (m - 1.0) ** 2) * FXY
+               - (8 * m - 12) / (m ** 5 * (m - 1)) * C ** 2
+               + 8.0 / (m ** 3 * (m - 1.0)) * (1.0 / m * (A + B) * C - a.dot(r) - b.dot(c)))
+    return mmd2, var_est

@@ -3045,6 +3045,134 @@ def class_mmd(label_s, feat_s, label_t, feat_t, mode, sigmas=SIGMA_LIST, num_cla
     return _ClassMMD.apply(feat_s, feat_t, label_s, label_t, mode, tuple(sigmas), int(num_class))
 
 
+MMD_EST_MAX_ROWS, MMD_EST_MAX_D, MMD_EST_MAX_SIGMAS, MMD_POLY_MAX_DEGREE = (
+    _H['SUG_MMD_' + _n] for _n in ('EST_MAX_ROWS', 'EST_MAX_D', 'EST_MAX_SIGMAS', 'POLY_MAX_DEGREE'))
+
+
+def _unit_rows(t):
+    """A 2-d fp32 tensor as rows with unit column stride (a column slice stays a view; anything else is copied)."""
+    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+class _MMDRatio(torch.autograd.Function):
+    """(loss, mmd2, var_est) of Z = [X ; Y] in four launches (sug_mmd_ratio_fwd), the gradient of any combination of the
+    three in one (sug_mmd_ratio_bwd): the factors of the two saved weight matrices are formed on the device from the three
+    upstream gradients and the forward's own outputs."""
+
+    @staticmethod
+    def forward(ctx, Z, m, sigmas, biased):
+        _need_gpu(Z)
+        Zc = _unit_rows(Z)
+        D, dev = Zc.shape[1], Z.device
+        M2 = 2 * m
+        ng = _neg_gammas(sigmas, dev)
+        need = ctx.needs_input_grad[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        KG = torch.empty(2, M2, M2, **f32)
+        wt = torch.empty(2, M2, M2, **f32) if need else None
+        rows = torch.empty(_H['SUG_MMD_RATIO_ROW_FIELDS'] * m, dtype=torch.float64, device=dev)
+        stats = torch.empty(_H['SUG_MMD_RATIO_STATS'], dtype=torch.float64, device=dev)
+        out3 = torch.empty(3, **f32)
+        check(lib().sug_mmd_ratio_fwd(_p(Zc), Zc.stride(0), m, D, _p(ng), len(sigmas), int(bool(biased)), _p(KG[0]), _p(KG[1]),
+                                      _p(rows), _p(stats), _p(out3), _p(wt[0]) if need else None, _p(wt[1]) if need else None,
+                                      _st()), 'sug_mmd_ratio_fwd')
+        if need:
+            ctx.save_for_backward(Zc, wt, out3)
+        return out3[0], out3[1], out3[2]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mmd2, g_var):
+        Z, wt, out3 = ctx.saved_tensors
+        M2, D = Z.shape
+        g3 = torch.stack((g_loss.detach().reshape(()), g_mmd2.detach().reshape(()), g_var.detach().reshape(()))).to(
+            device=Z.device, dtype=torch.float32)
+        dZ = torch.empty(M2, D, dtype=torch.float32, device=Z.device)
+        check(lib().sug_mmd_ratio_bwd(_p(Z), Z.stride(0), M2 // 2, D, _p(wt[0]), _p(wt[1]), _p(out3), _p(g3), _p(dZ), D, _st()),
+              'sug_mmd_ratio_bwd')
+        return dZ, None, None, None
+
+
+def _fp32_rows_pair(X, Y):
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 for t in (X, Y)) \
+        and X.shape == Y.shape and 2 <= X.shape[0] <= MMD_EST_MAX_ROWS and 1 <= X.shape[1] <= MMD_EST_MAX_D
+
+
+def mmd_ratio_supported(X, Y, sigmas=SIGMA_LIST):
+    """What mmd_ratio takes of the two domains' blocks (and sug_mmd_ratio_* would otherwise refuse): fp32 [m, D] of one
+    shape on the HIP device, 2 <= m <= 1024, 1 <= D <= 2^20, 1 to 8 sigmas."""
+    return _fp32_rows_pair(X, Y) and 1 <= len(sigmas) <= MMD_EST_MAX_SIGMAS
+
+
+def mmd_ratio(Z, m, sigmas=SIGMA_LIST, biased=True):
+    """Z = cat(X, Y) [2m, D] -> (loss, mmd2, var_est), 0-d fp32 tensors, differentiable in Z: the MMD^2 of the Gaussian
+    multi-kernel matrix (biased or unbiased), the estimate of its variance, and mmd2 / sqrt(max(var_est, 1e-8))
+    (_mmd2_and_ratio, model/mmd.py:315-373).  The row and scalar sums are folded in fp64 in a fixed order."""
+    if Z.dtype != torch.float32 or Z.dim() != 2 or Z.shape[0] != 2 * m:
+        raise RuntimeError('sug_amd.ops.mmd_ratio: Z = cat(X, Y), fp32 [2m, D]')
+    if not 2 <= m <= MMD_EST_MAX_ROWS:
+        raise RuntimeError('sug_amd.ops.mmd_ratio: m=%d rows per domain (2..%d)' % (m, MMD_EST_MAX_ROWS))
+    if not 1 <= len(sigmas) <= MMD_EST_MAX_SIGMAS:
+        raise RuntimeError('sug_amd.ops.mmd_ratio: 1 to %d sigmas (got %d)' % (MMD_EST_MAX_SIGMAS, len(sigmas)))
+    return _MMDRatio.apply(Z, int(m), tuple(sigmas), bool(biased))
+
+
+class _AdjacentMMD(torch.autograd.Function):
+    """linear_mmd2 (mode 0) / poly_mmd2 (mode 1) over the m - 1 adjacent row pairs (sug_mmd_adjacent_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, mode, degree, alpha, c):
+        _need_gpu(X, Y)
+        Xc, Yc = _unit_rows(X), _unit_rows(Y)
+        m, D = Xc.shape
+        dev = X.device
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        part = torch.empty(m - 1, dtype=torch.float64, device=dev)
+        coef = torch.empty(4, m - 1, dtype=torch.float32, device=dev) if (need and mode == 1) else None
+        val = torch.empty((), dtype=torch.float32, device=dev)
+        check(lib().sug_mmd_adjacent_fwd(_p(Xc), Xc.stride(0), _p(Yc), Yc.stride(0), m, D, mode, degree, alpha, c, _p(part),
+                                         _p(coef), _p(val), _st()), 'sug_mmd_adjacent_fwd')
+        if need:
+            ctx.mode = mode
+            ctx.save_for_backward(Xc, Yc, coef)
+        return val
+
+    @staticmethod
+    def backward(ctx, g):
+        X, Y, coef = ctx.saved_tensors
+        m, D = X.shape
+        gs = g.detach().to(device=X.device, dtype=torch.float32).reshape(1)
+        d = torch.empty(2, m, D, dtype=torch.float32, device=X.device)
+        check(lib().sug_mmd_adjacent_bwd(_p(X), X.stride(0), _p(Y), Y.stride(0), m, D, ctx.mode, _p(coef), _p(gs), _p(d[0]), D,
+                                         _p(d[1]), D, _st()), 'sug_mmd_adjacent_bwd')
+        return (d[0] if ctx.needs_input_grad[0] else None, d[1] if ctx.needs_input_grad[1] else None, None, None, None, None)
+
+
+def adjacent_mmd_supported(X, Y, d=1):
+    """What linear_mmd2 / poly_mmd2 take: two fp32 [m, D] blocks of one shape on the HIP device, 2 <= m <= 1024,
+    1 <= D <= 2^20, and an integer degree in 1..8."""
+    return _fp32_rows_pair(X, Y) and not isinstance(d, bool) and isinstance(d, (int, float)) and float(d).is_integer() \
+        and 1 <= int(d) <= MMD_POLY_MAX_DEGREE
+
+
+def _adjacent(name, X, Y, mode, d, alpha, c):
+    if not adjacent_mmd_supported(X, Y, d):
+        _need_gpu(*(t for t in (X, Y) if isinstance(t, torch.Tensor)))
+        raise RuntimeError('sug_amd.ops.%s: two fp32 [m, D] blocks of one shape, 2 <= m <= %d, 1 <= D <= %d, an integer degree '
+                           'in 1..%d' % (name, MMD_EST_MAX_ROWS, MMD_EST_MAX_D, MMD_POLY_MAX_DEGREE))
+    return _AdjacentMMD.apply(X, Y, mode, int(d), float(alpha), float(c))
+
+
+def linear_mmd2(X, Y):
+    """mean_i <x_i - y_i, x_{i+1} - y_{i+1}> (model/mmd.py:211-216): the linear-time MMD^2 with the linear kernel, 0-d fp32,
+    differentiable in both blocks."""
+    return _adjacent('linear_mmd2', X, Y, 0, 1, 1.0, 0.0)
+
+
+def poly_mmd2(X, Y, d=2, alpha=1.0, c=2.0):
+    """The linear-time MMD^2 with the kernel (alpha <x, y> + c)^d over adjacent rows (model/mmd.py:223-236)."""
+    return _adjacent('poly_mmd2', X, Y, 1, d, alpha, c)
+
+
 def colsum(x2, sign=1.0):
     """fp32 column sums [C] of a [R, C] fp32 / fp16 matrix (sug_colsum: no memset, fixed order)."""
     _need_gpu(x2)
