@@ -989,6 +989,41 @@ int sug_seg_max_pool_bwd(const float* g, const int32_t* arg, const int32_t* rev_
 /* y [B, C] = per-cloud mean of x [N, C]; dx [N, C] = g[b] / N_b */
 int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C, float* y, void* stream);
 int sug_seg_mean_bwd(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream);
+/* Capacity forms (a graph-capturable pyramid): level l owns a buffer of a static number of rows C_l; rows [0, off[B])
+ * are valid, rows [off[B], C_l) are dead and exactly zero in every level tensor; the shadow index of a table is the
+ * capacity of its support level; a dead query's table row is all shadow, a dead support's reverse list is empty.  Every
+ * function reads the valid counts from device memory, never reads a dead input row, and writes zeros to the dead rows of
+ * its outputs.  sug_kpconv_bwd, sug_seg_max_pool_fwd and sug_seg_max_pool_bwd serve this layout as they are (Nq / Ns =
+ * the capacities).
+ *
+ * sug_grid_subsample_cap: sug_grid_subsample into out [C, 3], C <= B*cap.  out_off is clamped to C (the rows past C are
+ * dropped), the dead rows of out are zeroed, and the unclamped total is folded into record (int32
+ * [SUG_KPCONV_RECORD_INTS], zeroed by the caller once): record[level] = max(record[level], total), record[4] = forwards in
+ * which any level overflowed (counted once per forward; the level-0 call opens a forward), record[5] = scratch. */
+#define SUG_KPCONV_RECORD_INTS 8
+int sug_grid_subsample_cap(const float* pts, const int32_t* off, int B, int cap, float dl, int C, int level, float* out_pad,
+                           int32_t* cnt, float* out, int32_t* out_off, int32_t* record, void* stream);
+/* out [Cq, limit]; a dead query (row >= qoff[B]) gets an all-shadow row, the shadow index is Cs */
+int sug_radius_neighbors_cap(const float* q, const int32_t* qoff, int Cq, const float* s, const int32_t* soff, int Cs, int B,
+                             float radius, int limit, int32_t* out, void* stream);
+/* rev_be [Cs, 2]: (0, 0) for the dead supports [soff[B], Cs); cap >= every cloud's support count (the level-0 cloud size) */
+int sug_radius_reverse_cap(const int32_t* nbr, const int32_t* qoff, const int32_t* soff, int B, int H, int Cs, int cap,
+                           int32_t* rev_be, int32_t* rev_ent, void* stream);
+/* nq_valid: device pointer to the number of valid queries (qoff + B); dead rows: wf = 0, w = 0, cnt = 1 */
+int sug_kpconv_fwd_cap(const float* q, const float* s, const int32_t* nbr, const int32_t* nq_valid, int Cq, int H, int Cs,
+                       const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w, float* cnt,
+                       void* stream);
+/* x / y / dx / dsc [N, C], N the capacity; an empty cloud: mean = rstd = 0, nothing normalised */
+int sug_seg_instnorm_fwd_cap(const float* x, const int32_t* off, int B, int N, int C, float eps, int mode, const float* sc,
+                             float* y, float* mean, float* rstd, void* stream);
+int sug_seg_instnorm_bwd_cap(const float* g, const float* y, const float* x, const float* mean, const float* rstd,
+                             const int32_t* off, int B, int N, int C, int mode, float* dx, float* dsc, void* stream);
+/* an empty cloud: y row = 0; dx rows >= off[B] = 0 */
+int sug_seg_mean_fwd_cap(const float* x, const int32_t* off, int B, int C, float* y, void* stream);
+int sug_seg_mean_bwd_cap(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream);
+/* sample_tensor_slices (model/KPConv_blocks.py:159-176) from device offsets: out [B, S, D], out[b, j] = x[off[b] + i],
+ * i = j * (n / S) for n = off[b+1] - off[b] >= S, j mod n below that, zeros for n = 0.  Forward only. */
+int sug_kp_sample_rows(const float* x, const int32_t* off, int B, int S, int D, float* out, void* stream);
 
 /* ---- Point Transformer classifier head (PointTransformerCls.fc2 on points.mean(1), model/Ptran_model.py:104-117) ----
  * logits [B, NC] = L3(relu(L2(relu(L1(mean_P(points)))))), points [B, P, K] dense, Li(x) = x . Wi^T + bi with W1 [N1, K],

@@ -361,8 +361,10 @@ class CallGraphs:
 
 def manager_for(model):
     """The model's call-graph manager (created on first use), or None when call graphs are switched off or the encoder's
-    sizes depend on the data (KPConv_g: graph_capturable = False), so that the call runs eagerly."""
-    if not ENABLED or not getattr(getattr(model, 'g', None), 'graph_capturable', True):
+    sizes depend on the data (KPConv_g: graph_capturable = False), so that the call runs eagerly.  KPConv_g with level caps
+    is declined as well: per-call replay is not tested on the capacity form (SUGStep replays the whole step instead)."""
+    g = getattr(model, 'g', None)
+    if not ENABLED or not getattr(g, 'graph_capturable', True) or hasattr(g, 'set_level_caps'):
         return None
     mgr = model.__dict__.get('_call_graph_mgr')
     if mgr is None:

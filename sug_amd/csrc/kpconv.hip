@@ -6,6 +6,24 @@
 // support indices; a missing slot holds the shadow index Ns (the number of supports), as the reference pads them.
 // Every reduction has one fixed order, no float atomics: the backward scatters go through the sorted reverse lists of
 // sug_radius_reverse, so the backbone is reproducible bit for bit from run to run.
+//
+// CAPACITY LAYOUT (the sug_*_cap entry points).  Level l owns a buffer of a static number of rows
+// C_l (C_0 = B*N, C_l = min(C_{l-1}, 64*ceil(B*caps[l-1]/64))); rows [0, off[B]) are valid, rows [off[B], C_l) are dead.
+// The shadow index of a table is the CAPACITY of its support level, a constant of the launch sequence.  Invariants:
+//   1. every dead row of every level tensor is exactly zero: coordinates, activations, and the gradients of both;
+//   2. every slot of a dead query's table row is the shadow index;
+//   3. the reverse list of a dead support is empty (lo == hi);
+//   4. a kernel of this file never reads a dead row of an input, and writes zeros to the dead rows of each output,
+//      forward and backward.  The library GEMMs run on all C_l rows; their weight gradients stay right because the
+//      dead rows of both operands are zero (a NaN in a dead row would poison dW);
+//   5. no buffer, no grid and no host branch depends on a value in device memory, and nothing is copied to the host.
+// The kernels take the valid count from device memory (off[B], by pointer) and the capacity by value; the kernel bodies
+// are shared with the exact-size path (template<bool CAPS>).  sug_kpconv_bwd, sug_seg_max_pool_fwd and
+// sug_seg_max_pool_bwd hold under 2. and 3. as they are (Ns / Nq = the capacities): a dead support's empty list sums
+// to 0, a dead query's all-shadow row reads only the zero shadow, so they have no capacity twin.
+// Overflow (a level total above C_l): the pack step clamps the offsets to C_l and drops the rows past it -- the tail of
+// the last clouds, a cloud may become empty (an empty cloud normalises nothing; its mean row and pooled feature are 0).
+// The unclamped total is folded into a small device record (sug_grid_subsample_cap).
 #include "common.h"
 
 namespace {
@@ -127,17 +145,60 @@ __global__ void pack_kernel(const float* __restrict__ pad, int cap, const int32_
   }
 }
 
+// Capacity form of pack_kernel: out has C rows.  Offsets are clamped to C (rows past C are dropped), the dead rows
+// [min(total, C), C) are zero-filled, and the unclamped total is folded into rec (int32 [SUG_KPCONV_RECORD_INTS]):
+// rec[level] = max(rec[level], total); rec[4] counts the forwards with an overflow at any level (rec[5] = this forward
+// has been counted; cleared by the level-0 call) -- one lane, plain stores.  Grid covers max(B*cap, C) threads.
+__global__ void pack_cap_kernel(const float* __restrict__ pad, int cap, const int32_t* __restrict__ cnt, int B, int C,
+                                float* __restrict__ out, int32_t* __restrict__ out_off, int32_t* __restrict__ rec,
+                                int level) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < B * cap) {
+    const int b = t / cap, i = t - b * cap;
+    if (i < cnt[b]) {
+      int o = 0;
+      for (int j = 0; j < b; ++j) o += cnt[j];
+      if (o + i < C)
+        for (int a = 0; a < 3; ++a) out[(size_t)(o + i) * 3 + a] = pad[(size_t)t * 3 + a];
+    }
+  }
+  if (t < C) {
+    int total = 0;
+    for (int j = 0; j < B; ++j) total += cnt[j];
+    if (t >= total)
+      for (int a = 0; a < 3; ++a) out[(size_t)t * 3 + a] = 0.f;
+  }
+  if (t == 0) {
+    int o = 0;
+    out_off[0] = 0;
+    for (int j = 0; j < B; ++j) out_off[j + 1] = min(o += cnt[j], C);
+    if (o > rec[level]) rec[level] = o;
+    int counted = level == 0 ? 0 : rec[5];
+    if (o > C && !counted) {
+      rec[4] += 1;
+      counted = 1;
+    }
+    rec[5] = counted;
+  }
+}
+
 // One query per thread: the first `limit` supports of its cloud, in support order, with d^2 < r^2; shadow-padded.
+// CAPS: Nq / Ns are capacities; a dead query (i >= qoff[B]) gets an all-shadow row and reads nothing.
+template <bool CAPS>
 __global__ void radius_kernel(const float* __restrict__ q, const int32_t* __restrict__ qoff, const float* __restrict__ s,
                               const int32_t* __restrict__ soff, int B, int Nq, int Ns, float r2, int limit,
                               int32_t* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Nq) return;
+  int32_t* o = out + (size_t)i * limit;
+  int m = 0;
+  if (CAPS && i >= qoff[B]) {
+    for (; m < limit; ++m) o[m] = Ns;
+    return;
+  }
   const int b = cloud_of(qoff, B, i);
   const int s0 = soff[b], s1 = min(soff[b + 1], Ns);
   const float qx = q[(size_t)i * 3], qy = q[(size_t)i * 3 + 1], qz = q[(size_t)i * 3 + 2];
-  int32_t* o = out + (size_t)i * limit;
-  int m = 0;
   for (int j = s0; j < s1 && m < limit; ++j) {
     const float dx = __fsub_rn(s[(size_t)j * 3], qx), dy = __fsub_rn(s[(size_t)j * 3 + 1], qy),
                 dz = __fsub_rn(s[(size_t)j * 3 + 2], qz);
@@ -149,6 +210,8 @@ __global__ void radius_kernel(const float* __restrict__ q, const int32_t* __rest
 
 // One cloud per workgroup: the entries e = q*H + h of the cloud's queries that name support s, ascending, at
 // rev_ent[rev_be[s][0] .. rev_be[s][1]) (inside the cloud's own range [q0*H, q1*H) of rev_ent).
+// CAPS: one more workgroup (blockIdx.x == B) gives the dead supports [soff[B], Ns) their empty lists.
+template <bool CAPS>
 __global__ void __launch_bounds__(SUB_BLOCK) radius_reverse_kernel(const int32_t* __restrict__ nbr,
                                                                    const int32_t* __restrict__ qoff,
                                                                    const int32_t* __restrict__ soff, int H, int Ns,
@@ -159,6 +222,10 @@ __global__ void __launch_bounds__(SUB_BLOCK) radius_reverse_kernel(const int32_t
   int* cur = cnt + cap;
   int* part = cur + cap;
   const int b = blockIdx.x;
+  if (CAPS && b == (int)gridDim.x - 1) {      // uniform: before the first barrier
+    for (int i = soff[b] + threadIdx.x; i < Ns; i += SUB_BLOCK) rev_be[(size_t)i * 2] = rev_be[(size_t)i * 2 + 1] = 0;
+    return;
+  }
   const int q0 = qoff[b], q1 = qoff[b + 1], s0 = soff[b], ns = soff[b + 1] - s0;
   if (ns > cap) return;
   const int e0 = q0 * H, e1 = q1 * H;
@@ -202,8 +269,11 @@ __global__ void __launch_bounds__(SUB_BLOCK) radius_reverse_kernel(const int32_t
 // w[k,h] = max(0, 1 - |(s_h - q) - kp_k| / extent) into LDS and out to w_out [Nq, H, K]; the positive-sum flags of the
 // neighbour rows.  Phase 2 (threads over QB x Cin): wf[q, k, c] = sum_h w[k,h] x[s_h, c], divided by
 // max(1, #positive rows); written as [Nq, K*Cin] for the GEMM against W viewed as [K*Cin, Cout].
+// CAPS: Nq / Ns are capacities, *nq_valid the valid queries; dead queries get zero wf / w rows and cnt 1.
+template <bool CAPS>
 __global__ void __launch_bounds__(256) kpconv_fwd_kernel(const float* __restrict__ q, const float* __restrict__ s,
-                                                         const int32_t* __restrict__ nbr, int Nq, int H, int Ns,
+                                                         const int32_t* __restrict__ nbr,
+                                                         const int32_t* __restrict__ nq_valid, int Nq, int H, int Ns,
                                                          const float* __restrict__ kp, int K, float extent,
                                                          const float* __restrict__ x, int Cin, float* __restrict__ wf,
                                                          float* __restrict__ w_out, float* __restrict__ cnt_out) {
@@ -212,10 +282,18 @@ __global__ void __launch_bounds__(256) kpconv_fwd_kernel(const float* __restrict
   __shared__ int pos[KP_QB][KP_MAX_H];
   __shared__ float cnt[KP_QB];
   const int qb0 = blockIdx.x * KP_QB;
+  const int nv = CAPS ? min(*nq_valid, Nq) : Nq;
+  if (CAPS && qb0 >= nv) {      // a wholly dead tile (blockIdx and a uniform load only): zeros, before the first barrier
+    const int rows = min(KP_QB, Nq - qb0);
+    for (int t = threadIdx.x; t < rows * K * Cin; t += blockDim.x) wf[(size_t)qb0 * K * Cin + t] = 0.f;
+    for (int t = threadIdx.x; t < rows * H * K; t += blockDim.x) w_out[(size_t)qb0 * H * K + t] = 0.f;
+    if ((int)threadIdx.x < rows) cnt_out[qb0 + threadIdx.x] = 1.f;
+    return;
+  }
   for (int t = threadIdx.x; t < KP_QB * H; t += blockDim.x) {
     const int qi = t / H, h = t - qi * H, qq = qb0 + qi;
     int sid = -1, p = 0;
-    if (qq < Nq) {
+    if (qq < nv) {
       const int sv = nbr[(size_t)qq * H + h];
       if (sv >= 0 && sv < Ns) sid = sv;
     }
@@ -301,14 +379,26 @@ __device__ __forceinline__ double seg_combine(double v, double* red) {
   return r;
 }
 
+// CAPS (x / y have N rows, N a capacity): workgroup blockIdx.x == B zero-fills the dead rows [off[B], N) of y; an empty
+// cloud writes mean = rstd = 0 and normalises nothing.  Both leave before the first barrier, on uniform values only.
+template <bool CAPS>
 __global__ void __launch_bounds__(256) seg_instnorm_fwd_kernel(const float* __restrict__ x, const int32_t* __restrict__ off,
-                                                               int C, float eps, int mode, const float* __restrict__ sc,
-                                                               float* __restrict__ y, float* __restrict__ mean_out,
-                                                               float* __restrict__ rstd_out) {
+                                                               int N, int C, float eps, int mode,
+                                                               const float* __restrict__ sc, float* __restrict__ y,
+                                                               float* __restrict__ mean_out, float* __restrict__ rstd_out) {
   __shared__ double red[256];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), l = threadIdx.x >> 6;
   const bool on = c < C;
+  if (CAPS && b == (int)gridDim.x - 1) {
+    if (on)
+      for (int r = off[b] + l; r < N; r += 4) y[(size_t)r * C + c] = 0.f;
+    return;
+  }
   const int r0 = off[b], r1 = off[b + 1];
+  if (CAPS && r1 <= r0) {
+    if (on && l == 0) mean_out[(size_t)b * C + c] = rstd_out[(size_t)b * C + c] = 0.f;
+    return;
+  }
   const double n = (double)(r1 - r0);
   double s1 = 0.0;
   if (on)
@@ -337,15 +427,25 @@ __global__ void __launch_bounds__(256) seg_instnorm_fwd_kernel(const float* __re
 }
 
 // gp = g * act'(out); dsc = gp (mode 2); dx = rstd (gp - mean(gp) - xhat mean(gp xhat)), xhat = (x - mean) rstd
+template <bool CAPS>
 __global__ void __launch_bounds__(256) seg_instnorm_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y,
                                                                const float* __restrict__ x, const float* __restrict__ mean_in,
                                                                const float* __restrict__ rstd_in,
-                                                               const int32_t* __restrict__ off, int C, int mode,
+                                                               const int32_t* __restrict__ off, int N, int C, int mode,
                                                                float* __restrict__ dx, float* __restrict__ dsc) {
   __shared__ double red[256];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), l = threadIdx.x >> 6;
   const bool on = c < C;
+  if (CAPS && b == (int)gridDim.x - 1) {      // the dead rows of dx (and dsc): zeros
+    if (on)
+      for (int r = off[b] + l; r < N; r += 4) {
+        dx[(size_t)r * C + c] = 0.f;
+        if (mode == 2) dsc[(size_t)r * C + c] = 0.f;
+      }
+    return;
+  }
   const int r0 = off[b], r1 = off[b + 1];
+  if (CAPS && r1 <= r0) return;               // an empty cloud has no rows to write
   const double n = (double)(r1 - r0);
   const float m = on ? mean_in[(size_t)b * C + c] : 0.f, rs = on ? rstd_in[(size_t)b * C + c] : 0.f;
   double s1 = 0.0, s2 = 0.0;
@@ -407,11 +507,16 @@ __global__ void max_pool_bwd_kernel(const float* __restrict__ g, const int32_t* 
   dx[t] = acc;
 }
 
+template <bool CAPS>
 __global__ void __launch_bounds__(256) seg_mean_fwd_kernel(const float* __restrict__ x, const int32_t* __restrict__ off,
                                                            int C, float* __restrict__ y) {
   __shared__ double red[256];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), l = threadIdx.x >> 6;
   const int r0 = off[b], r1 = off[b + 1];
+  if (CAPS && r1 <= r0) {                     // an empty cloud's pooled row is 0 (uniform: before the barrier)
+    if (c < C && l == 0) y[(size_t)b * C + c] = 0.f;
+    return;
+  }
   double s = 0.0;
   if (c < C)
     for (int r = r0 + l; r < r1; r += 4) s += (double)x[(size_t)r * C + c];
@@ -419,13 +524,34 @@ __global__ void __launch_bounds__(256) seg_mean_fwd_kernel(const float* __restri
   if (c < C && l == 0) y[(size_t)b * C + c] = (float)(s / (double)(r1 - r0));
 }
 
+template <bool CAPS>
 __global__ void seg_mean_bwd_kernel(const float* __restrict__ g, const int32_t* __restrict__ off, int B, int N, int C,
                                     float* __restrict__ dx) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (int64_t)N * C) return;
   const int r = (int)(t / C), c = (int)(t - (int64_t)r * C);
+  if (CAPS && r >= off[B]) {                  // a dead row
+    dx[t] = 0.f;
+    return;
+  }
   const int b = cloud_of(off, B, r);
   dx[t] = __fdiv_rn(g[(size_t)b * C + c], (float)(off[b + 1] - off[b]));
+}
+
+// sample_tensor_slices from device offsets: out[b, j, :] = x[off[b] + idx(j, n), :], n = off[b+1] - off[b],
+// idx = j * (n / S) for n >= S and j mod n below that; zeros for n == 0.  One thread per output element.
+__global__ void sample_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ off, int B, int S, int D,
+                                   float* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * S * D) return;
+  const int d = (int)(t % D), j = (int)((t / D) % S), b = (int)(t / ((int64_t)D * S));
+  const int r0 = off[b], n = off[b + 1] - r0;
+  float v = 0.f;
+  if (n > 0) {
+    const int idx = n >= S ? j * (n / S) : j % n;
+    v = x[(size_t)(r0 + idx) * D + d];
+  }
+  out[t] = v;
 }
 
 }  // namespace
@@ -455,7 +581,7 @@ extern "C" int sug_radius_neighbors(const float* q, const int32_t* qoff, int Nq,
   SUG_REQUIRE(q && qoff && s && soff && out, "sug_radius_neighbors: null pointer");
   SUG_REQUIRE(B > 0 && Nq > 0 && Ns > 0 && limit > 0 && limit <= KP_MAX_H, "sug_radius_neighbors: bad shape");
   const float r2 = radius * radius;       // fp32(r) * fp32(r), rounded once
-  hipLaunchKernelGGL(radius_kernel, dim3(sug_divup(Nq, 256)), dim3(256), 0, (hipStream_t)stream, q, qoff, s, soff, B, Nq,
+  hipLaunchKernelGGL(radius_kernel<false>, dim3(sug_divup(Nq, 256)), dim3(256), 0, (hipStream_t)stream, q, qoff, s, soff, B, Nq,
                      Ns, r2, limit, out);
   SUG_LAUNCH_CHECK("sug_radius_neighbors");
   return SUG_OK;
@@ -467,7 +593,7 @@ extern "C" int sug_radius_reverse(const int32_t* nbr, const int32_t* qoff, const
   SUG_REQUIRE(B > 0 && H > 0 && Ns > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD,
               "sug_radius_reverse: bad shape (cap %d, at most %d supports per cloud)", cap, SUG_KPCONV_MAX_CLOUD);
   const int sh = (2 * cap + SUB_BLOCK) * (int)sizeof(int);
-  hipLaunchKernelGGL(radius_reverse_kernel, dim3(B), dim3(SUB_BLOCK), sh, (hipStream_t)stream, nbr, qoff, soff, H, Ns,
+  hipLaunchKernelGGL(radius_reverse_kernel<false>, dim3(B), dim3(SUB_BLOCK), sh, (hipStream_t)stream, nbr, qoff, soff, H, Ns,
                      cap, rev_be, rev_ent);
   SUG_LAUNCH_CHECK("sug_radius_reverse");
   return SUG_OK;
@@ -479,8 +605,8 @@ extern "C" int sug_kpconv_fwd(const float* q, const float* s, const int32_t* nbr
   SUG_REQUIRE(q && s && nbr && kp && x && wf && w && cnt, "sug_kpconv_fwd: null pointer");
   SUG_REQUIRE(Nq > 0 && Ns > 0 && Cin > 0 && H > 0 && H <= KP_MAX_H && K > 0 && K <= KP_MAX_K && extent > 0.f,
               "sug_kpconv_fwd: bad shape (H %d <= %d, K %d <= %d)", H, KP_MAX_H, K, KP_MAX_K);
-  hipLaunchKernelGGL(kpconv_fwd_kernel, dim3(sug_divup(Nq, KP_QB)), dim3(256), 0, (hipStream_t)stream, q, s, nbr, Nq, H,
-                     Ns, kp, K, extent, x, Cin, wf, w, cnt);
+  hipLaunchKernelGGL(kpconv_fwd_kernel<false>, dim3(sug_divup(Nq, KP_QB)), dim3(256), 0, (hipStream_t)stream, q, s, nbr,
+                     (const int32_t*)nullptr, Nq, H, Ns, kp, K, extent, x, Cin, wf, w, cnt);
   SUG_LAUNCH_CHECK("sug_kpconv_fwd");
   return SUG_OK;
 }
@@ -499,8 +625,8 @@ extern "C" int sug_seg_instnorm_fwd(const float* x, const int32_t* off, int B, i
                                     const float* sc, float* y, float* mean, float* rstd, void* stream) {
   SUG_REQUIRE(x && off && y && mean && rstd && (mode != 2 || sc), "sug_seg_instnorm_fwd: null pointer");
   SUG_REQUIRE(B > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_fwd: bad shape / mode");
-  hipLaunchKernelGGL(seg_instnorm_fwd_kernel, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, eps,
-                     mode, sc, y, mean, rstd);
+  hipLaunchKernelGGL(seg_instnorm_fwd_kernel<false>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, 0,
+                     C, eps, mode, sc, y, mean, rstd);
   SUG_LAUNCH_CHECK("sug_seg_instnorm_fwd");
   return SUG_OK;
 }
@@ -509,8 +635,8 @@ extern "C" int sug_seg_instnorm_bwd(const float* g, const float* y, const float*
                                     const int32_t* off, int B, int C, int mode, float* dx, float* dsc, void* stream) {
   SUG_REQUIRE(g && y && x && mean && rstd && off && dx && (mode != 2 || dsc), "sug_seg_instnorm_bwd: null pointer");
   SUG_REQUIRE(B > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_bwd: bad shape / mode");
-  hipLaunchKernelGGL(seg_instnorm_bwd_kernel, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, g, y, x, mean,
-                     rstd, off, C, mode, dx, dsc);
+  hipLaunchKernelGGL(seg_instnorm_bwd_kernel<false>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, g, y, x,
+                     mean, rstd, off, 0, C, mode, dx, dsc);
   SUG_LAUNCH_CHECK("sug_seg_instnorm_bwd");
   return SUG_OK;
 }
@@ -538,7 +664,7 @@ extern "C" int sug_seg_max_pool_bwd(const float* g, const int32_t* arg, const in
 extern "C" int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C, float* y, void* stream) {
   SUG_REQUIRE(x && off && y, "sug_seg_mean_fwd: null pointer");
   SUG_REQUIRE(B > 0 && C > 0, "sug_seg_mean_fwd: bad shape");
-  hipLaunchKernelGGL(seg_mean_fwd_kernel, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, y);
+  hipLaunchKernelGGL(seg_mean_fwd_kernel<false>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, y);
   SUG_LAUNCH_CHECK("sug_seg_mean_fwd");
   return SUG_OK;
 }
@@ -546,8 +672,114 @@ extern "C" int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C
 extern "C" int sug_seg_mean_bwd(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream) {
   SUG_REQUIRE(g && off && dx, "sug_seg_mean_bwd: null pointer");
   SUG_REQUIRE(B > 0 && N > 0 && C > 0, "sug_seg_mean_bwd: bad shape");
-  hipLaunchKernelGGL(seg_mean_bwd_kernel, dim3(sug_divup((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, g, off, B,
+  hipLaunchKernelGGL(seg_mean_bwd_kernel<false>, dim3(sug_divup((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, g, off, B,
                      N, C, dx);
   SUG_LAUNCH_CHECK("sug_seg_mean_bwd");
+  return SUG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- capacity forms
+extern "C" int sug_grid_subsample_cap(const float* pts, const int32_t* off, int B, int cap, float dl, int C, int level,
+                                      float* out_pad, int32_t* cnt, float* out, int32_t* out_off, int32_t* record,
+                                      void* stream) {
+  SUG_REQUIRE(pts && off && out_pad && cnt && out && out_off && record, "sug_grid_subsample_cap: null pointer");
+  SUG_REQUIRE(B > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD, "sug_grid_subsample_cap: cap %d outside (0, %d]", cap,
+              SUG_KPCONV_MAX_CLOUD);
+  SUG_REQUIRE(C > 0 && (int64_t)C <= (int64_t)B * cap && level >= 0 && level < 4,
+              "sug_grid_subsample_cap: capacity %d outside (0, B*cap] or level %d outside [0, 4)", C, level);
+  SUG_REQUIRE(dl > 0.f, "sug_grid_subsample_cap: dl must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  const int sh = (5 * cap + SUB_BLOCK) * (int)sizeof(int);
+  static SugLdsOptIn note;
+  if (int rc = sug_allow_dynamic_lds(note, &grid_subsample_kernel, (5 * SUG_KPCONV_MAX_CLOUD + SUB_BLOCK) * 4,
+                                     "sug_grid_subsample_cap"))
+    return rc;
+  hipLaunchKernelGGL(grid_subsample_kernel, dim3(B), dim3(SUB_BLOCK), sh, st, pts, off, dl, cap, out_pad, cnt);
+  SUG_LAUNCH_CHECK("sug_grid_subsample_cap");
+  hipLaunchKernelGGL(pack_cap_kernel, dim3(sug_divup((int64_t)B * cap, 256)), dim3(256), 0, st, out_pad, cap, cnt, B, C, out,
+                     out_off, record, level);
+  SUG_LAUNCH_CHECK("sug_grid_subsample_cap/pack");
+  return SUG_OK;
+}
+
+extern "C" int sug_radius_neighbors_cap(const float* q, const int32_t* qoff, int Cq, const float* s, const int32_t* soff,
+                                        int Cs, int B, float radius, int limit, int32_t* out, void* stream) {
+  SUG_REQUIRE(q && qoff && s && soff && out, "sug_radius_neighbors_cap: null pointer");
+  SUG_REQUIRE(B > 0 && Cq > 0 && Cs > 0 && limit > 0 && limit <= KP_MAX_H, "sug_radius_neighbors_cap: bad shape");
+  const float r2 = radius * radius;
+  hipLaunchKernelGGL(radius_kernel<true>, dim3(sug_divup(Cq, 256)), dim3(256), 0, (hipStream_t)stream, q, qoff, s, soff, B,
+                     Cq, Cs, r2, limit, out);
+  SUG_LAUNCH_CHECK("sug_radius_neighbors_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_radius_reverse_cap(const int32_t* nbr, const int32_t* qoff, const int32_t* soff, int B, int H, int Cs,
+                                      int cap, int32_t* rev_be, int32_t* rev_ent, void* stream) {
+  SUG_REQUIRE(nbr && qoff && soff && rev_be && rev_ent, "sug_radius_reverse_cap: null pointer");
+  SUG_REQUIRE(B > 0 && H > 0 && Cs > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD,
+              "sug_radius_reverse_cap: bad shape (cap %d, at most %d supports per cloud)", cap, SUG_KPCONV_MAX_CLOUD);
+  const int sh = (2 * cap + SUB_BLOCK) * (int)sizeof(int);
+  hipLaunchKernelGGL(radius_reverse_kernel<true>, dim3(B + 1), dim3(SUB_BLOCK), sh, (hipStream_t)stream, nbr, qoff, soff, H,
+                     Cs, cap, rev_be, rev_ent);
+  SUG_LAUNCH_CHECK("sug_radius_reverse_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_kpconv_fwd_cap(const float* q, const float* s, const int32_t* nbr, const int32_t* nq_valid, int Cq, int H,
+                                  int Cs, const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w,
+                                  float* cnt, void* stream) {
+  SUG_REQUIRE(q && s && nbr && nq_valid && kp && x && wf && w && cnt, "sug_kpconv_fwd_cap: null pointer");
+  SUG_REQUIRE(Cq > 0 && Cs > 0 && Cin > 0 && H > 0 && H <= KP_MAX_H && K > 0 && K <= KP_MAX_K && extent > 0.f,
+              "sug_kpconv_fwd_cap: bad shape (H %d <= %d, K %d <= %d)", H, KP_MAX_H, K, KP_MAX_K);
+  hipLaunchKernelGGL(kpconv_fwd_kernel<true>, dim3(sug_divup(Cq, KP_QB)), dim3(256), 0, (hipStream_t)stream, q, s, nbr,
+                     nq_valid, Cq, H, Cs, kp, K, extent, x, Cin, wf, w, cnt);
+  SUG_LAUNCH_CHECK("sug_kpconv_fwd_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_seg_instnorm_fwd_cap(const float* x, const int32_t* off, int B, int N, int C, float eps, int mode,
+                                        const float* sc, float* y, float* mean, float* rstd, void* stream) {
+  SUG_REQUIRE(x && off && y && mean && rstd && (mode != 2 || sc), "sug_seg_instnorm_fwd_cap: null pointer");
+  SUG_REQUIRE(B > 0 && N > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_fwd_cap: bad shape / mode");
+  hipLaunchKernelGGL(seg_instnorm_fwd_kernel<true>, dim3(B + 1, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off,
+                     N, C, eps, mode, sc, y, mean, rstd);
+  SUG_LAUNCH_CHECK("sug_seg_instnorm_fwd_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_seg_instnorm_bwd_cap(const float* g, const float* y, const float* x, const float* mean,
+                                        const float* rstd, const int32_t* off, int B, int N, int C, int mode, float* dx,
+                                        float* dsc, void* stream) {
+  SUG_REQUIRE(g && y && x && mean && rstd && off && dx && (mode != 2 || dsc), "sug_seg_instnorm_bwd_cap: null pointer");
+  SUG_REQUIRE(B > 0 && N > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_bwd_cap: bad shape / mode");
+  hipLaunchKernelGGL(seg_instnorm_bwd_kernel<true>, dim3(B + 1, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, g, y, x,
+                     mean, rstd, off, N, C, mode, dx, dsc);
+  SUG_LAUNCH_CHECK("sug_seg_instnorm_bwd_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_seg_mean_fwd_cap(const float* x, const int32_t* off, int B, int C, float* y, void* stream) {
+  SUG_REQUIRE(x && off && y, "sug_seg_mean_fwd_cap: null pointer");
+  SUG_REQUIRE(B > 0 && C > 0, "sug_seg_mean_fwd_cap: bad shape");
+  hipLaunchKernelGGL(seg_mean_fwd_kernel<true>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, y);
+  SUG_LAUNCH_CHECK("sug_seg_mean_fwd_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_seg_mean_bwd_cap(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream) {
+  SUG_REQUIRE(g && off && dx, "sug_seg_mean_bwd_cap: null pointer");
+  SUG_REQUIRE(B > 0 && N > 0 && C > 0, "sug_seg_mean_bwd_cap: bad shape");
+  hipLaunchKernelGGL(seg_mean_bwd_kernel<true>, dim3(sug_divup((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, g, off,
+                     B, N, C, dx);
+  SUG_LAUNCH_CHECK("sug_seg_mean_bwd_cap");
+  return SUG_OK;
+}
+
+extern "C" int sug_kp_sample_rows(const float* x, const int32_t* off, int B, int S, int D, float* out, void* stream) {
+  SUG_REQUIRE(x && off && out, "sug_kp_sample_rows: null pointer");
+  SUG_REQUIRE(B > 0 && S > 0 && D > 0, "sug_kp_sample_rows: bad shape");
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(sug_divup((int64_t)B * S * D, 256)), dim3(256), 0, (hipStream_t)stream, x, off, B,
+                     S, D, out);
+  SUG_LAUNCH_CHECK("sug_kp_sample_rows");
   return SUG_OK;
 }

@@ -53,7 +53,9 @@ def signature(model):
     sd = model.state_dict(keep_vars=True)
     dev = str(next(iter(sd.values())).device) if sd else None
     g = getattr(model, 'g', None)
-    return (type(model).__module__ + '.' + type(model).__qualname__, None if g is None else type(g).__qualname__,
+    caps = getattr(g, 'level_caps', None)                   # KPConv_g: the capacities size the private copy's launches
+    return (type(model).__module__ + '.' + type(model).__qualname__,
+            None if g is None else type(g).__qualname__ + ('' if caps is None else ' caps=%r' % (caps,)),
             tuple((k, tuple(v.shape), str(v.dtype)) for k, v in sd.items()), dev, str(PT.GEMM_DTYPE),
             str(getattr(PT, 'PROJ_16BIT', None)))
 
@@ -63,7 +65,7 @@ def fallback_reason(model, x):
     if not isinstance(model, _known_types()):
         return 'module %s' % type(model).__name__
     if not getattr(getattr(model, 'g', None), 'graph_capturable', True):
-        return 'KPConv: level sizes depend on the data'
+        return 'KPConv: level sizes depend on the data (set_level_caps fixes them)'
     if any(m.training for m in model.modules()):
         return 'train mode'
     if not ops.CTX.unscoped():

@@ -7,6 +7,10 @@ seg_mean).
 Where the reference passes `stack_lengths` (per-cloud row counts) this build passes the level's int32 device offsets
 [B+1] (the `offsets` entry of the preprocessing dict): the kernels take the segments from device memory, without a host
 synchronisation.  Only the rigid / linear / sum path is built; the other options raise NotImplementedError.
+
+A preprocessing dict with `capacity: True` (PreprocessorGPU with level caps) holds every level at a static number of rows;
+the blocks then call the capacity forms of the ops (ops.kpconv_cap, seg_instnorm_cap, seg_mean_cap), which read the valid
+row counts from the offsets on the device and keep the dead rows exactly zero.
 """
 import functools
 import math
@@ -89,9 +93,10 @@ def max_pool(x, inds, rev=None):
     return ops.seg_max_pool(x, inds, rev)
 
 
-def global_average(x, batch_offsets):
-    """[B, d]: per-cloud mean of the rows of x (model/KPConv_blocks.py:179-197); batch_offsets [B+1] int32 (device)."""
-    return ops.seg_mean(x, batch_offsets)
+def global_average(x, batch_offsets, capacity=False):
+    """[B, d]: per-cloud mean of the rows of x (model/KPConv_blocks.py:179-197); batch_offsets [B+1] int32 (device).
+    capacity: x is at capacity (an empty cloud's row is zero)."""
+    return (ops.seg_mean_cap if capacity else ops.seg_mean)(x, batch_offsets)
 
 
 def sample_index(lengths, sampled_len=64):
@@ -160,9 +165,13 @@ class KPConv(nn.Module):
         K_points_numpy = load_kernels(self.radius, self.K, dimension=self.p_dim, fixed=self.fixed_kernel_points)
         return Parameter(torch.tensor(K_points_numpy, dtype=torch.float32), requires_grad=False)
 
-    def forward(self, q_pts, s_pts, neighb_inds, x, rev=None):
-        """[Nq, out_channels]; rev: the sorted reverse lists of neighb_inds (ops.radius_reverse), built here if absent."""
+    def forward(self, q_pts, s_pts, neighb_inds, x, rev=None, qoff=None):
+        """[Nq, out_channels]; rev: the sorted reverse lists of neighb_inds (ops.radius_reverse), built here if absent.
+        qoff (the capacity layout): the query level's device offsets; rev is then required."""
         neighb_inds = _i32(neighb_inds)
+        if qoff is not None:
+            return ops.kpconv_cap(x, q_pts.contiguous(), s_pts.contiguous(), neighb_inds, rev, self.kernel_points,
+                                  self.weights, self.KP_extent, qoff)
         if rev is None:
             rev = _rev_single(neighb_inds, q_pts.shape[0], s_pts.shape[0])
         return ops.kpconv(x, q_pts.contiguous(), s_pts.contiguous(), neighb_inds, rev, self.kernel_points, self.weights,
@@ -201,10 +210,10 @@ class BatchNormBlock(nn.Module):
         self.in_dim = in_dim
         self.norm = nn.InstanceNorm1d(in_dim, momentum=bn_momentum)
 
-    def forward(self, x, stack_lengths, act=False, shortcut=None):
+    def forward(self, x, stack_lengths, act=False, shortcut=None, capacity=False):
         """stack_lengths: the level's device offsets [B+1] (int32).  act: LeakyReLU(0.1) after the norm;
-        shortcut: LeakyReLU(0.1)(norm + shortcut) (the end of the bottleneck block)."""
-        return ops.seg_instnorm(x, stack_lengths, act=act, shortcut=shortcut)
+        shortcut: LeakyReLU(0.1)(norm + shortcut) (the end of the bottleneck block).  capacity: x is at capacity."""
+        return (ops.seg_instnorm_cap if capacity else ops.seg_instnorm)(x, stack_lengths, act=act, shortcut=shortcut)
 
     def __repr__(self):
         return 'BatchNormBlock(in_feat: {:d}, momentum: {:.3f}, only_bias: {:s})'.format(
@@ -225,10 +234,10 @@ class UnaryBlock(nn.Module):
         if not no_relu:
             self.leaky_relu = nn.LeakyReLU(0.1)
 
-    def forward(self, x, stack_lengths=None, shortcut=None):
+    def forward(self, x, stack_lengths=None, shortcut=None, capacity=False):
         """shortcut (no_relu blocks only): LeakyReLU(0.1)(block(x) + shortcut) in the norm's epilogue."""
         y = ops.linear_rows(x, self.mlp.weight)
-        return self.batch_norm(y, stack_lengths, act=not self.no_relu, shortcut=shortcut)
+        return self.batch_norm(y, stack_lengths, act=not self.no_relu, shortcut=shortcut, capacity=capacity)
 
     def __repr__(self):
         return 'UnaryBlock(in_feat: {:d}, out_feat: {:d}, BN: {:s}, ReLU: {:s})'.format(
@@ -264,8 +273,9 @@ class SimpleBlock(nn.Module):
 
     def forward(self, x, batch):
         q_pts, s_pts, nbr, rev, off = _level(batch, self.layer_ind, 'strided' in self.block_name)
-        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev)
-        return self.batch_norm(x, off, act=True)
+        cap = bool(batch.get('capacity', False))
+        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev, qoff=off if cap else None)
+        return self.batch_norm(x, off, act=True, capacity=cap)
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -300,11 +310,12 @@ class ResnetBottleneckBlock(nn.Module):
         strided = 'strided' in self.block_name
         off_pre = batch['offsets'][self.layer_ind]
         q_pts, s_pts, nbr, rev, off_post = _level(batch, self.layer_ind, strided)
-        x = self.unary1(features, off_pre) if isinstance(self.unary1, UnaryBlock) else features
-        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev)
-        x = self.batch_norm_conv(x, off_post, act=True)
+        cap = bool(batch.get('capacity', False))
+        x = self.unary1(features, off_pre, capacity=cap) if isinstance(self.unary1, UnaryBlock) else features
+        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev, qoff=off_post if cap else None)
+        x = self.batch_norm_conv(x, off_post, act=True, capacity=cap)
         shortcut = max_pool(features, nbr, rev) if strided else features
         if isinstance(self.unary_shortcut, UnaryBlock):
-            shortcut = self.unary_shortcut(shortcut, off_post)
+            shortcut = self.unary_shortcut(shortcut, off_post, capacity=cap)
         # unary2 (Linear + norm, no ReLU), the residual sum and the LeakyReLU in one epilogue
-        return self.unary2(x, off_post, shortcut=shortcut)
+        return self.unary2(x, off_post, shortcut=shortcut, capacity=cap)

@@ -9,7 +9,14 @@ are restated under documented assumptions:
     (s - q) per axis, summed x, y, z; r^2 = fp32(r) * fp32(r); missing slots hold the shadow index (total supports);
   * grid subsample: key = floor(fp32(p) / fp32(dl)) per axis (true division), voxels per cloud in order of their first
     point (MinkowskiEngine's own order is a hash order), the voxel point = fp32 sum in point order / count.
+
+With level caps (`set_level_caps` of KPConv_g / KPFCls) the pyramid takes the CAPACITY form instead: level l owns a buffer
+of a static number of rows (`level_capacity`), the kernels read the valid counts from the device offsets, and nothing is
+copied to the host -- a forward and its backward are one static launch sequence, which a hipGraph can replay.  A level
+that needs more rows than its capacity is truncated (the tail of the last clouds) and noted in a small device record that
+`capacity_report` reads; `calibrate_level_caps` measures caps on sample batches with the exact-size path.
 """
+import math
 from typing import List
 
 import numpy as np
@@ -22,7 +29,11 @@ from .KPConv_blocks import block_decider, global_average, UnaryBlock
 
 class _Config(dict):
     """Attribute access over a dict (the reference's EasyDict)."""
-    __getattr__ = dict.__getitem__
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError:
+            raise AttributeError(k) from None       # (copy.deepcopy probes __deepcopy__: a KeyError would escape it)
 
     def __setattr__(self, k, v):
         self[k] = v
@@ -74,12 +85,149 @@ def _layer_plan(config):
     return plan
 
 
+def _pooled_levels(config):
+    return sum(1 for _, pooled in _layer_plan(config) if pooled)
+
+
+def level_capacity(B, N, caps):
+    """Rows of every level buffer of B clouds of N points under per-cloud caps (levels 1..): C_0 = B*N,
+    C_l = min(C_{l-1}, 64*ceil(B*caps[l-1]/64)).  Plain host code."""
+    C = [int(B) * int(N)]
+    for c in caps:
+        C.append(min(C[-1], 64 * int(math.ceil(int(B) * float(c) / 64.0))))
+    return C
+
+
+def _checked_caps(caps, levels):
+    """caps as a tuple of `levels` positive finite numbers (None stays None)."""
+    if caps is None:
+        return None
+    if isinstance(caps, (str, bytes)) or not hasattr(caps, '__len__') or len(caps) != levels:
+        raise ValueError('set_level_caps: a sequence of %d per-cloud row caps (levels 1..%d), or None; got %r'
+                         % (levels, levels, caps))
+    out = []
+    for c in caps:
+        if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)) or not math.isfinite(c) or c <= 0:
+            raise ValueError('set_level_caps: every cap is a positive finite number (got %r in %r)' % (c, tuple(caps)))
+        out.append(int(c) if float(c).is_integer() else float(c))
+    return tuple(out)
+
+
+def calibrate_level_caps(batches, config=None, margin=1.15):
+    """Per-cloud caps for `set_level_caps` from sample batches: the exact-size preprocessing runs over an iterable of
+    [B,3,N,1] device batches, and per level the largest total / B seen, times `margin`, rounded up, is returned.  This is
+    the one place that waits for the host, once, before training."""
+    config = KPConvConfig if config is None else config
+    pre = PreprocessorGPU(config)
+    worst = None
+    for x in batches:
+        pts, lengths = _split_clouds(x)
+        meta = pre.forward_packed(pts, lengths)
+        per = [sum(l) / float(len(lengths)) for l in meta['lengths'][1:]]
+        worst = per if worst is None else [max(a, b) for a, b in zip(worst, per)]
+    if worst is None:
+        raise ValueError('calibrate_level_caps: no batches')
+    return tuple(max(1, int(math.ceil(w * float(margin)))) for w in worst)
+
+
+class LevelCaps:
+    """set_level_caps / capacity_report of a module with a `preprocessor` (KPConv_g, KPFCls)."""
+
+    def set_level_caps(self, caps):
+        """caps: 4 positive numbers -- the rows PER CLOUD allowed at levels 1..4 -- or None for the exact-size path.
+        While caps are set the module is graph_capturable: nothing in its forward or backward waits for the host."""
+        caps = _checked_caps(caps, _pooled_levels(self.config))
+        self.preprocessor.set_level_caps(caps)
+        self.level_caps = caps
+        self.graph_capturable = caps is not None
+
+    def capacity_report(self, reset=False):
+        """One host read of the capacity record.  {'levels': [{'level', 'capacity' (rows in force, of the last forward's
+        batch), 'needed' (most rows any forward needed so far), 'cap' (the per-cloud cap in force), 'cap_needed' (the
+        per-cloud cap that would have sufficed for the last batch size)}, ...], 'overflows': forwards in which a level
+        overflowed}; reset=True clears the record."""
+        return self.preprocessor.capacity_report(reset)
+
+
 class PreprocessorGPU(nn.Module):
     """Computes the metadata used for KPConv on the device (deterministic: voxels in first-point order)."""
 
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
+        self.level_caps = None          # per-cloud caps of levels 1.. (capacity form), None: exact sizes
+        self._record = None             # int32 [ops.KPCONV_RECORD_INTS] on the device: needed rows per level, overflows
+        self._shape = None              # (B, N) of the last capacity forward
+
+    def set_level_caps(self, caps):
+        self.level_caps = None if caps is None else tuple(caps)
+        self._record = self._shape = None
+
+    def _record_on(self, dev):
+        if self._record is None or self._record.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('KPConv capacity record: the first forward with level caps must run outside a capture')
+            self._record = torch.zeros(ops.KPCONV_RECORD_INTS, dtype=torch.int32, device=dev)
+        return self._record
+
+    def capacity_report(self, reset=False):
+        if self.level_caps is None:
+            raise RuntimeError('capacity_report: no level caps are set (set_level_caps)')
+        rec = [0] * ops.KPCONV_RECORD_INTS if self._record is None else self._record.tolist()   # the one host read
+        if reset and self._record is not None:
+            self._record.zero_()
+        B, N = self._shape if self._shape is not None else (1, 0)
+        C = level_capacity(B, N, self.level_caps)
+        levels = [{'level': l + 1, 'capacity': C[l + 1], 'needed': rec[l], 'cap': self.level_caps[l],
+                   'cap_needed': int(math.ceil(rec[l] / float(B)))} for l in range(len(self.level_caps))]
+        return {'levels': levels, 'overflows': rec[4]}
+
+    def _forward_capacity(self, points, B, N):
+        """The pyramid at capacity: every tensor has a static size, every count stays on the device."""
+        config = self.cfg
+        plan = _layer_plan(config)
+        limits = config.neighborhood_limits
+        dev = points.device
+        if N > ops.KPCONV_MAX_CLOUD:
+            raise NotImplementedError('KPConv preprocessing: clouds of at most %d points (got %d)' % (ops.KPCONV_MAX_CLOUD, N))
+        C = level_capacity(B, N, self.level_caps)
+        rec = self._record_on(dev)
+        self._shape = (B, N)
+        bufs, offs = [points], [torch.arange(0, (B + 1) * N, N, dtype=torch.int32, device=dev)]
+        for li, (r, pooled) in enumerate(plan):
+            if not pooled:
+                break
+            p, o = ops.kp_grid_subsample_cap(bufs[-1], offs[-1], B, N, 2 * r / config.conv_radius, C[li + 1], rec, li)
+            bufs.append(p)
+            offs.append(o)
+        neighbors, pools, upsamples, rev_n, rev_p = [], [], [], [], []
+        for li, (r, pooled) in enumerate(plan):
+            nb = ops.radius_neighbors_cap(bufs[li], offs[li], bufs[li], offs[li], r, limits[li])
+            neighbors.append(nb)
+            rev_n.append(ops.radius_reverse_cap(nb, offs[li], offs[li], C[li], N))
+            if pooled:
+                pl = ops.radius_neighbors_cap(bufs[li + 1], offs[li + 1], bufs[li], offs[li], r, limits[li])
+                pools.append(pl)
+                rev_p.append(ops.radius_reverse_cap(pl, offs[li + 1], offs[li], C[li], N))
+                upsamples.append(ops.radius_neighbors_cap(bufs[li], offs[li], bufs[li + 1], offs[li + 1], 2 * r, limits[li]))
+            else:
+                empty = torch.zeros((0, 1), dtype=torch.int32, device=dev)
+                pools.append(empty)
+                upsamples.append(empty)
+                rev_p.append(None)
+        return {
+            'points': bufs,
+            'neighbors': neighbors,
+            'pools': pools,
+            'upsamples': upsamples,
+            'stack_lengths': [(o[1:] - o[:-1]).to(torch.int64) for o in offs],
+            'offsets': offs,
+            'rev_neighbors': rev_n,
+            'rev_pools': rev_p,
+            'lengths': None,            # nothing may need host lengths
+            'capacity': True,
+            'capacities': C,
+        }
 
     def forward(self, pts: List[torch.Tensor]):
         """pts: list of point clouds XYZ [Ni, 3] (fp32, HIP device)."""
@@ -88,6 +236,10 @@ class PreprocessorGPU(nn.Module):
     def forward_packed(self, points, lengths):
         """points [sum Ni, 3] packed on the device, lengths: host ints."""
         ops._need_gpu(points)
+        if self.level_caps is not None:
+            if len(set(lengths)) != 1:
+                raise NotImplementedError('KPConv preprocessing with level caps: clouds of one length (got %r)' % (lengths,))
+            return self._forward_capacity(points, len(lengths), int(lengths[0]))
         config = self.cfg
         plan = _layer_plan(config)
         limits = config.neighborhood_limits
@@ -188,9 +340,9 @@ class GlobalAverageBlock(nn.Module):
     def __init__(self):
         super(GlobalAverageBlock, self).__init__()
 
-    def forward(self, x, len):
+    def forward(self, x, len, capacity=False):
         """len: the last level's device offsets [B+1] (int32) in this build (the reference: stack lengths)."""
-        return global_average(x, len)
+        return global_average(x, len, capacity)
 
 
 def _split_clouds(x):
@@ -200,10 +352,11 @@ def _split_clouds(x):
     return pts, [N] * B
 
 
-class KPFCls(nn.Module):
+class KPFCls(LevelCaps, nn.Module):
     """model/KPConv_model.py:60-90.  B = 1 works here (the reference builds an empty cloud list for it)."""
 
-    graph_capturable = False        # level sizes depend on the data, as KPConv_g's: SourceStep runs it eagerly
+    graph_capturable = False        # level sizes depend on the data, as KPConv_g's: SourceStep runs it eagerly --
+    level_caps = None               # unless set_level_caps(caps) fixes the level capacities (then True, on the instance)
 
     def __init__(self, config=None, increase_channel_when_downsample=True):
         super().__init__()
@@ -220,7 +373,7 @@ class KPFCls(nn.Module):
         kpconv_meta = self.preprocessor.forward_packed(pts, lengths)
         feats0 = kpconv_meta["points"][0][:, 0:1]
         feats = self.encoder(feats0, kpconv_meta)
-        feats_avg = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1])
+        feats_avg = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1], kpconv_meta.get('capacity', False))
         return self.fc(feats_avg)
 
 
@@ -233,5 +386,5 @@ def p2p_fitting_regularizer(net, deform_fitting_power=1):
     return 0
 
 
-__all__ = ['KPConvConfig', 'PreprocessorGPU', 'KPFEncoder', 'GlobalAverageBlock', 'KPFCls', 'p2p_fitting_regularizer',
+__all__ = ['level_capacity', 'calibrate_level_caps', 'KPConvConfig', 'PreprocessorGPU', 'KPFEncoder', 'GlobalAverageBlock', 'KPFCls', 'p2p_fitting_regularizer',
            'UnaryBlock']

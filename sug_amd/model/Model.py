@@ -532,8 +532,12 @@ class Pointnet_c(nn.Module):
 class KPConv_g(nn.Module):
     """model/Model.py:349-386: the KPConv encoder -- device-side preprocessing, 14 blocks on 5 levels, the per-cloud mean
     of the last level [B, 1024] and the node features [B, 64, 64] (64 rows per cloud of block 2's output, detached as in
-    the reference).  The level sizes depend on the data, so this encoder runs eagerly (no per-call graph replay)."""
+    the reference).  The level sizes depend on the data, so this encoder runs eagerly (no per-call graph replay) -- unless
+    set_level_caps(caps) fixes the capacity of every level (KPConv_model.LevelCaps): then nothing in a forward or backward
+    waits for the host, graph_capturable is True on the instance, and SUGStep / eval_graphs accept the encoder."""
     graph_capturable = False
+    level_caps = None
+    samples_fps = False             # no FPS stage: forward_pair draws no starts for it
 
     def __init__(self, config=None):
         super(KPConv_g, self).__init__()
@@ -546,6 +550,16 @@ class KPConv_g(nn.Module):
         self.global_avg_pooling = GlobalAverageBlock()
         self.deform_fitting_power = self.config.deform_fitting_power
 
+    def set_level_caps(self, caps):
+        """caps: 4 positive numbers -- rows per cloud allowed at levels 1..4 -- or None for the exact-size path
+        (KPConv_model.LevelCaps.set_level_caps, calibrate_level_caps)."""
+        from .KPConv_model import LevelCaps
+        LevelCaps.set_level_caps(self, caps)
+
+    def capacity_report(self, reset=False):
+        """KPConv_model.LevelCaps.capacity_report: one host read of the capacity record."""
+        return self.preprocessor.capacity_report(reset)
+
     def forward(self, x, node=False, feat_grad=True):
         """x [B,3,N,1].  B = 1 is accepted (the reference's `if x.shape[0] > 1` leaves it an empty cloud list)."""
         from .KPConv_model import _split_clouds
@@ -553,8 +567,11 @@ class KPConv_g(nn.Module):
         kpconv_meta = self.preprocessor.forward_packed(pts, lengths)
         feats0 = kpconv_meta["points"][0][:, 0:1]
         feats = self.encoder(feats0, kpconv_meta)
-        nodes = self.sample_tensor_slices(feats[2], kpconv_meta["lengths"][1])
-        feats = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1])
+        if kpconv_meta.get('capacity', False):
+            nodes = ops.kp_sample_rows(feats[2], kpconv_meta["offsets"][1])
+        else:
+            nodes = self.sample_tensor_slices(feats[2], kpconv_meta["lengths"][1])
+        feats = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1], kpconv_meta.get('capacity', False))
         if node:
             return feats, nodes, None
         return feats, nodes
@@ -790,7 +807,9 @@ class Net_MDA(nn.Module):
             if not geom[1] or geom[0]() is not x_pair:
                 self._geometry = None
         plan = self.g.fps_plan(x_pair.size(2)) if hasattr(self.g, 'fps_plan') else [x_pair.size(2)]
-        if geometry is None and (ops.CTX.start_provider is None or len(plan) > 1):
+        if not getattr(self.g, 'samples_fps', True):
+            pass                # an encoder without an FPS stage (KPConv_g): no draw, as in its four-call form
+        elif geometry is None and (ops.CTX.start_provider is None or len(plan) > 1):
             # CPU-generator draws in the reference's order: all FPS calls of the source forward, then all of the target
             # forward.  Under a graph's start feeder the same order is recorded / replayed (one device slice per draw), so a
             # captured step and its eager twin see the same starts; with ONE FPS call per forward a single draw of 2B

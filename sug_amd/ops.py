@@ -3603,6 +3603,152 @@ def seg_mean(x, off):
     return _SegMean.apply(x, off)
 
 
+# Capacity forms (kpconv.hip, "CAPACITY LAYOUT"): every level tensor has a static number of rows, of which the first
+# off[B] are valid and the rest exactly zero; the valid counts are read on the device, so nothing here waits for the host
+# and the launch sequence of a forward + backward is static.  sug_kpconv_bwd / sug_seg_max_pool_* serve both layouts.
+KPCONV_RECORD_INTS = _H['SUG_KPCONV_RECORD_INTS']
+
+
+def kp_grid_subsample_cap(pts, off, B, cap, dl, C, record, level):
+    """kp_grid_subsample into a buffer of C rows: (points [C,3] with zero dead rows, offsets [B+1] clamped to C); the
+    unclamped total goes into `record` (int32 [KPCONV_RECORD_INTS]) at `level` (0 = the first pooled level)."""
+    _need_gpu(pts, off, record)
+    pts = pts.detach().contiguous()
+    pad = torch.empty(B, cap, 3, dtype=torch.float32, device=pts.device)
+    cnt = torch.empty(B, dtype=torch.int32, device=pts.device)
+    out = torch.empty(C, 3, dtype=torch.float32, device=pts.device)
+    out_off = torch.empty(B + 1, dtype=torch.int32, device=pts.device)
+    check(lib().sug_grid_subsample_cap(_p(pts), _p(off), B, cap, float(dl), C, level, _p(pad), _p(cnt), _p(out), _p(out_off),
+                                       _p(record), _st()), 'sug_grid_subsample_cap')
+    return out, out_off
+
+
+def radius_neighbors_cap(q, qoff, s, soff, radius, limit):
+    """[Cq, limit] int32 at capacity: the shadow index is Cs = s.shape[0]; a dead query's row is all shadow."""
+    _need_gpu(q, qoff, s, soff)
+    q, s = q.detach().contiguous(), s.detach().contiguous()
+    out = torch.empty(q.shape[0], limit, dtype=torch.int32, device=q.device)
+    check(lib().sug_radius_neighbors_cap(_p(q), _p(qoff), q.shape[0], _p(s), _p(soff), s.shape[0], qoff.numel() - 1,
+                                         float(radius), limit, _p(out), _st()), 'sug_radius_neighbors_cap')
+    return out
+
+
+def radius_reverse_cap(nbr, qoff, soff, Cs, cap):
+    """Sorted reverse lists at capacity: (rev_be [Cs,2] with empty lists for the dead supports, rev_ent [Cq*H]); cap: the
+    level-0 cloud size (no cloud grows)."""
+    _need_gpu(nbr, qoff, soff)
+    Cq, H = nbr.shape
+    be = torch.empty(Cs, 2, dtype=torch.int32, device=nbr.device)
+    ent = torch.empty(max(1, Cq * H), dtype=torch.int32, device=nbr.device)
+    check(lib().sug_radius_reverse_cap(_p(nbr), _p(qoff), _p(soff), qoff.numel() - 1, H, Cs, cap, _p(be), _p(ent), _st()),
+          'sug_radius_reverse_cap')
+    return be, ent
+
+
+class _KPConvAggCap(torch.autograd.Function):
+    """_KPConvAgg at capacity: qoff's last entry is the number of valid queries (read on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, q, s, nbr, kp, extent, rev, qoff):
+        _need_gpu(x, q, s, nbr, kp, qoff)
+        x = x.contiguous()
+        Cq, H = nbr.shape
+        K, Cin = kp.shape[0], x.shape[1]
+        wf = torch.empty(Cq, K * Cin, dtype=torch.float32, device=x.device)
+        w = torch.empty(Cq, H, K, dtype=torch.float32, device=x.device)
+        cnt = torch.empty(Cq, dtype=torch.float32, device=x.device)
+        check(_timed('kpconv_fwd', {'Nq': Cq, 'Cin': Cin},
+                     lambda: lib().sug_kpconv_fwd_cap(_p(q), _p(s), _p(nbr), _p(qoff[-1:]), Cq, H, s.shape[0],
+                                                      _p(kp.detach().contiguous()), K, float(extent), _p(x), Cin, _p(wf),
+                                                      _p(w), _p(cnt), _st())), 'sug_kpconv_fwd_cap')
+        ctx.save_for_backward(w, cnt)
+        ctx.rev, ctx.dims = rev, (H, K, s.shape[0], Cin)
+        return wf
+
+    @staticmethod
+    def backward(ctx, g):
+        return _KPConvAgg.backward(ctx, g) + (None,)
+
+
+def kpconv_cap(x, q, s, nbr, rev, kernel_points, weights, extent, qoff):
+    """kpconv at capacity (q / nbr [Cq, ...], x / s [Cs, ...]); the GEMM runs on all Cq rows, the dead ones being zero."""
+    _need_gpu(x, q, s, nbr, kernel_points, weights)
+    K, Cin, Cout = weights.shape
+    wf = _KPConvAggCap.apply(x, q, s, nbr, kernel_points, extent, rev, qoff)
+    return linear_rows(wf, weights.view(K * Cin, Cout).t())
+
+
+class _SegInstNormCap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, off, mode, sc):
+        _need_gpu(x, off, sc)
+        x = x.contiguous()
+        B, (N, C) = off.numel() - 1, x.shape
+        y = torch.empty_like(x)
+        mean = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        scc = sc.contiguous() if sc is not None else None
+        check(lib().sug_seg_instnorm_fwd_cap(_p(x), _p(off), B, N, C, 1e-5, mode, _p(scc), _p(y), _p(mean), _p(rstd), _st()),
+              'sug_seg_instnorm_fwd_cap')
+        ctx.save_for_backward(x, y, mean, rstd, off)
+        ctx.mode = mode
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, mean, rstd, off = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        dsc = torch.empty_like(x) if ctx.mode == 2 else None
+        check(lib().sug_seg_instnorm_bwd_cap(_p(g), _p(y), _p(x), _p(mean), _p(rstd), _p(off), off.numel() - 1, x.shape[0],
+                                             x.shape[1], ctx.mode, _p(dx), _p(dsc), _st()), 'sug_seg_instnorm_bwd_cap')
+        return dx, None, None, dsc
+
+
+def seg_instnorm_cap(x, off, act=False, shortcut=None):
+    """seg_instnorm at capacity: x [C_l, C] with valid rows [0, off[B]); the dead rows of the result are zero."""
+    mode = 2 if shortcut is not None else (1 if act else 0)
+    return _SegInstNormCap.apply(x, off, mode, shortcut)
+
+
+class _SegMeanCap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, off):
+        _need_gpu(x, off)
+        x = x.contiguous()
+        B, C = off.numel() - 1, x.shape[1]
+        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        check(lib().sug_seg_mean_fwd_cap(_p(x), _p(off), B, C, _p(y), _st()), 'sug_seg_mean_fwd_cap')
+        ctx.save_for_backward(off)
+        ctx.N = x.shape[0]
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (off,) = ctx.saved_tensors
+        g = g.contiguous()
+        B, C = g.shape
+        dx = torch.empty(ctx.N, C, dtype=torch.float32, device=g.device)
+        check(lib().sug_seg_mean_bwd_cap(_p(g), _p(off), B, ctx.N, C, _p(dx), _st()), 'sug_seg_mean_bwd_cap')
+        return dx, None
+
+
+def seg_mean_cap(x, off):
+    """seg_mean at capacity; an empty cloud's row is zero, with a zero gradient."""
+    return _SegMeanCap.apply(x, off)
+
+
+def kp_sample_rows(x, off, sampled_len=64):
+    """[B, sampled_len, D]: sample_tensor_slices of the rows x [C_l, D] from the device offsets off [B+1] (forward only:
+    the reference detaches this tensor)."""
+    _need_gpu(x, off)
+    x = x.detach().contiguous()
+    B, D = off.numel() - 1, x.shape[1]
+    out = torch.empty(B, sampled_len, D, dtype=torch.float32, device=x.device)
+    check(lib().sug_kp_sample_rows(_p(x), _p(off), B, sampled_len, D, _p(out), _st()), 'sug_kp_sample_rows')
+    return out
+
+
 # ----------------------------------------------------------------------------- data pipeline
 PREP_NORMALIZE, PREP_ROTATE_Z, PREP_JITTER, PREP_SHUFFLE, PREP_MAX_POINTS = (          # the stage bits and the limit on P
     _H['SUG_PREP_' + _n] for _n in ('NORMALIZE', 'ROTATE_Z', 'JITTER', 'SHUFFLE', 'MAX_POINTS'))

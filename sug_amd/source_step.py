@@ -35,7 +35,7 @@ class SourceStep(ReplayedStep):
         if self.use_graph and not (getattr(model, 'graph_capturable', True) and
                                    getattr(getattr(model, 'g', None), 'graph_capturable', True)):
             self.use_graph = False
-            self.why = '%s: level sizes depend on the data' % type(model).__name__
+            self.why = '%s: level sizes depend on the data (set_level_caps fixes them)' % type(model).__name__
         AdamCls, kw = adam_choice(on_gpu, fused_adam, self.use_graph)
         self.optimizer = AdamCls(model.parameters(), lr=lr, weight_decay=weight_decay, **kw)      # train_source.py:95
         # (loss_total, data_total) of train_source.py:110-111, :130-131; rows of steps whose criterion is not the fused
@@ -61,6 +61,9 @@ class SourceStep(ReplayedStep):
         train_source.py:134 prints every ten batches as loss_total / data_total)."""
         if self._totals is None:
             return 0.0, 0.0
+        from .train_step import check_level_caps
+        for m in (self.model, getattr(self.model, 'g', None)):      # KPFCls / a KPConv encoder with level caps: overflow raises
+            check_level_caps(m, reset)
         loss_total, rows = self._totals.tolist()
         rows += self._rows_host[0]
         if reset:
@@ -88,8 +91,10 @@ class SourceStep(ReplayedStep):
         from .model import Ptran_transformer as PT
         c = self.criterion
         crit = ('ce', int(c.ignore_index), float(c.label_smoothing)) if plain_ce(c, smoothing_ok=True) else ('call', id(c), repr(c))
-        return (tuple(batch[0].shape), tuple(batch[1].shape), crit, self.model.training, PT.GEMM_DTYPE,
-                getattr(PT, 'PROJ_16BIT', None), hyper_key(self.optimizer))
+        key = (tuple(batch[0].shape), tuple(batch[1].shape), crit, self.model.training, PT.GEMM_DTYPE,
+               getattr(PT, 'PROJ_16BIT', None), hyper_key(self.optimizer))
+        caps = getattr(self.model, 'level_caps', None)      # KPFCls: the level capacities size every launch
+        return key if caps is None else key + (('level_caps', caps),)
 
     def _eager_step(self, data, label):
         model, B = self.model, data.shape[0]

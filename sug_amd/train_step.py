@@ -205,6 +205,22 @@ class GradReducer:
         self.flats = self.members = self.handles = None
 
 
+def check_level_caps(module, reset=True):
+    """The capacity report of a module with level caps (None without); RuntimeError if a forward overflowed: its results
+    were computed on truncated clouds."""
+    if getattr(module, 'level_caps', None) is None:
+        return None
+    rep = module.capacity_report(reset=reset)
+    if rep['overflows']:
+        bad = [l for l in rep['levels'] if l['needed'] > l['capacity']]
+        what = '; '.join('level %d needed %d rows (capacity %d): a cap of %d rows per cloud would have sufficed, %s is set'
+                         % (l['level'], l['needed'], l['capacity'], l['cap_needed'], l['cap']) for l in bad)
+        raise RuntimeError('KPConv level caps overflowed in %d forward(s) since the last read -- those steps ran on truncated '
+                           'clouds: %s.  Raise the caps (set_level_caps; calibrate_level_caps measures them)'
+                           % (rep['overflows'], what))
+    return rep
+
+
 def _params_above_encoder(model):
     """The parameters above the encoder (heads, attention layers): their gradients are ready first in a backward."""
     return [p for m in (model.c1, model.c2, model.attention_s, model.attention_t) for p in m.parameters()]
@@ -228,7 +244,8 @@ class SUGStep:
                  global_mmd=True, fused_adam=None, share_prefix=True, use_graph=False, pair_domains=True,
                  force_segmented=False, single_pass=False):
         if not getattr(getattr(model, 'g', None), 'graph_capturable', True):
-            raise NotImplementedError('SUGStep: the KPConv backbone is not supported (its level sizes depend on the data); '
+            raise NotImplementedError('SUGStep: the KPConv backbone is not supported (its level sizes depend on the data) '
+                                      'unless model.g.set_level_caps(caps) fixes the level capacities; without caps '
                                       'train it with the eager four-call form -- model(...) per loss term, as '
                                       'train_dg_single_gpu.py does -- which Net_MDA(\'KPConv\') supports')
         self.model = model
@@ -527,12 +544,20 @@ class SUGStep:
     def _opts(self):
         return (self.optimizer_g, self.optimizer_c, self.optimizer_dis)
 
+    def epoch_check(self, reset=True):
+        """The epoch's host read for an encoder with level caps (KPConv_g.set_level_caps): reads the capacity record once
+        and raises a RuntimeError naming the level and the cap it needed if any forward overflowed; returns the report
+        (None for an encoder without caps)."""
+        return check_level_caps(self.model.g, reset)
+
     def _graph_key(self, mmd_on, tensors):
         """Everything a captured step bakes in by value.  sug_amd.optim.Adam keeps lr on the device (one graph serves a
         whole schedule); any other optimizer takes lr by value, so its lr of every group is part of the key."""
         c = self.criterion
         crit = ('ce', int(c.ignore_index)) if plain_ce(c) else (self._crit.record(c, self.max_graphs) or ('call', id(c), repr(c)))
-        return (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()), crit)
+        key = (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()), crit)
+        caps = getattr(self.model.g, 'level_caps', None)    # KPConv_g: the level capacities size every launch
+        return key if caps is None else key + (('level_caps', caps),)
 
     def _plan_generations(self):
         return plan_generations(self._opts() + (self._adam_chain,))

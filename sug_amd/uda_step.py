@@ -74,12 +74,15 @@ class UDAStep(ReplayedStep):
         p0 = next(model.parameters())
         self.device = p0.device
         on_gpu = p0.is_cuda
-        capturable = getattr(getattr(model, 'g', None), 'graph_capturable', True)
+        # a KPConv encoder is declined here with or without level caps: the two-phase step is not tested on the capacity form
+        capturable = getattr(getattr(model, 'g', None), 'graph_capturable', True) and \
+            not hasattr(getattr(model, 'g', None), 'set_level_caps')
         super().__init__(max_graphs, rows=2)
         self.use_graph = bool(use_graph) and on_gpu
         if self.use_graph and not capturable:           # Net_MDA('KPConv'): no static launch sequence, always eager
             self.use_graph = False
-            self.why = '%s: level sizes depend on the data' % type(model.g).__name__
+            self.why = '%s: level sizes depend on the data' % type(model.g).__name__ if getattr(model.g, 'level_caps', None) is None \
+                else '%s: level caps are not supported by UDAStep (eager launches)' % type(model.g).__name__
         self.pair_domains = bool(pair_domains) and capturable and hasattr(model, 'forward_pair')
         # fused_loss=False is the plain composition throughout: the loss tail from torch ops and the heads' LayerNorm +
         # activation unfused, i.e. exactly what an unchanged caller's model(...) calls launch
@@ -128,6 +131,8 @@ class UDAStep(ReplayedStep):
         host read of an epoch (train_uda.py:186-190 prints the first three over data_total every ten batches)."""
         if self._books is None:
             return 0.0, 0.0, 0.0, 0.0, 0.0
+        from .train_step import check_level_caps
+        check_level_caps(getattr(self.model, 'g', None), reset)     # a KPConv encoder run eagerly with level caps: overflow raises
         ls, adv, rows, rows_t, node = self._books.tolist()
         rows += self._rows_host[0]
         rows_t += self._rows_host[1]
