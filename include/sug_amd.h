@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -799,6 +799,36 @@ int sug_mmd_adjacent_fwd(const float* x, int64_t ldx, const float* y, int64_t ld
                          double alpha, double c, double* part, float* coef, float* value, void* stream);
 int sug_mmd_adjacent_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy, int m, int D, int mode, const float* coef,
                          const float* gscale, float* dx, int64_t lddx, float* dy, int64_t lddy, void* stream);
+
+/* The contrastive alignment mode (NAME: CL; contrastive_loss_weighted, model/mmd.py:80-94, with the trainer's
+ * nn.CosineEmbeddingLoss(margin, reduction='none'), train_dg_single_gpu.py:236-242) of n <= SUG_CL_LOSS_MAX_TERMS terms of ONE
+ * batch (same m rows per domain, same labels) in one launch sequence.  Per term and row i, x_i / y_i fp32 rows of length D:
+ *   dot = sum x y, a = sum x x + 1e-12, b = sum y y + 1e-12, cos = dot / sqrt(a b);
+ *   l_i = 1 - cos where label_s[i] == label_t[i], max(0, cos - margin) elsewhere; value = (1/m) sum_i w_i l_i (w_i = 1 without w).
+ * No host read, no atomics, no memset: capturable.  Every sum is carried in fp64 in one fixed order (per lane ascending, lane
+ * tree, waves in index order) and rounded to fp32 once, at the outputs; a row's numbers depend on that row alone, and a
+ * strided view gives the bits of its contiguous copy (16-byte loads where base pointer and row stride allow, else 4-byte
+ * loads of the same elements by the same lanes).  Limits (checked before any launch): 1 <= m <= SUG_CL_LOSS_MAX_ROWS,
+ * 1 <= D <= SUG_CL_LOSS_MAX_D, row strides >= D, finite margins, no null pointer except the entries of w (and of coef / dx / dy
+ * as stated).  HOST arrays of n entries: x / y (device [m, D[i]], row strides ldx / ldy), D, margin, w (device fp32 [m] or
+ * null), coef (device fp64 [SUG_CL_LOSS_ROW_FIELDS * m], written: the three backward coefficients of the rows and their cos;
+ * or null: no backward).  sums: device fp64 [n * SUG_CL_LOSS_SUM_FIELDS * m] scratch; values: device fp32 [n].
+ * sug_cl_loss_fwd: two launches (row sums over (row, term); fold, one workgroup per term).
+ * sug_cl_loss_bwd: one launch; gscale[i] = device scalar (upstream gradient of value i) or null (term skipped); dx[i] / dy[i]
+ *   device [m, D[i]] (row strides lddx / lddy; either may be null: one-sided, both null: term skipped), STORED:
+ *   dx_i = g (c1 y_i - c2 x_i), dy_i = g (c1 x_i - c3 y_i), c1 = w s / (m sqrt(a b)), c2 = w s cos / (m a), c3 = w s cos / (m b),
+ *   s = -1 for a positive pair, +1 for a negative pair with cos > margin, 0 otherwise.  The weights are constants. */
+#define SUG_CL_LOSS_MAX_ROWS 1024
+#define SUG_CL_LOSS_MAX_D 1048576
+#define SUG_CL_LOSS_MAX_TERMS 4
+#define SUG_CL_LOSS_SUM_FIELDS 3
+#define SUG_CL_LOSS_ROW_FIELDS 4
+int sug_cl_loss_fwd(int n, const void* const* x, const int64_t* ldx, const void* const* y, const int64_t* ldy, const int32_t* D,
+                    const double* margin, const int64_t* label_s, const int64_t* label_t, int m, const void* const* w,
+                    double* sums, void* const* coef, float* values, void* stream);
+int sug_cl_loss_bwd(int n, const void* const* x, const int64_t* ldx, const void* const* y, const int64_t* ldy, const int32_t* D,
+                    int m, const void* const* coef, const void* const* gscale, void* const* dx, const int64_t* lddx,
+                    void* const* dy, const int64_t* lddy, void* stream);
 
 /* The EdgeConv GEMM operand of a conv_2d weight W [Co, 2C] (get_graph_feature's cat(x_j - x_i, x_i) folded into
  * the weights, model/model_utils.py:188-210): backward = 0: in = W, out [2Co, C] = [W[:, :C] ; W[:, C:] - W[:, :C]];

@@ -5,10 +5,11 @@ The (2m x 2m) kernel-matrix reduction runs in one HIP kernel (sug_mmd_rbf); the 
 weights are computed on the device (the reference round-trips them through the CPU,
 model/mmd.py:138-142, :295).  The variance / ratio estimator and the linear-time estimators
 (mix_rbf_mmd2_and_ratio, linear_mmd2, poly_mmd2) run in their own kernels (ops.mmd_ratio,
-ops.linear_mmd2 / poly_mmd2)."""
+ops.linear_mmd2 / poly_mmd2), and so does the contrastive mode NAME: CL (contrastive_loss_weighted, ops.cl_loss)."""
 from copy import deepcopy
 
 import torch
+import torch.nn as nn
 
 from .. import ops
 from ..utils.common_utils import create_one_hot_labels, get_most_overlapped_element
@@ -17,11 +18,22 @@ min_var_est = 1e-8
 sigma_list = [0.01, 0.1, 1, 10, 100]
 
 
-def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=None, KPC=False, sample_weights=None):
+def _cl_criterion(args, CL_criterion=None):
+    """The criterion of a NAME: CL term: the caller's, or the trainer's own construction (train_dg_single_gpu.py:236-242)
+    with the margin of the term's MARGIN key."""
+    if CL_criterion is not None:
+        return CL_criterion
+    return nn.CosineEmbeddingLoss(margin=float(args.get("MARGIN", 0.2)), reduction="none")
+
+
+def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=None, KPC=False, sample_weights=None,
+            CL_criterion=None):
     """model/mmd.py:25-41.  `sample_weights` (not in the reference signature): SDA weights the caller
     already has (the batch-sharded step computes them once from the gathered batch).  KPC=True (the KPConv
     backbone's call) uses the same Chamfer weights as KPC=False: the reference's KPC branch (model/mmd.py:122-124)
-    only calls the unpinned third-party Chamfer op another way."""
+    only calls the unpinned third-party Chamfer op another way.  NAME: CL (not dispatched by the reference, whose trainer
+    nevertheless builds its criterion) is contrastive_loss_weighted with `CL_criterion`, by default
+    nn.CosineEmbeddingLoss(margin=args.get('MARGIN', 0.2), reduction='none')."""
     sample_weights_flag = args.get("GEO_WEIGHTS", None) or args.get("SEM_WEIGHTS", None)
     if sample_weights is None and data_s is not None and sample_weights_flag:
         sample_weights = cal_sample_weights(data_s, data_t, args, label_s=label_s, label_t=label_t)
@@ -33,6 +45,9 @@ def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=No
         return max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing=args.get("PAIRING", "sorted"))
     elif args["NAME"] == "OFF":
         return mix_rbf_mmd2(feat_s, feat_t, sigma_list)
+    elif args["NAME"] == "CL":
+        return contrastive_loss_weighted(label_s, feat_s, label_t, feat_t, float(args.get("LABEL_SCALE", 0.0)),
+                                         _cl_criterion(args, CL_criterion), sample_weights=sample_weights)
     raise RuntimeError("Not Supported MMD Method")
 
 
@@ -72,6 +87,14 @@ def soft_mmd_multi(label_s, label_t, terms):
     for _, _, args, _, _ in terms:
         if args["NAME"] != "SOFT_MMD":
             raise RuntimeError("soft_mmd_multi: SOFT_MMD terms only")
+    ws = _terms_sample_weights(label_s, label_t, terms)
+    packed = [(fs, ft, float(args["LABEL_SCALE"]), w) for (fs, ft, args, _, _), w in zip(terms, ws)]
+    return ops.soft_mmd_multi(label_s, label_t, packed, sigma_list)
+
+
+def _terms_sample_weights(label_s, label_t, terms):
+    """The SDA weights of every (feat_s, feat_t, args, data_s, data_t) term of one batch as mmd_cal would form them (None
+    for a term without), the terms weighted from head logits by one rule in one launch."""
     ws = [None] * len(terms)
     # terms weighted from head logits by the same rule (cal_sample_weights' third branch): their weights in one launch
     by_rule = {}
@@ -88,8 +111,24 @@ def soft_mmd_multi(label_s, label_t, terms):
         outs = ops.sda_prob_weights_multi([(terms[i][3], terms[i][4]) for i in idx], label_s, label_t, lw, rule)
         for i, o in zip(idx, outs):
             ws[i] = o.reshape(1, -1)
-    packed = [(fs, ft, float(args["LABEL_SCALE"]), w) for (fs, ft, args, _, _), w in zip(terms, ws)]
-    return ops.soft_mmd_multi(label_s, label_t, packed, sigma_list)
+    return ws
+
+
+def cl_loss_multi(label_s, label_t, terms):
+    """[mmd_cal(label_s, feat_s, label_t, feat_t, args, data_s, data_t) for (feat_s, feat_t, args, data_s, data_t) in terms]
+    for NAME: CL terms of one batch, the sibling of soft_mmd_multi: the SDA weights per term as mmd_cal forms them, then
+    all terms in one launch sequence (ops.cl_loss_multi) where ops.cl_loss_supported holds for every one of them, term by
+    term through contrastive_loss_weighted otherwise."""
+    terms = list(terms)
+    for _, _, args, _, _ in terms:
+        if args["NAME"] != "CL":
+            raise RuntimeError("cl_loss_multi: CL terms only")
+    ws = _terms_sample_weights(label_s, label_t, terms)
+    margins = [float(args.get("MARGIN", 0.2)) for _, _, args, _, _ in terms]
+    if all(ops.cl_loss_supported(label_s, fs, label_t, ft, mg, w) for (fs, ft, _, _, _), mg, w in zip(terms, margins, ws)):
+        return ops.cl_loss_multi(label_s, label_t, [(fs, ft, mg, w) for (fs, ft, _, _, _), mg, w in zip(terms, margins, ws)])
+    return [contrastive_loss_weighted(label_s, fs, label_t, ft, float(args.get("LABEL_SCALE", 0.0)), _cl_criterion(args),
+                                      sample_weights=w) for (fs, ft, args, _, _), w in zip(terms, ws)]
 
 
 def soft_mmd_sharded(label_s, feat_s, label_t, feat_t, label_g, feat_g_s, label_tg, feat_g_t, label_weight, row0,
@@ -111,6 +150,23 @@ def hard_mmd(label_s, feat_s, label_t, feat_t):
         return ops.class_mmd(label_s, feat_s, label_t, feat_t, 0, sigma_list)
     same = torch.eq(label_s, label_t)
     return mix_rbf_mmd2(feat_s[same], feat_t[same], sigma_list)
+
+
+def contrastive_loss_weighted(label_s, feat_s, label_t, feat_t, label_weight, CL_criterion, sample_weights=None):
+    """model/mmd.py:80-94: the criterion's row-wise loss between paired rows, target +1 where the two labels agree and -1
+    elsewhere, times the SDA weights, averaged over ALL rows.  `label_weight` takes no part: the reference builds the
+    label-augmented features (:81-84) and then hands the plain ones to the criterion (:88); nothing is launched for them here.
+    An nn.CosineEmbeddingLoss (exactly that class) with reduction 'none' on what ops.cl_loss_supported lists goes through
+    ops.cl_loss with the criterion's margin; anything else (another callable, CPU tensors, fp64, SUG_CL_LOSS=0) through the
+    composed lines."""
+    if type(CL_criterion) is nn.CosineEmbeddingLoss and CL_criterion.reduction == 'none' \
+            and ops.cl_loss_supported(label_s, feat_s, label_t, feat_t, CL_criterion.margin, sample_weights):
+        return ops.cl_loss(label_s, feat_s, label_t, feat_t, CL_criterion.margin, sample_weights)
+    same_class_index = 2 * torch.eq(label_s, label_t) - 1
+    loss = CL_criterion(feat_s, feat_t, same_class_index)
+    if sample_weights is not None:
+        loss = torch.mul(sample_weights.squeeze().to(device=loss.device), loss)
+    return torch.mean(loss)
 
 
 def max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing='sorted'):

@@ -3173,6 +3173,139 @@ def poly_mmd2(X, Y, d=2, alpha=1.0, c=2.0):
     return _adjacent('poly_mmd2', X, Y, 1, d, alpha, c)
 
 
+CL_LOSS = _os.environ.get('SUG_CL_LOSS', '1') != '0'          # A/B knob: 0 = the composed lines of mmd.contrastive_loss_weighted
+CL_LOSS_MAX_ROWS, CL_LOSS_MAX_D, CL_LOSS_MAX_TERMS = (_H['SUG_CL_LOSS_MAX_' + _n] for _n in ('ROWS', 'D', 'TERMS'))
+
+
+def _cl_weights(w, m, dev):
+    if w is None:
+        return None
+    wc = w.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    if wc.numel() != m:
+        raise RuntimeError('sug_amd.ops.cl_loss: %d sample weights for %d samples' % (wc.numel(), m))
+    return wc
+
+
+def _cl_forward(label_s, label_t, margins, ws, fs, ft, need):
+    """sug_cl_loss_fwd of the terms (fs[i], ft[i]): (values fp32 [n], coef: fp64 [4, m] per term with need[i], else None)."""
+    n, m, dev = len(fs), fs[0].shape[0], fs[0].device
+    ls, lt = label_s.reshape(-1).contiguous(), label_t.reshape(-1).contiguous()
+    wc = [_cl_weights(w, m, dev) for w in ws]
+    sums = torch.empty(n * _H['SUG_CL_LOSS_SUM_FIELDS'] * m, dtype=torch.float64, device=dev)
+    coef = [torch.empty(_H['SUG_CL_LOSS_ROW_FIELDS'], m, dtype=torch.float64, device=dev) if nd else None for nd in need]
+    vals = torch.empty(n, dtype=torch.float32, device=dev)
+    I64, I32, F64 = ctypes.c_int64 * n, ctypes.c_int32 * n, ctypes.c_double * n
+    check(lib().sug_cl_loss_fwd(n, _ptrs(fs), I64(*[f.stride(0) for f in fs]), _ptrs(ft), I64(*[f.stride(0) for f in ft]),
+                                I32(*[f.shape[1] for f in fs]), F64(*[float(v) for v in margins]), _p(ls), _p(lt), m, _ptrs(wc),
+                                _p(sums), _ptrs(coef), _p(vals), _st()), 'sug_cl_loss_fwd')
+    return vals, coef
+
+
+class _CLLossMulti(torch.autograd.Function):
+    """The weighted cosine-embedding loss (contrastive_loss_weighted, model/mmd.py:80-94) of up to four (feat_s, feat_t)
+    pairs of ONE batch -- same rows, same labels: two launches forward for all of them, one backward (sug_cl_loss_*).  A
+    term's value and gradient do not depend on the terms beside it."""
+
+    @staticmethod
+    def forward(ctx, label_s, label_t, margins, ws, *feats):
+        n = len(feats) // 2
+        _need_gpu(label_s, label_t, *feats)
+        fs, ft = [_unit_rows(f) for f in feats[0::2]], [_unit_rows(f) for f in feats[1::2]]
+        need = [ctx.needs_input_grad[4 + 2 * i] or ctx.needs_input_grad[5 + 2 * i] for i in range(n)]
+        vals, coef = _cl_forward(label_s, label_t, margins, ws, fs, ft, need)
+        ctx.need = need
+        ctx.save_for_backward(*(fs + ft + coef))
+        ctx.set_materialize_grads(False)
+        return tuple(vals.unbind(0))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        need, n = ctx.need, len(ctx.need)
+        saved = ctx.saved_tensors
+        fs, ft, coef = saved[:n], saved[n:2 * n], saved[2 * n:]
+        dev = fs[0].device
+        m = fs[0].shape[0]
+        live = [need[i] and gs[i] is not None for i in range(n)]
+        gsc = [gs[i].detach().to(device=dev, dtype=torch.float32).reshape(1) if live[i] else None for i in range(n)]
+        dx = [torch.empty_like(fs[i], memory_format=torch.contiguous_format) if (live[i] and ctx.needs_input_grad[4 + 2 * i]) else None
+              for i in range(n)]
+        dy = [torch.empty_like(ft[i], memory_format=torch.contiguous_format) if (live[i] and ctx.needs_input_grad[5 + 2 * i]) else None
+              for i in range(n)]
+        if any(live):
+            Ds = [f.shape[1] for f in fs]
+            I64, I32 = ctypes.c_int64 * n, ctypes.c_int32 * n
+            check(lib().sug_cl_loss_bwd(n, _ptrs(fs), I64(*[f.stride(0) for f in fs]), _ptrs(ft), I64(*[f.stride(0) for f in ft]),
+                                        I32(*Ds), m, _ptrs(coef), _ptrs(gsc), _ptrs(dx), I64(*Ds), _ptrs(dy), I64(*Ds), _st()),
+                  'sug_cl_loss_bwd')
+        out = [None] * 4
+        for i in range(n):
+            out += [dx[i], dy[i]]
+        return tuple(out)
+
+
+def cl_loss_supported(label_s, feat_s, label_t, feat_t, margin=0.2, sample_weights=None):
+    """What cl_loss takes (and sug_cl_loss_* would otherwise refuse), and the SUG_CL_LOSS knob: two fp32 [m, D] feature blocks
+    of one shape and m int64 labels per domain (1-D) on the HIP device, 1 <= m <= 1024, 1 <= D <= 2^20, a finite margin, and
+    sample weights -- constants here -- that do not require grad and have m elements after squeeze."""
+    if not CL_LOSS:
+        return False
+    ts = (label_s, feat_s, label_t, feat_t)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+        return False
+    if feat_s.dtype != torch.float32 or feat_t.dtype != torch.float32 or feat_s.dim() != 2 or feat_s.shape != feat_t.shape:
+        return False
+    m, D = feat_s.shape
+    for lab in (label_s, label_t):
+        if lab.dtype != torch.int64 or lab.dim() != 1 or lab.numel() != m:
+            return False
+    if sample_weights is not None:
+        if not isinstance(sample_weights, torch.Tensor) or sample_weights.requires_grad or not sample_weights.is_floating_point():
+            return False
+        sq = sample_weights.squeeze()
+        if sq.numel() != m or sq.dim() > 1:
+            return False
+    try:
+        finite = math.isfinite(float(margin))
+    except (TypeError, ValueError):
+        return False
+    return finite and 1 <= m <= CL_LOSS_MAX_ROWS and 1 <= D <= CL_LOSS_MAX_D
+
+
+def cl_loss_multi(label_s, label_t, terms):
+    """[cl_loss of (feat_s, feat_t, margin, sample_weights) for each of `terms`] on one batch (label_s / label_t int64 [m]
+    shared by the terms), at most four terms per launch set; each value and gradient has the bits of its own cl_loss call."""
+    terms = list(terms)
+    for fs, ft, margin, w in terms:
+        if not cl_loss_supported(label_s, fs, label_t, ft, margin, w):
+            _need_gpu(*(t for t in (label_s, fs, label_t, ft) if isinstance(t, torch.Tensor)))
+            raise RuntimeError('sug_amd.ops.cl_loss: two fp32 [m, D] feature blocks of one shape, int64 labels [m], 1 <= m <= %d, '
+                               '1 <= D <= %d, a finite margin, constant sample weights with m elements%s'
+                               % (CL_LOSS_MAX_ROWS, CL_LOSS_MAX_D, '' if CL_LOSS else ' (and not with SUG_CL_LOSS=0)'))
+    out = []
+    for i in range(0, len(terms), CL_LOSS_MAX_TERMS):
+        grp = terms[i:i + CL_LOSS_MAX_TERMS]
+        feats = [t for fs, ft, _, _ in grp for t in (fs, ft)]
+        out += list(_CLLossMulti.apply(label_s, label_t, tuple(float(g[2]) for g in grp), tuple(g[3] for g in grp), *feats))
+    return out
+
+
+def cl_loss(label_s, feat_s, label_t, feat_t, margin=0.2, sample_weights=None):
+    """mean_i w_i l_i with l_i = 1 - cos(x_i, y_i) where label_s[i] == label_t[i] and max(0, cos - margin) elsewhere
+    (contrastive_loss_weighted with nn.CosineEmbeddingLoss(margin, reduction='none'), model/mmd.py:80-94): 0-d fp32,
+    differentiable in both feature blocks; the weights are constants.  Sums in fp64 in a fixed order."""
+    return cl_loss_multi(label_s, label_t, [(feat_s, feat_t, margin, sample_weights)])[0]
+
+
+def cl_loss_cos(feat_s, feat_t):
+    """The rows' cosines as cl_loss forms them, fp64 [m] (the fold's saved field): what a row contributes depends on that
+    row alone."""
+    lab = torch.zeros(feat_s.shape[0], dtype=torch.int64, device=feat_s.device)
+    if not cl_loss_supported(lab, feat_s, lab, feat_t):
+        raise RuntimeError('sug_amd.ops.cl_loss_cos: two fp32 [m, D] feature blocks of one shape on the HIP device')
+    _, coef = _cl_forward(lab, lab, (0.0,), (None,), [_unit_rows(feat_s.detach())], [_unit_rows(feat_t.detach())], [True])
+    return coef[0][_H['SUG_CL_LOSS_ROW_FIELDS'] - 1]
+
+
 def colsum(x2, sign=1.0):
     """fp32 column sums [C] of a [R, C] fp32 / fp16 matrix (sug_colsum: no memset, fixed order)."""
     _need_gpu(x2)

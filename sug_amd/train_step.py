@@ -501,17 +501,20 @@ class SUGStep:
         if pair is not None and geo.get('GEO_WEIGHTS') and not self.global_mmd and pair.shape[2] != 3:   # (N == 3: [m,3,3] rows would read as channel-first, mmd.py:110)
             rows = ops.cloud_rows(pair)                  # the encoder's own [2B,N,3] rows: no second transpose for Chamfer
             cs, ct = rows[:data.shape[0], :, :3], rows[data.shape[0]:, :, :3]
+        multi = None                # every active term of one name that has a multi-term form: SOFT_MMD or CL
         if self._mmd_multi and not self.global_mmd and not ops.CTX.parallel_branches and feat_node_s.is_cuda \
-                and geo['NAME'] == 'SOFT_MMD' and (sem['SEM_SCALE'] <= 0 or sem['NAME'] == 'SOFT_MMD') \
+                and geo['NAME'] in ('SOFT_MMD', 'CL') and (sem['SEM_SCALE'] <= 0 or sem['NAME'] == geo['NAME']) \
                 and feat_node_s.dim() == 2 and feat_node_s.shape == feat_node_t.shape \
                 and (sem['SEM_SCALE'] <= 0 or (sem_s1.dim() == 2 and sem_s1.shape == sem_t1.shape == sem_s2.shape == sem_t2.shape
                                                and sem_s1.shape[0] == feat_node_s.shape[0])):
-            # the terms share the batch and its labels: every stage of the three in one launch (mmd.soft_mmd_multi; each
-            # term's value and gradient are those of its own mmd_cal call bit for bit)
+            multi = mmd.soft_mmd_multi if geo['NAME'] == 'SOFT_MMD' else mmd.cl_loss_multi
+        if multi is not None:
+            # the terms share the batch and its labels: every stage of the three in one launch (mmd.soft_mmd_multi,
+            # mmd.cl_loss_multi; each term's value and gradient are those of its own mmd_cal call bit for bit)
             tl = [(feat_node_s, feat_node_t, geo, cs, ct)]
             if sem['SEM_SCALE'] > 0:
                 tl += [(sem_s1, sem_t1, sem, pred_s1, pred_t1), (sem_s2, sem_t2, sem, pred_s2, pred_t2)]
-            vals = mmd.soft_mmd_multi(label, label_t, tl)
+            vals = multi(label, label_t, tl)
         else:
             terms = [lambda: self._mmd(label, feat_node_s, label_t, feat_node_t, geo, cs, ct)]
             if sem['SEM_SCALE'] > 0:
