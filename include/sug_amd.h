@@ -1113,6 +1113,48 @@ int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B,
                       uint64_t seed, const uint64_t* counter, float sigma, float clip, float* out,
                       float* angles_out, float* noise_out, int32_t* sel_out, void* stream);
 
+/* sug_prepare_batch plus the three augmentations that pc_augment (data/data_utils.py:169-175) lists behind the jitter, one
+ * draw of each per cloud.  The same kernel; the stage order becomes
+ *   1. normalise  2. pre_rot  3. z-rotation, jitter
+ *   3a. SUG_PREP_SCALE:   p * s, s uniform in [scale_low, scale_high)                       (random_scale_point_cloud);
+ *   3b. SUG_PREP_PERTURB: p . R, R = Rz (Ry Rx) of the three angles clip(angle_sigma * n, -angle_clip, angle_clip), n standard
+ *       normal (rotate_perturbation_point_cloud).  R is formed once per cloud in fp64 (angles from the fp32 normals, sines and
+ *       cosines in double) and rounded to fp32 once; the product is (x R0j + y R1j) + z R2j, as the pre-rotation's.  It is
+ *       not merged with the z-rotation, nor is the scale folded into it;
+ *   3c. SUG_PREP_SHIFT:   p + t, each component of t uniform in [-shift_range, shift_range)  (shift_point_cloud);
+ *   4. pad / subset  5. the transposed store.
+ * The three stages act on kept points only: padding rows stay exact zeros.  With none of the three bits set the output is
+ * sug_prepare_batch's bit for bit, and the old purposes and words of the generator do not move.
+ * aug_params: HOST pointer to SUG_PREP_AUG_PARAMS floats at the SUG_PREP_AUG_* positions (may be null when none of the three
+ * stages is on); checked on the host: scale_low and scale_high finite, 0 < scale_low <= scale_high; shift_range, angle_sigma
+ * and angle_clip finite and >= 0.
+ * Draws: scales [B] (the factor), perturb [B, 3] (standard normals, as noise), shifts [B, 3] (the vector) when given, else
+ * from the same Philox stream at index 0 of the purposes
+ *   SUG_PREP_DRAW_SCALE:    s = scale_low + ((word0 >> 8) * 2^-24) * (scale_high - scale_low), in fp32 (like numpy's uniform
+ *                           the sum may round up to scale_high itself);
+ *   SUG_PREP_DRAW_PERTURB:  the three normals by the Box-Muller of SUG_PREP_DRAW_NOISE (words 0, 1 -> two, words 2, 3 -> the third);
+ *   SUG_PREP_DRAW_SHIFT:    t_j = (2 * ((word_j >> 8) * 2^-24) - 1) * shift_range, j = 0..2.
+ * A null counter is refused whenever any draw is needed.  Debug outputs (each may be null): scales_out [B] (1 when the stage
+ * is off), perturb_out [B, 3] (the normals; 0 when off), shifts_out [B, 3] (0 when off). */
+#define SUG_PREP_SCALE 16
+#define SUG_PREP_PERTURB 32
+#define SUG_PREP_SHIFT 64
+#define SUG_PREP_DRAW_SCALE 0x30000000u
+#define SUG_PREP_DRAW_PERTURB 0x40000000u
+#define SUG_PREP_DRAW_SHIFT 0x50000000u
+#define SUG_PREP_AUG_PARAMS 5
+#define SUG_PREP_AUG_SCALE_LOW 0
+#define SUG_PREP_AUG_SCALE_HIGH 1
+#define SUG_PREP_AUG_SHIFT_RANGE 2
+#define SUG_PREP_AUG_ANGLE_SIGMA 3
+#define SUG_PREP_AUG_ANGLE_CLIP 4
+int sug_prepare_batch_aug(const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
+                          const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
+                          const float* scales, const float* perturb, const float* shifts, uint64_t seed,
+                          const uint64_t* counter, float sigma, float clip, const float* aug_params, float* out,
+                          float* angles_out, float* noise_out, int32_t* sel_out, float* scales_out, float* perturb_out,
+                          float* shifts_out, void* stream);
+
 /* ---- Batched point-to-point ICP fitness (the geometric sub-domain splitter, dataset_splitter.py:217-231) ----------------
  * icp_distance() calls open3d's registration_icp(source, target, max_correspondence_distance=0.15) once per cloud; this
  * entry point registers B (source, target) pairs in one launch, one workgroup per pair.  src [B or 1, Ns, 3] fp32 with

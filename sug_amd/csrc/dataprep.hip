@@ -1,6 +1,8 @@
 // Device-resident data pipeline: what UnifiedPointDG.__getitem__ (data/dataloader.py:302-327) does per cloud -- normal_pc,
 // the fixed pre-rotation, the random z-rotation, the clipped jitter, zero padding or a random ordered subset, the transpose
-// -- for a whole batch in one launch, one workgroup per cloud.  Counter layout of the in-kernel draws: include/sug_amd.h.
+// -- for a whole batch in one launch, one workgroup per cloud.  sug_prepare_batch_aug adds the three augmentations that
+// pc_augment lists but leaves switched off (random scale, rotation perturbation, shift), behind the jitter in its line order.
+// Counter layout of the in-kernel draws: include/sug_amd.h.
 #include "common.h"
 
 namespace {
@@ -50,7 +52,17 @@ struct PrepArgs {
   int M, P, N, P2;
   int stages, has_pre, sort;
   float sigma, clip;
+  // sug_prepare_batch_aug only (SUG_PREP_SCALE / _PERTURB / _SHIFT); the draws are per cloud
+  const float* scales;      // [B] or null
+  const float* perturb;     // [B, 3] standard normals, or null
+  const float* shifts;      // [B, 3] or null
+  float* scales_out;        // [B] or null
+  float* perturb_out;       // [B, 3] or null
+  float* shifts_out;        // [B, 3] or null
+  float scale_low, scale_high, shift_range, angle_sigma, angle_clip;
 };
+
+constexpr int PREP_AUG_STAGES = SUG_PREP_SCALE | SUG_PREP_PERTURB | SUG_PREP_SHIFT;
 
 __global__ __launch_bounds__(1024) void prepare_batch_kernel(const PrepArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -58,6 +70,7 @@ __global__ __launch_bounds__(1024) void prepare_batch_kernel(const PrepArgs a) {
   unsigned long long* s_key = reinterpret_cast<unsigned long long*>(s_raw + (((size_t)a.P * 12 + 15) & ~(size_t)15));  // [P2] when sort
   __shared__ double s_sum[PREP_MAX_WAVES][3];
   __shared__ float s_max[PREP_MAX_WAVES];
+  __shared__ float s_aug[13];           // per cloud: the scale, the perturbation matrix (row-major), the shift
 
   const int b = blockIdx.x, t = threadIdx.x, T = blockDim.x;
   const int lane = t & (WAVE - 1), wv = t / WAVE, nw = T / WAVE;
@@ -77,6 +90,59 @@ __global__ __launch_bounds__(1024) void prepare_batch_kernel(const PrepArgs a) {
     c0 = (uint32_t)c; c1 = (uint32_t)(c >> 32);
   }
   const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
+  if (t == 0 && ((a.stages & PREP_AUG_STAGES) || a.scales_out || a.perturb_out || a.shifts_out)) {
+    // the per-cloud draws of the three extra stages, by one lane; every lane reads them behind the barrier below
+    float sc = 1.0f, g[3] = {0.0f, 0.0f, 0.0f}, sh[3] = {0.0f, 0.0f, 0.0f};
+    if (a.stages & SUG_PREP_SCALE) {
+      if (a.scales) {
+        sc = a.scales[b];
+      } else {
+        uint32_t w[4];
+        philox4x32_10(c0, c1, (uint32_t)b, SUG_PREP_DRAW_SCALE, k0, k1, w);
+        sc = a.scale_low + u24(w[0]) * (a.scale_high - a.scale_low);
+      }
+    }
+    if (a.stages & SUG_PREP_PERTURB) {
+      if (a.perturb) {
+        g[0] = a.perturb[3 * b + 0]; g[1] = a.perturb[3 * b + 1]; g[2] = a.perturb[3 * b + 2];
+      } else {                                  // the jitter's Box-Muller
+        uint32_t w[4];
+        philox4x32_10(c0, c1, (uint32_t)b, SUG_PREP_DRAW_PERTURB, k0, k1, w);
+        const float r0 = sqrtf(-2.0f * logf(u24_open(w[0]))), r1 = sqrtf(-2.0f * logf(u24_open(w[2])));
+        float s0, q0, s1, q1;
+        sincosf(6.28318530717958647692f * u24(w[1]), &s0, &q0);
+        sincosf(6.28318530717958647692f * u24(w[3]), &s1, &q1);
+        g[0] = r0 * q0; g[1] = r0 * s0; g[2] = r1 * q1;
+      }
+      // R = Rz (Ry Rx) of rotate_perturbation_point_cloud, formed in fp64 from the fp32 normals and rounded once
+      const double lim = (double)a.angle_clip;
+      double sx, cx, sy, cy, sz, cz;
+      sincos(fmin(fmax((double)a.angle_sigma * (double)g[0], -lim), lim), &sx, &cx);
+      sincos(fmin(fmax((double)a.angle_sigma * (double)g[1], -lim), lim), &sy, &cy);
+      sincos(fmin(fmax((double)a.angle_sigma * (double)g[2], -lim), lim), &sz, &cz);
+      const double m0[3] = {cy, sy * sx, sy * cx}, m1[3] = {0.0, cx, -sx}, m2[3] = {-sy, cy * sx, cy * cx};   // Ry Rx
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        s_aug[1 + j] = (float)(cz * m0[j] - sz * m1[j]);
+        s_aug[4 + j] = (float)(sz * m0[j] + cz * m1[j]);
+        s_aug[7 + j] = (float)m2[j];
+      }
+    }
+    if (a.stages & SUG_PREP_SHIFT) {
+      if (a.shifts) {
+        sh[0] = a.shifts[3 * b + 0]; sh[1] = a.shifts[3 * b + 1]; sh[2] = a.shifts[3 * b + 2];
+      } else {
+        uint32_t w[4];
+        philox4x32_10(c0, c1, (uint32_t)b, SUG_PREP_DRAW_SHIFT, k0, k1, w);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) sh[j] = (2.0f * u24(w[j]) - 1.0f) * a.shift_range;
+      }
+    }
+    s_aug[0] = sc; s_aug[10] = sh[0]; s_aug[11] = sh[1]; s_aug[12] = sh[2];
+    if (a.scales_out) a.scales_out[b] = sc;
+    if (a.perturb_out) { a.perturb_out[3 * b + 0] = g[0]; a.perturb_out[3 * b + 1] = g[1]; a.perturb_out[3 * b + 2] = g[2]; }
+    if (a.shifts_out) { a.shifts_out[3 * b + 0] = sh[0]; a.shifts_out[3 * b + 1] = sh[1]; a.shifts_out[3 * b + 2] = sh[2]; }
+  }
   if (a.sort) {                         // subset keys: Philox block q -> points 4q .. 4q+3; past P: last in the order
     for (int q = t; q < a.P2 / 4; q += T) {
       uint32_t w[4];
@@ -191,6 +257,16 @@ __global__ __launch_bounds__(1024) void prepare_batch_kernel(const PrepArgs a) {
         y += fminf(fmaxf(a.sigma * g1, -a.clip), a.clip);
         z += fminf(fmaxf(a.sigma * g2, -a.clip), a.clip);
       }
+      if (a.stages & SUG_PREP_SCALE) {
+        const float sc = s_aug[0];
+        x *= sc; y *= sc; z *= sc;
+      }
+      if (a.stages & SUG_PREP_PERTURB) {        // p . R, as the pre-rotation
+        const float u = (x * s_aug[1] + y * s_aug[4]) + z * s_aug[7], v = (x * s_aug[2] + y * s_aug[5]) + z * s_aug[8],
+                    w = (x * s_aug[3] + y * s_aug[6]) + z * s_aug[9];
+        x = u; y = v; z = w;
+      }
+      if (a.stages & SUG_PREP_SHIFT) { x += s_aug[10]; y += s_aug[11]; z += s_aug[12]; }
     }
     ob[n] = x; ob[N + n] = y; ob[2 * N + n] = z;              // [3, N]: coalesced along N
     if (a.sel_out) a.sel_out[(int64_t)b * N + n] = src;
@@ -203,25 +279,46 @@ __global__ __launch_bounds__(1024) void prepare_batch_kernel(const PrepArgs a) {
 
 }  // namespace
 
-extern "C" int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
-                                 const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
-                                 uint64_t seed, const uint64_t* counter, float sigma, float clip, float* out,
-                                 float* angles_out, float* noise_out, int32_t* sel_out, void* stream) {
-  SUG_REQUIRE(pts && idx && out, "sug_prepare_batch: null pointer (pts, idx and out are required)");
-  SUG_REQUIRE(B > 0, "sug_prepare_batch: B=%d: an empty batch", B);
-  SUG_REQUIRE(M > 0 && P > 0 && N > 0, "sug_prepare_batch: bad shape M=%d P=%d N=%d", M, P, N);
-  SUG_REQUIRE(P <= PREP_MAX_P, "sug_prepare_batch: P=%d > %d points per cloud", P, PREP_MAX_P);
-  SUG_REQUIRE(2 * (int64_t)N <= 3 * (int64_t)P, "sug_prepare_batch: too few points: N=%d > 1.5 * P=%d", N, P);
-  SUG_REQUIRE((stages & ~(SUG_PREP_NORMALIZE | SUG_PREP_ROTATE_Z | SUG_PREP_JITTER | SUG_PREP_SHUFFLE)) == 0,
-              "sug_prepare_batch: unknown bits in stages=%d", stages);
-  SUG_REQUIRE(!sel || N <= P, "sug_prepare_batch: sel given but N=%d > P=%d (padding rows have no source point)", N, P);
+// The checks and the launch of both entry points; `fn` names the caller in the messages, `known` are its stage bits.
+static int prepare_launch(const char* fn, int known, const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
+                          const float* pre_rot, const float* angles, const float* noise, const int32_t* sel, const float* scales,
+                          const float* perturb, const float* shifts, uint64_t seed, const uint64_t* counter, float sigma,
+                          float clip, const float* aug, float* out, float* angles_out, float* noise_out, int32_t* sel_out,
+                          float* scales_out, float* perturb_out, float* shifts_out, void* stream) {
+  SUG_REQUIRE(pts && idx && out, "%s: null pointer (pts, idx and out are required)", fn);
+  SUG_REQUIRE(B > 0, "%s: B=%d: an empty batch", fn, B);
+  SUG_REQUIRE(M > 0 && P > 0 && N > 0, "%s: bad shape M=%d P=%d N=%d", fn, M, P, N);
+  SUG_REQUIRE(P <= PREP_MAX_P, "%s: P=%d > %d points per cloud", fn, P, PREP_MAX_P);
+  SUG_REQUIRE(2 * (int64_t)N <= 3 * (int64_t)P, "%s: too few points: N=%d > 1.5 * P=%d", fn, N, P);
+  SUG_REQUIRE((stages & ~known) == 0, "%s: unknown bits in stages=%d", fn, stages);
+  SUG_REQUIRE(!sel || N <= P, "%s: sel given but N=%d > P=%d (padding rows have no source point)", fn, N, P);
   const bool sort = !sel && (P > N || (P == N && (stages & SUG_PREP_SHUFFLE)));
-  const bool draws = sort || ((stages & SUG_PREP_ROTATE_Z) && !angles) || ((stages & SUG_PREP_JITTER) && !noise);
-  SUG_REQUIRE(!draws || counter, "sug_prepare_batch: null counter: in-kernel draws need the device batch counter");
-  SUG_REQUIRE(sigma >= 0.f && clip >= 0.f, "sug_prepare_batch: sigma and clip must not be negative");
+  const bool draws = sort || ((stages & SUG_PREP_ROTATE_Z) && !angles) || ((stages & SUG_PREP_JITTER) && !noise) ||
+                     ((stages & SUG_PREP_SCALE) && !scales) || ((stages & SUG_PREP_PERTURB) && !perturb) ||
+                     ((stages & SUG_PREP_SHIFT) && !shifts);
+  SUG_REQUIRE(!draws || counter, "%s: null counter: in-kernel draws need the device batch counter", fn);
+  SUG_REQUIRE(sigma >= 0.f && clip >= 0.f, "%s: sigma and clip must not be negative", fn);
   PrepArgs a;
+  a.scale_low = a.scale_high = 1.f; a.shift_range = a.angle_sigma = a.angle_clip = 0.f;
+  if (stages & PREP_AUG_STAGES) {
+    SUG_REQUIRE(aug, "%s: null aug_params: the scale, perturbation and shift stages need their %d parameters", fn,
+                SUG_PREP_AUG_PARAMS);
+    a.scale_low = aug[SUG_PREP_AUG_SCALE_LOW]; a.scale_high = aug[SUG_PREP_AUG_SCALE_HIGH];
+    a.shift_range = aug[SUG_PREP_AUG_SHIFT_RANGE];
+    a.angle_sigma = aug[SUG_PREP_AUG_ANGLE_SIGMA]; a.angle_clip = aug[SUG_PREP_AUG_ANGLE_CLIP];
+    SUG_REQUIRE(std::isfinite(a.scale_low) && std::isfinite(a.scale_high) && a.scale_low > 0.f && a.scale_low <= a.scale_high,
+                "%s: scale_low=%g, scale_high=%g: need finite 0 < scale_low <= scale_high", fn, a.scale_low, a.scale_high);
+    SUG_REQUIRE(a.shift_range >= 0.f && std::isfinite(a.shift_range), "%s: shift_range=%g must be finite and not negative", fn,
+                a.shift_range);
+    SUG_REQUIRE(a.angle_sigma >= 0.f && std::isfinite(a.angle_sigma), "%s: angle_sigma=%g must be finite and not negative", fn,
+                a.angle_sigma);
+    SUG_REQUIRE(a.angle_clip >= 0.f && std::isfinite(a.angle_clip), "%s: angle_clip=%g must be finite and not negative", fn,
+                a.angle_clip);
+  }
   a.pts = pts; a.idx = idx; a.angles = angles; a.noise = noise; a.sel = sel; a.counter = draws ? counter : nullptr;
   a.out = out; a.angles_out = angles_out; a.noise_out = noise_out; a.sel_out = sel_out;
+  a.scales = scales; a.perturb = perturb; a.shifts = shifts;
+  a.scales_out = scales_out; a.perturb_out = perturb_out; a.shifts_out = shifts_out;
   for (int i = 0; i < 9; ++i) a.pre[i] = pre_rot ? pre_rot[i] : (i % 4 == 0 ? 1.f : 0.f);
   a.seed = seed; a.M = M; a.P = P; a.N = N;
   int P2 = 128;                 // sort slots: a power of two, whole 128-slot chunks
@@ -231,10 +328,31 @@ extern "C" int sug_prepare_batch(const float* pts, int M, int P, const int32_t* 
   const size_t sh = (((size_t)P * 12 + 15) & ~(size_t)15) + (sort ? (size_t)P2 * 8 : 0);
   if (sh > 64 * 1024) {
     static SugLdsOptIn note;
-    if (int rc = sug_allow_dynamic_lds(note, &prepare_batch_kernel, 96 * 1024, "sug_prepare_batch")) return rc;
+    if (int rc = sug_allow_dynamic_lds(note, &prepare_batch_kernel, 96 * 1024, fn)) return rc;
   }
   const int threads = P <= 256 ? 256 : (P <= 1024 ? 512 : 1024);
   hipLaunchKernelGGL(prepare_batch_kernel, dim3(B), dim3(threads), sh, (hipStream_t)stream, a);
-  SUG_LAUNCH_CHECK("sug_prepare_batch");
+  SUG_LAUNCH_CHECK(fn);
   return SUG_OK;
+}
+
+extern "C" int sug_prepare_batch(const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
+                                 const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
+                                 uint64_t seed, const uint64_t* counter, float sigma, float clip, float* out,
+                                 float* angles_out, float* noise_out, int32_t* sel_out, void* stream) {
+  return prepare_launch("sug_prepare_batch", SUG_PREP_NORMALIZE | SUG_PREP_ROTATE_Z | SUG_PREP_JITTER | SUG_PREP_SHUFFLE, pts, M, P,
+                        idx, B, N, stages, pre_rot, angles, noise, sel, nullptr, nullptr, nullptr, seed, counter, sigma, clip,
+                        nullptr, out, angles_out, noise_out, sel_out, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int sug_prepare_batch_aug(const float* pts, int M, int P, const int32_t* idx, int B, int N, int stages,
+                                     const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
+                                     const float* scales, const float* perturb, const float* shifts, uint64_t seed,
+                                     const uint64_t* counter, float sigma, float clip, const float* aug_params, float* out,
+                                     float* angles_out, float* noise_out, int32_t* sel_out, float* scales_out,
+                                     float* perturb_out, float* shifts_out, void* stream) {
+  return prepare_launch("sug_prepare_batch_aug",
+                        SUG_PREP_NORMALIZE | SUG_PREP_ROTATE_Z | SUG_PREP_JITTER | SUG_PREP_SHUFFLE | PREP_AUG_STAGES, pts, M, P, idx,
+                        B, N, stages, pre_rot, angles, noise, sel, scales, perturb, shifts, seed, counter, sigma, clip, aug_params,
+                        out, angles_out, noise_out, sel_out, scales_out, perturb_out, shifts_out, stream);
 }

@@ -3946,6 +3946,63 @@ def prepare_batch(pts, idx, num_points, pre_rotate, aug, *, angles=None, noise=N
     return (out, a_out, n_out, s_out) if return_draws else out
 
 
+PREP_SCALE, PREP_PERTURB, PREP_SHIFT, PREP_AUG_PARAMS = (                               # sug_prepare_batch_aug's extra stages
+    _H['SUG_PREP_' + _n] for _n in ('SCALE', 'PERTURB', 'SHIFT', 'AUG_PARAMS'))
+_PREP_AUG_SLOTS = tuple(_H['SUG_PREP_AUG_' + _n] for _n in ('SCALE_LOW', 'SCALE_HIGH', 'SHIFT_RANGE', 'ANGLE_SIGMA', 'ANGLE_CLIP'))
+
+
+def prepare_batch_aug(pts, idx, num_points, pre_rotate, aug, *, angles=None, noise=None, sel=None, scales=None, perturb=None,
+                      shifts=None, seed=None, counter=None, out=None, sigma=0.01, clip=0.05, scale_low=0.8, scale_high=1.25,
+                      shift_range=0.1, angle_sigma=0.06, angle_clip=0.18, return_draws=False, stages=None, pre_matrix=None):
+    """prepare_batch with the scale, rotation-perturbation and shift stages (sug_prepare_batch_aug), applied behind the
+    jitter in pc_augment's line order.  `stages` selects the stage bits (default: prepare_batch's, i.e. none of the three
+    new ones; add PREP_SCALE | PREP_PERTURB | PREP_SHIFT).  The per-cloud draws come from `scales` [B] (the factor),
+    `perturb` [B,3] (standard normals, scaled by angle_sigma and clipped to +-angle_clip in the kernel) and `shifts` [B,3]
+    (the vector) when given, else from the in-kernel generator at (`seed`, `counter`).  return_draws: (out, angles [B],
+    noise [B,N,3], sel [B,N], scales [B], perturb [B,3], shifts [B,3]).  No host synchronisation; with `out` and `counter`
+    given the call is one kernel launch and can be captured."""
+    _need_gpu(pts, idx, angles, noise, sel, scales, perturb, shifts, counter, out)
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise ValueError('prepare_batch_aug: pts must be a contiguous fp32 [M, P, 3] tensor, got %s %s' % (tuple(pts.shape), pts.dtype))
+    if idx.dim() != 1 or idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise ValueError('prepare_batch_aug: idx must be a contiguous int32 [B] tensor')
+    M, P, _ = pts.shape
+    B, N = idx.shape[0], int(num_points)
+    dev = pts.device
+    if stages is None:
+        stages = PREP_NORMALIZE | ((PREP_ROTATE_Z | PREP_JITTER) if aug else 0)
+    if pre_matrix is None and pre_rotate:
+        pre_matrix = _PRE_ROTATE_X
+    pre = (ctypes.c_float * 9)(*pre_matrix) if pre_matrix is not None else None
+    params = (ctypes.c_float * PREP_AUG_PARAMS)()
+    for slot, v in zip(_PREP_AUG_SLOTS, (scale_low, scale_high, shift_range, angle_sigma, angle_clip)):
+        params[slot] = v
+
+    def given(t, shape, dtype, name):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError('prepare_batch_aug: %s must be a contiguous %s tensor of shape %s, got %s %s'
+                             % (name, dtype, shape, t.dtype, tuple(t.shape)))
+    given(angles, (B,), torch.float32, 'angles')
+    given(noise, (B, P, 3), torch.float32, 'noise')
+    given(sel, (B, N), torch.int32, 'sel')
+    given(scales, (B,), torch.float32, 'scales')
+    given(perturb, (B, 3), torch.float32, 'perturb')
+    given(shifts, (B, 3), torch.float32, 'shifts')
+    given(out, (B, 3, N), torch.float32, 'out')
+    given(counter, (1,), torch.int64, 'counter')
+    if out is None:
+        out = torch.empty(B, 3, N, dtype=torch.float32, device=dev)
+    draws = [None] * 6
+    if return_draws:
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        draws = [f32(B), f32(B, N, 3), torch.empty(B, N, dtype=torch.int32, device=dev), f32(B), f32(B, 3), f32(B, 3)]
+    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(lib().sug_prepare_batch_aug(_p(pts), M, P, _p(idx), B, N, stages, pre, _p(angles), _p(noise), _p(sel), _p(scales),
+                                      _p(perturb), _p(shifts), seed, _p(counter), sigma, clip, params, _p(out),
+                                      *[_p(d) for d in draws], _st()), 'sug_prepare_batch_aug')
+    return (out, *draws) if return_draws else out
+
+
 # ----------------------------------------------------------------------------- sub-domain splitter
 ICP_MAX_POINTS = _H['SUG_ICP_MAX_POINTS']
 

@@ -1,4 +1,5 @@
-"""The two helpers of utils/common_utils.py that model/mmd.py calls."""
+"""The two helpers of utils/common_utils.py that model/mmd.py calls, and get_dist_info for
+data/dataloader.py's build_dataloader."""
 import weakref
 
 import torch
@@ -22,6 +23,19 @@ def create_one_hot_labels(original_labels, num_class=10):
         _one_hot_cache.clear()
     _one_hot_cache[id(original_labels)] = (weakref.ref(original_labels), key, one_hot)
     return one_hot
+
+
+def get_dist_info(return_gpu_per_machine=False):
+    """utils/common_utils.py:14-33: (rank, world_size) of the default process group, (0, 1) when there is none; with
+    return_gpu_per_machine also the number of visible devices."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world_size = dist.get_rank(), dist.get_world_size()
+    else:
+        rank, world_size = 0, 1
+    if return_gpu_per_machine:
+        return rank, world_size, torch.cuda.device_count()
+    return rank, world_size
 
 
 def get_most_overlapped_element(vec_a, vec_b, num_class=10):
