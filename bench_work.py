@@ -58,13 +58,21 @@ def _edgeconv(acc, clouds, N, C, Co, k, train):
     acc.add('edgeconv_%dto%d' % (C, Co), f * (3 if train else 1), b * (3 if train else 1))
 
 
-def _adapt(acc, clouds, N, train):
-    """SA-node module (model_utils.py:92-128): FPS(64), ball query, offset prediction, 64-NN, residual conv, 3-NN interp."""
+def _adapt(acc, clouds, N, train, shared_half=False):
+    """SA-node module (model_utils.py:92-128): FPS(64), ball query, offset prediction, 64-NN, residual conv, 3-NN interp.
+    shared_half: the offset projection and the residual layer read the shared prefix and the weights only -- an earlier pass
+    of the step has computed their forward values (DGCNN's node pass): the forwards are not counted again, the residual
+    layer's backward (input + weight gradient, 2x the forward) still runs per pass; the node pass sends no gradient into the
+    projection."""
     acc.add('fps_64', clouds * 8.0 * N * 64, clouds * (12.0 * N + 4 * 64))
     acc.add('ball_query_64', clouds * 8.0 * N * 64, clouds * (12.0 * N + 12 * 64 + 4 * 64 * 64))
     acc.add('knn_query_64', clouds * 8.0 * N * 64, clouds * (12.0 * N + 12 * 64 + 4 * 64 * 64))
-    _dense(acc, 'adapt.pred_offset', clouds * N, 64, 3, train)
-    _dense(acc, 'adapt.residual', clouds * N, 64, 64, train)
+    if not shared_half:
+        _dense(acc, 'adapt.pred_offset', clouds * N, 64, 3, train)
+        _dense(acc, 'adapt.residual', clouds * N, 64, 64, train)
+    elif train:
+        rows = clouds * N
+        acc.add('adapt.residual', 2 * 2.0 * rows * 64 * 64, 2 * (rows * (64 * 4 + 64 * 4) + 4.0 * 64 * 64))
     acc.add('adapt.group+interp', clouds * N * 64 * 8.0, clouds * N * (64 + 128 + 3 * 2) * 4.0 * (3 if train else 1))
 
 
@@ -95,7 +103,9 @@ def _dgcnn(acc, clouds, N, k, node_pass):
         _edgeconv(acc, clouds, N, 3, 64, k, True)
         _knn(acc, clouds, N, 64, k)
         _edgeconv(acc, clouds, N, 64, 64, k, True)
-    _adapt(acc, clouds, N, True)                        # (node pass: its outputs carry the geometric MMD's gradient)
+    # (node pass: its outputs carry the geometric MMD's gradient; the SA-node module's offset projection and residual layer
+    # belong to the shared prefix)
+    _adapt(acc, clouds, N, True, shared_half=node_pass)
     _dense(acc, 'conv1d', clouds * N, 128, 64, tr)
     _knn(acc, clouds, N, 64, k)
     _edgeconv(acc, clouds, N, 64, 128, k, tr)

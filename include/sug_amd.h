@@ -165,6 +165,10 @@ int sug_scatter_rows_ordered(const float* g, int64_t ldg, const int32_t* idx, in
  * (replaces index_points + torch.max(dim=-1), model/model_utils.py:122-123). */
 int sug_group_max(const float* feat, int64_t ldf, const int32_t* idx, int B, int N, int S,
                   int ns, int C, float* out, int32_t* arg, void* stream);
+/* The same over B = P * Bsrc "virtual clouds" (pass-major) that share the Bsrc clouds of feat: cloud b reads
+ * feat[b % Bsrc] (the semantic and the node pass of a step in one launch; sug_group_max is the case Bsrc == B). */
+int sug_group_max_shared(const float* feat, int64_t ldf, int Bsrc, const int32_t* idx, int B, int N, int S,
+                         int ns, int C, float* out, int32_t* arg, void* stream);
 /* Backward: dfeat[b, arg[b,s,c], c] += g[b,s,c].  CONTRACT: dfeat [B, N, ldf] must be ZERO-FILLED by the caller; it is not an
  * accumulate-into entry point.  (S <= 64: a fixed-order kernel that STORES the sums of the touched entries; otherwise float
  * atomics that ADD -- identical on a zeroed buffer, unspecified on any other.) */
@@ -408,6 +412,11 @@ int sug_node_offset_fwd(const float* proj, const float* loc, const int32_t* fidx
 int sug_node_offset_bwd(const float* proj, const float* loc, const int32_t* fidx,
                         const int32_t* gidx, const float* goff, int B, int N, int S, int ns,
                         float* dproj, void* stream);
+/* Forward over B = P * Bsrc pass-major virtual clouds: loc / fidx / gidx / off / nloc are [B,...], proj is [Bsrc,N,3]
+ * and cloud b reads proj[b % Bsrc].  Same lanes and order per cloud as sug_node_offset_fwd (the case Bsrc == B). */
+int sug_node_offset_fwd_shared(const float* proj, int Bsrc, const float* loc, const int32_t* fidx,
+                               const int32_t* gidx, int B, int N, int S, int ns, float* off, float* nloc,
+                               void* stream);
 /* out[b,n,:] = [ fea[b,n,0:C1] | sum_t w_t * node[b, idx3[b,n,t], 0:C2] ] with the inverse-distance
  * weights of upsample_inter (model/point_utils.py:156-162) from the 3-NN distances d3 (C1 == 0: fea may be null).
  * Backward (g = d out): dnode [B,S,C2] and dnloc [B,S,3] (both zero-initialised by the caller,
@@ -415,6 +424,11 @@ int sug_node_offset_bwd(const float* proj, const float* loc, const int32_t* fidx
 int sug_interp3_cat_fwd(const float* fea, int64_t ldf, int C1, const float* node,
                         const int32_t* idx3, const float* d3, int B, int N, int S, int C2,
                         float* out, int64_t ldo, void* stream);
+/* Forward over B = P * Bsrc pass-major virtual clouds: node / idx3 / d3 / out are [B,...], fea is [Bsrc,N,ldf] and
+ * cloud b copies fea[b % Bsrc] (sug_interp3_cat_fwd is the case Bsrc == B). */
+int sug_interp3_cat_fwd_shared(const float* fea, int64_t ldf, int C1, int Bsrc, const float* node,
+                               const int32_t* idx3, const float* d3, int B, int N, int S, int C2,
+                               float* out, int64_t ldo, void* stream);
 int sug_interp3_cat_bwd(const float* g, int64_t ldg, int C1, const float* node, const int32_t* idx3,
                         const float* d3, const float* xyz, const float* nloc, int B, int N, int S,
                         int C2, float* dnode, float* dnloc, void* stream);

@@ -16,8 +16,9 @@ module keeps the caller's code unchanged and removes the host from the picture:
     since the caller's zero_grad() IS the static gradient tensor (no copy), later ones are added in one multi-tensor launch:
     no `AccumulateGrad` node, no `at::add` per parameter and call;
   * two calls on the same batch share the encoder prefix as the eager form does (`share_prefix = 'auto'`): the first call's
-    graph exposes the prefix tensors as hidden outputs of its Function, the second call's graph was captured reading them in
-    place, its backward hands the prefix gradients to the first call's backward through autograd;
+    graph exposes the prefix tensors as hidden outputs of its Function (and, as `prefix_extra`, static values the second call
+    reads without autograd: recorded BatchNorm statistics, DGCNN's SA-node forward values), the second call's graph was
+    captured reading them in place, its backward hands the prefix gradients to the first call's backward through autograd;
   * as many graph instances per key as calls are in flight between two backwards (source and target semantic pass = two
     instances of one key); an instance is reused once its backward has run (or its outputs were dropped).
 

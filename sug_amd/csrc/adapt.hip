@@ -15,14 +15,14 @@ __global__ __launch_bounds__(256) void node_offset_fwd_kernel(const float* __res
                                                               const float* __restrict__ loc,
                                                               const int32_t* __restrict__ fidx,
                                                               const int32_t* __restrict__ gidx, int N,
-                                                              int S, int ns, int total,
+                                                              int S, int ns, int total, int Bsrc,
                                                               float* __restrict__ off,
                                                               float* __restrict__ nloc) {
   const int e = blockIdx.x * 4 + (threadIdx.x >> 6);  // (b, s)
   if (e >= total) return;
   const int lane = threadIdx.x & 63;
   const int b = e / S;
-  const float* pb = proj + (int64_t)b * N * 3;
+  const float* pb = proj + (int64_t)(b % Bsrc) * N * 3;   // proj of cloud b % Bsrc (the passes of a step share it)
   const float* lb = loc + (int64_t)b * N * 3;
   int f = fidx[e];
   f = f < 0 ? 0 : (f >= N ? N - 1 : f);
@@ -273,12 +273,13 @@ __global__ __launch_bounds__(256) void interp3_cat_fwd_kernel(const float* __res
                                                               int C1, const float* __restrict__ node,
                                                               const int32_t* __restrict__ idx3,
                                                               const float* __restrict__ d3, int N, int S,
-                                                              int C2, int64_t BN, float* __restrict__ out,
-                                                              int64_t ldo) {
+                                                              int C2, int64_t BN, int64_t BNsrc,
+                                                              float* __restrict__ out, int64_t ldo) {
   const int64_t p = (int64_t)blockIdx.x * 16 + threadIdx.x / 16;
   if (p >= BN) return;
   const int lane = threadIdx.x & 15;
   const int64_t b = p / N;
+  const int64_t ps = p % BNsrc;                       // fea row of cloud b % B_src (the passes of a step share fea)
   const float r0 = 1.0f / fmaxf(d3[p * 3 + 0], 1e-10f), r1 = 1.0f / fmaxf(d3[p * 3 + 1], 1e-10f),
               r2 = 1.0f / fmaxf(d3[p * 3 + 2], 1e-10f);
   const float R = (r0 + r1) + r2;
@@ -287,7 +288,7 @@ __global__ __launch_bounds__(256) void interp3_cat_fwd_kernel(const float* __res
   const float* n1 = node + (b * S + idx3[p * 3 + 1]) * C2;
   const float* n2 = node + (b * S + idx3[p * 3 + 2]) * C2;
   for (int c = lane * 4; c < C1; c += 64)
-    *reinterpret_cast<float4*>(out + p * ldo + c) = *reinterpret_cast<const float4*>(fea + p * ldf + c);
+    *reinterpret_cast<float4*>(out + p * ldo + c) = *reinterpret_cast<const float4*>(fea + ps * ldf + c);
   for (int c = lane * 4; c < C2; c += 64) {
     const float4 a = *reinterpret_cast<const float4*>(n0 + c), bq = *reinterpret_cast<const float4*>(n1 + c),
                  cq = *reinterpret_cast<const float4*>(n2 + c);
@@ -476,16 +477,24 @@ __global__ __launch_bounds__(256) void interp3_bwd_node_kernel(const float* __re
 
 }  // namespace
 
+extern "C" int sug_node_offset_fwd_shared(const float* proj, int Bsrc, const float* loc, const int32_t* fidx,
+                                          const int32_t* gidx, int B, int N, int S, int ns, float* off,
+                                          float* nloc, void* stream) {
+  SUG_REQUIRE(proj && loc && fidx && gidx && off && nloc, "sug_node_offset_fwd: null pointer");
+  SUG_REQUIRE(B > 0 && N > 0 && S > 0 && ns > 0, "sug_node_offset_fwd: bad shape");
+  SUG_REQUIRE(Bsrc > 0 && B % Bsrc == 0, "sug_node_offset_fwd: %d clouds are not whole passes over %d source clouds", B, Bsrc);
+  SUG_REQUIRE((int64_t)B * S <= INT32_MAX, "sug_node_offset_fwd: B*S too large");
+  const int total = B * S;
+  hipLaunchKernelGGL(node_offset_fwd_kernel, dim3(sug_divup(total, 4)), dim3(256), 0, (hipStream_t)stream,
+                     proj, loc, fidx, gidx, N, S, ns, total, Bsrc, off, nloc);
+  SUG_LAUNCH_CHECK("sug_node_offset_fwd");
+  return SUG_OK;
+}
+
 extern "C" int sug_node_offset_fwd(const float* proj, const float* loc, const int32_t* fidx,
                                    const int32_t* gidx, int B, int N, int S, int ns, float* off,
                                    float* nloc, void* stream) {
-  SUG_REQUIRE(proj && loc && fidx && gidx && off && nloc, "sug_node_offset_fwd: null pointer");
-  SUG_REQUIRE(B > 0 && N > 0 && S > 0 && ns > 0, "sug_node_offset_fwd: bad shape");
-  const int total = B * S;
-  hipLaunchKernelGGL(node_offset_fwd_kernel, dim3(sug_divup(total, 4)), dim3(256), 0, (hipStream_t)stream,
-                     proj, loc, fidx, gidx, N, S, ns, total, off, nloc);
-  SUG_LAUNCH_CHECK("sug_node_offset_fwd");
-  return SUG_OK;
+  return sug_node_offset_fwd_shared(proj, B, loc, fidx, gidx, B, N, S, ns, off, nloc, stream);
 }
 
 extern "C" int sug_node_offset_bwd(const float* proj, const float* loc, const int32_t* fidx,
@@ -542,20 +551,27 @@ extern "C" int sug_node_offset_bwd(const float* proj, const float* loc, const in
   return SUG_OK;
 }
 
-extern "C" int sug_interp3_cat_fwd(const float* fea, int64_t ldf, int C1, const float* node,
-                                   const int32_t* idx3, const float* d3, int B, int N, int S, int C2,
-                                   float* out, int64_t ldo, void* stream) {
+extern "C" int sug_interp3_cat_fwd_shared(const float* fea, int64_t ldf, int C1, int Bsrc, const float* node,
+                                          const int32_t* idx3, const float* d3, int B, int N, int S, int C2,
+                                          float* out, int64_t ldo, void* stream) {
   SUG_REQUIRE((fea || C1 == 0) && node && idx3 && d3 && out, "sug_interp3_cat_fwd: null pointer");
   SUG_REQUIRE(B > 0 && N > 0 && S >= 3 && C1 >= 0 && C2 > 0 && C1 % 4 == 0 && C2 % 4 == 0 && ldf % 4 == 0 &&
                   ldo % 4 == 0 && ldo >= C1 + C2 && ldf >= C1,
               "sug_interp3_cat_fwd: bad shape (channel counts and strides must be multiples of 4)");
+  SUG_REQUIRE(Bsrc > 0 && B % Bsrc == 0, "sug_interp3_cat_fwd: %d clouds are not whole passes over %d source clouds", B, Bsrc);
   SUG_REQUIRE(((uintptr_t)fea % 16 == 0) && ((uintptr_t)node % 16 == 0) && ((uintptr_t)out % 16 == 0),
               "sug_interp3_cat_fwd: pointers must be 16-byte aligned");
   const int64_t BN = (int64_t)B * N;
   hipLaunchKernelGGL(interp3_cat_fwd_kernel, dim3(sug_divup(BN, 16)), dim3(256), 0, (hipStream_t)stream, fea,
-                     ldf, C1, node, idx3, d3, N, S, C2, BN, out, ldo);
+                     ldf, C1, node, idx3, d3, N, S, C2, BN, (int64_t)Bsrc * N, out, ldo);
   SUG_LAUNCH_CHECK("sug_interp3_cat_fwd");
   return SUG_OK;
+}
+
+extern "C" int sug_interp3_cat_fwd(const float* fea, int64_t ldf, int C1, const float* node,
+                                   const int32_t* idx3, const float* d3, int B, int N, int S, int C2,
+                                   float* out, int64_t ldo, void* stream) {
+  return sug_interp3_cat_fwd_shared(fea, ldf, C1, B, node, idx3, d3, B, N, S, C2, out, ldo, stream);
 }
 
 extern "C" int sug_interp3_cat_bwd(const float* g, int64_t ldg, int C1, const float* node,

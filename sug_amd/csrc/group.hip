@@ -35,13 +35,13 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* __re
 
 __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict__ feat, int64_t ldf,
                                                         const int32_t* __restrict__ idx, int N, int S,
-                                                        int ns, int C, int64_t total,
+                                                        int ns, int C, int64_t total, int Bsrc,
                                                         float* __restrict__ out,
                                                         int32_t* __restrict__ arg) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c = (int)(e % C);
     const int64_t row = e / C;  // b*S + s
-    const int b = (int)(row / S);
+    const int b = (int)(row / S) % Bsrc;     // feat of cloud b % Bsrc (the passes of a step share it)
     const int32_t* ir = idx + row * ns;
     float best = -INFINITY;
     int bj = -1;
@@ -239,15 +239,21 @@ extern "C" int sug_scatter_rows_ordered(const float* g, int64_t ldg, const int32
   return SUG_OK;
 }
 
-extern "C" int sug_group_max(const float* feat, int64_t ldf, const int32_t* idx, int B, int N, int S,
-                             int ns, int C, float* out, int32_t* arg, void* stream) {
+extern "C" int sug_group_max_shared(const float* feat, int64_t ldf, int Bsrc, const int32_t* idx, int B, int N, int S,
+                                    int ns, int C, float* out, int32_t* arg, void* stream) {
   SUG_REQUIRE(feat && idx && out && arg, "sug_group_max: null pointer");
   SUG_REQUIRE(B > 0 && N > 0 && S > 0 && ns > 0 && C > 0 && ldf >= C, "sug_group_max: bad shape");
+  SUG_REQUIRE(Bsrc > 0 && B % Bsrc == 0, "sug_group_max: %d clouds are not whole passes over %d source clouds", B, Bsrc);
   const int64_t total = (int64_t)B * S * C;
   hipLaunchKernelGGL(group_max_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, feat,
-                     ldf, idx, N, S, ns, C, total, out, arg);
+                     ldf, idx, N, S, ns, C, total, Bsrc, out, arg);
   SUG_LAUNCH_CHECK("sug_group_max");
   return SUG_OK;
+}
+
+extern "C" int sug_group_max(const float* feat, int64_t ldf, const int32_t* idx, int B, int N, int S,
+                             int ns, int C, float* out, int32_t* arg, void* stream) {
+  return sug_group_max_shared(feat, ldf, B, idx, B, N, S, ns, C, out, arg, stream);
 }
 
 extern "C" int sug_group_max_bwd(const float* g, const int32_t* arg, int B, int N, int S, int C,

@@ -41,6 +41,8 @@ class _PrefixEntry:
         # the hook must not reference this entry (entry -> tensor -> grad_fn -> hook -> entry would be a cycle, and the
         # cached tensors -- graph-pool memory under hipGraph capture -- would wait for the cyclic collector)
         self._flag = flag = [True]
+        # DGCNN: the SharedHalf of the SA-node module built from `extra` (forward values only); None until a hit asks
+        self.shared = None
         last = tensors[-1]
         if last.requires_grad:
             last.register_hook(lambda grad, f=flag: f.__setitem__(0, False))
@@ -105,7 +107,7 @@ class _PrefixSharing:
 
 def _dead_prefix_entry():
     e = _PrefixEntry.__new__(_PrefixEntry)
-    e.tensors, e.extra, e._source, e._flag, e._live, e.provider = (), None, None, [False], None, None
+    e.tensors, e.extra, e._source, e._flag, e._live, e.provider, e.shared = (), None, None, [False], None, None, None
     return e
 
 
@@ -182,32 +184,51 @@ class DGCNN(nn.Module, _PrefixSharing):
         # one training step run the encoder twice on the same batch with the same weights; the
         # stage in front of the SA-node module (kNN + conv1, kNN + conv2) is then bit-identical
         # in both passes (train-mode BN uses batch statistics, no dropout, deterministic
-        # kernels), so the second pass reuses it and only replays the BN running-stat update.
+        # kernels), so the second pass reuses it and only replays the BN running-stat update.  The two stages of the
+        # SA-node module that read that stage's output and the weights only (offset projection, residual layer) have
+        # the same forward values too: the second pass takes them over and keeps its own backward through them.
         # Requires a single backward over both passes (the graph of the prefix is shared).
         self.share_prefix = 'auto'
         self._prefix_cache = {}
 
     def _prefix_params(self):
-        return [p for m in (self.conv1, self.conv2) for p in m.parameters()]
+        # the forward values of the SA-node module's pass-invariant half (offset projection, residual layer) ride on the entry
+        return [p for m in (self.conv1, self.conv2) for p in m.parameters()] + self.node_fea_adapt.shared_params()
 
     def _prefix(self, x, loc, nb, out1=None, wc=(None, None)):
-        """kNN + conv1, kNN + conv2.  out1: where conv1's activations should be written (a column
-        slice of the conv5 input buffer); a cache hit returns the tensors of the earlier pass instead."""
+        """kNN + conv1, kNN + conv2 -> (x1, x2, shared, miss).  out1: where conv1's activations should be written (a column
+        slice of the conv5 input buffer); a cache hit returns the tensors of the earlier pass instead.  shared: None
+        (no sharing), or the SharedHalf for node_fea_adapt.rows -- filled on a hit, empty on a miss.  miss: on a miss the
+        two layers' recorded statistics; _keep_prefix stores the entry once rows() has filled `shared`.
+        The entry: tensors (x1, x2), shared through autograd; extra (st1, st2, st_res, proj, y, res): recorded BatchNorm
+        statistics and the detached forward values of the SA-node module's offset projection and residual layer."""
         if not _sharing_on(self.share_prefix, self.training):
             x1 = self.conv1.edge_rows(loc, nb(loc, 0), out=out1, wcat=wc[0])
-            return x1, self.conv2.edge_rows(x1, nb(x1, 1), wcat=wc[1])
+            return x1, self.conv2.edge_rows(x1, nb(x1, 1), wcat=wc[1]), None, None
         key = self._prefix_key(x)
         hit = self._prefix_cache.get(key)
         if hit is not None and hit.serves(x):
             x1, x2 = hit.tensors
-            st1, st2 = hit.extra
-            ops.replay_bn_stats([(self.conv1.conv[1], st1), (self.conv2.conv[1], st2)])     # both layers' updates, one launch
-            return x1, x2
+            st1, st2, st_res, proj, y, res = hit.extra
+            if st_res is None:                  # the SA-node half could not be recorded: only the two EdgeConv layers
+                ops.replay_bn_stats([(self.conv1.conv[1], st1), (self.conv2.conv[1], st2)])
+                return x1, x2, None, None
+            # the three layers' running-statistics updates, one launch
+            bn_res = self.node_fea_adapt.residual.conv[1]
+            ops.replay_bn_stats([(self.conv1.conv[1], st1), (self.conv2.conv[1], st2), (bn_res, st_res)])
+            if hit.shared is None:              # an entry installed from outside (call graphs): tensors and extra only
+                hit.shared = _mu.SharedHalf(proj, y, res, [(bn_res, st_res)])
+            return x1, x2, hit.shared, None
         x1, st1 = self.conv1.edge_rows(loc, nb(loc, 0), return_stats=True, out=out1, wcat=wc[0])
         x2, st2 = self.conv2.edge_rows(x1, nb(x1, 1), return_stats=True, wcat=wc[1])
+        return x1, x2, _mu.SharedHalf(), (st1, st2)
+
+    def _keep_prefix(self, x, x1, x2, shared, st12):
+        """After node_fea_adapt.rows has filled `shared` on a miss: the prefix entry of this batch."""
+        half = (shared.stats[0][1], shared.proj, shared.y, shared.res) if shared.filled else (None,) * 4
         self._prune_prefix_cache()                  # a step has two inputs; never grow unbounded
-        self._prefix_cache[key] = _PrefixEntry((x1, x2), (st1, st2), source=x)
-        return x1, x2
+        e = self._prefix_cache[self._prefix_key(x)] = _PrefixEntry((x1, x2), st12 + half, source=x)
+        e.shared = shared if shared.filled else None
 
     def plan_geometry(self, x, passes, groups=1):
         """FPS + ball query of the SA-node module for `passes` forwards over the same batch, in one set of launches."""
@@ -229,8 +250,10 @@ class DGCNN(nn.Module, _PrefixSharing):
         cat_in = torch.empty(B, N, 512, dtype=torch.float32, device=x.device)
         # the [W1 ; W2-W1] operands of the four EdgeConv layers in one launch (one more in the backward)
         wc = edge_wcats((self.conv1, self.conv2, self.conv3, self.conv4))
-        x1, x2 = self._prefix(x, loc, nb, out1=cat_in[:, :, 0:64], wc=wc[:2])   # [B,N,64], [B,N,64]
-        x_, node_fea, _ = self.node_fea_adapt.rows(x2, loc)           # [B,N,128], [B,64,64]
+        x1, x2, shared, miss = self._prefix(x, loc, nb, out1=cat_in[:, :, 0:64], wc=wc[:2])   # [B,N,64], [B,N,64]
+        x_, node_fea, _ = self.node_fea_adapt.rows(x2, loc, shared=shared)     # [B,N,128], [B,64,64]
+        if miss is not None:
+            self._keep_prefix(x, x1, x2, shared, miss)
         with torch.set_grad_enabled(torch.is_grad_enabled() and feat_grad):
             x2 = ops.linear_rows(x_, self.conv1d.weight.squeeze(-1), self.conv1d.bias)
             x3 = self.conv3.edge_rows(x2, nb(x2, 2), out=cat_in[:, :, 128:256], wcat=wc[2])     # [B,N,128]

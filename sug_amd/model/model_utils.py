@@ -5,6 +5,8 @@ unchanged.  Every block has a ``forward`` in the reference's [B,C,N,1] layout an
 ``rows`` fast path on point-major [B,N,C] rows, which is what the encoders in
 ``Model.py`` use (data layout).
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -82,11 +84,19 @@ class conv_2d(nn.Module):
         w = self.conv[0].weight
         return w.view(w.shape[0], w.shape[1])
 
-    def rows(self, x):
-        """x [..., Cin] -> [..., Cout]: per-point GEMM + BN over all leading dims + act."""
-        y = ops.linear_rows(x, self.weight2d(), self.conv[0].bias)
+    def rows(self, x, pre=None, keep=None):
+        """x [..., Cin] -> [..., Cout]: per-point GEMM + BN over all leading dims + act.
+        keep: a list that receives the GEMM's output y (with ops.record_bn_stats: all a later pass needs to skip the forward).
+        pre: (y, out, coef) of an earlier pass of the step on the same x and weights -- no forward launch, no running-
+        statistics update (the caller replays it); this call only builds its own autograd nodes, so the layer's backward
+        runs per pass exactly as if the forward had been repeated."""
+        y = ops.linear_rows(x, self.weight2d(), self.conv[0].bias, pre=None if pre is None else pre[0])
+        if keep is not None:
+            keep.append(y)
         if self.activation in _ACT_SLOPE and OWN_BN(self.conv[1]):
-            return ops.bn_act_rows(y, self.conv[1], _ACT_SLOPE[self.activation])
+            return ops.bn_act_rows(y, self.conv[1], _ACT_SLOPE[self.activation], pre=None if pre is None else pre[1:])
+        if pre is not None:
+            raise RuntimeError('conv_2d.rows: a precomputed forward needs the fused BatchNorm + activation path')
         return self.conv[2](_bn_rows(self.conv[1], y))
 
     def forward(self, x):
@@ -202,6 +212,29 @@ class transform_net(nn.Module):
         return y.view(-1, self.K, self.K)
 
 
+# Both passes' SA-node glue in one launch per stage where a two-pass geometry plan exists (0: one launch per pass and stage)
+SA_GLUE_BATCHED = os.environ.get('SUG_SA_GLUE_BATCHED', '1') != '0'
+
+
+class SharedHalf:
+    """The forward VALUES of the pass-invariant half of adapt_layer_off.rows for one batch: `proj` (offset projection), `y`
+    and `res` (the residual layer's GEMM output and its result) and `stats`, the residual BatchNorm's recorded
+    [(bn, coef)].  A later pass takes them instead of running the forward kernels again (it still builds its own autograd
+    nodes: the backward is per pass, unchanged) and the encoder replays the BatchNorm's running-statistics update.
+    `glue`: (plan, results) of ops.sa_glue_passes while the passes of that plan are being served."""
+    __slots__ = ('proj', 'y', 'res', 'stats', 'glue')
+
+    def __init__(self, proj=None, y=None, res=None, stats=()):
+        self.proj, self.y, self.res, self.stats, self.glue = proj, y, res, tuple(stats), None
+
+    @property
+    def filled(self):
+        return self.proj is not None
+
+    def fill(self, proj, y, res, stats):
+        self.proj, self.y, self.res, self.stats = proj.detach(), y.detach(), res.detach(), tuple(stats)
+
+
 class adapt_layer_off(nn.Module):
     """SA-node module (model/model_utils.py:92-128): FPS(64) -> ball(0.3,64) -> learned node
     offset -> 64-NN of the moved nodes -> residual conv + max -> 3-NN interpolation back."""
@@ -216,13 +249,24 @@ class adapt_layer_off(nn.Module):
             nn.Tanh())
         self.residual = conv_2d(trans_dim_in, fc_dim, 1)
 
-    def rows(self, fea, loc):
-        """fea [B,N,64], loc [B,N,3] -> (out [B,N,128], node_fea [B,num_node,64], node_off [B,num_node,3])."""
+    def shared_params(self):
+        """The parameters `proj` and `res` of rows() are computed from (an encoder's prefix-cache key counts their versions)."""
+        return list(self.pred_offset.parameters()) + list(self.residual.parameters())
+
+    def rows(self, fea, loc, shared=None):
+        """fea [B,N,64], loc [B,N,3] -> (out [B,N,128], node_fea [B,num_node,64], node_off [B,num_node,3]).
+        shared: a SharedHalf from the encoder when `fea` is its shared prefix output.  The two stages that read `fea` and
+        the weights only -- the offset projection `proj` and the residual layer `res` -- then have the same forward values
+        in every pass over the batch: an empty SharedHalf is filled here, a filled one supplies them (the caller has
+        replayed the residual BatchNorm's running-statistics update) and only the autograd nodes are built, so that every
+        pass keeps its own backward through the two stages, as when it recomputes them.  With a geometry plan of several passes the glue behind them runs for all
+        of those passes in one launch per stage (ops.sa_glue_passes) and the later passes pick their slices up."""
         B, N, _ = loc.shape
         S = self.num_node
         plan = ops.CTX.geometry_plan
+        passes = None
         if plan:
-            fidx, f_loc, gidx = plan.pop(0)    # computed up front for this pass (plan_geometry below)
+            fidx, f_loc, gidx, passes, p = plan.pop(0)    # computed up front for this pass (plan_geometry below)
             if fidx.shape != (B, S) or gidx.shape[:2] != (B, S):
                 raise RuntimeError('geometry plan does not match the SA-node module')
         else:
@@ -233,19 +277,41 @@ class adapt_layer_off(nn.Module):
         # pred_offset on (fea_j - fea_c) is linear before the tanh: project once (one GEMM), then
         # gather / tanh / weight / mean in one kernel (sug_node_offset_*)
         w_off = self.pred_offset[0].weight.view(self.offset_dim, -1)
-        proj = ops.linear_rows(fea, w_off)                            # [B,N,3]
+        if shared is not None and shared.filled:
+            proj = ops.linear_rows(fea, w_off, pre=shared.proj)           # the values of the earlier pass, this pass's nodes
+            res = self.residual.rows(fea, pre=(shared.y, shared.res, shared.stats[0][1]))
+        else:
+            proj = ops.linear_rows(fea, w_off)                            # [B,N,3]
+            if shared is not None:
+                keep = []
+                with ops.record_bn_stats() as rec:
+                    res = self.residual.rows(fea, keep=keep)
+                if len(rec) == 1:               # (the fused BatchNorm path in train mode: what a later pass can take over)
+                    shared.fill(proj, keep[0], res, rec)
+            else:
+                res = self.residual.rows(fea)
+        fused = self.offset_dim == 3 and gidx.shape[2] == S and fea.shape[2] % 4 == 0 and res.shape[2] % 4 == 0
+        # every pass of the plan at once: only where the passes provably share proj / res / fea (a SharedHalf), and the
+        # fused kernels cover the shapes
+        pre = None
+        if shared is not None and passes is not None and fused and passes['count'] > 1 and SA_GLUE_BATCHED:
+            if shared.glue is None or shared.glue[0] is not passes:
+                shared.glue = (passes, ops.sa_glue_passes(proj, res, fea, passes['loc'], passes['fidx'], passes['gidx'], 64))
+            pre = {k: v[p * B:(p + 1) * B] for k, v in shared.glue[1].items()}
+            if p == passes['count'] - 1:
+                shared.glue = None              # the last pass of the plan has its slices
+        P = (lambda *ks: tuple(pre[k] for k in ks)) if pre is not None else (lambda *ks: None)
         if self.offset_dim == 3 and gidx.shape[2] == S:
-            node_off, n_loc = ops.node_offset(proj, loc, fidx, gidx)  # [B,S,3] each
+            node_off, n_loc = ops.node_offset(proj, loc, fidx, gidx, P('off', 'nloc'))  # [B,S,3] each
         else:
             sem = torch.tanh(ops.gather_rows(proj, gidx) - ops.gather_rows(proj, fidx).unsqueeze(2))
             g_loc = ops.gather_rows(loc, gidx) - f_loc.unsqueeze(2)
             node_off = (sem * g_loc).mean(dim=2)
             n_loc = f_loc + node_off
-        gidx2 = ops.knn_query(loc, n_loc, 64)                         # 64-NN of the moved nodes
-        res = self.residual.rows(fea)
-        node_fea = ops.group_max(res, gidx2)                          # [B,S,64]
+        gidx2 = pre['gidx2'] if pre is not None else ops.knn_query(loc, n_loc, 64)   # 64-NN of the moved nodes
+        node_fea = ops.group_max(res, gidx2, P('node', 'arg'))        # [B,S,64]
         if fea.shape[2] % 4 == 0 and node_fea.shape[2] % 4 == 0:
-            out = ops.interp3_cat(fea, node_fea, loc, n_loc)          # cat(fea, 3-NN interpolation)
+            out = ops.interp3_cat(fea, node_fea, loc, n_loc, P('out', 'idx3', 'd3'))   # cat(fea, 3-NN interpolation)
         else:
             out = torch.cat((fea, point_utils.interpolate_rows(loc, n_loc, node_fea, 3)), dim=2)
         return out, node_fea, node_off
@@ -253,7 +319,9 @@ class adapt_layer_off(nn.Module):
     def plan_geometry(self, loc, passes, groups=1):
         """The coordinate-only part of `passes` forwards over the same clouds loc [B,N,3] -- FPS start draws (in the order
         the forwards would make them), FPS, the sampled coordinates, the radius-0.3 ball query -- in one set of launches
-        (SUGStep: the semantic and the node pass of a step).  -> per pass [(fidx, f_loc, gidx)] for ops.CTX.geometry_plan."""
+        (SUGStep: the semantic and the node pass of a step).  -> per pass [(fidx, f_loc, gidx, passes, p)] for
+        ops.CTX.geometry_plan: the pass's slices, then the whole plan (`passes`: the pass-major [passes*B,...] tensors, shared
+        by the entries) and the pass's index in it, from which rows() evaluates the glue of all passes at once."""
         B, N, _ = loc.shape
         S = self.num_node
         starts = []
@@ -268,7 +336,8 @@ class adapt_layer_off(nn.Module):
         fidx = ops.fps(locp, S, st)
         f_loc = ops.gather_rows(locp, fidx)
         gidx = ops.ball_query(locp, f_loc, 0.3, 64)
-        return [[(fidx[p * B:(p + 1) * B], f_loc[p * B:(p + 1) * B], gidx[p * B:(p + 1) * B])] for p in range(passes)]
+        whole = {'count': passes, 'loc': locp, 'fidx': fidx, 'gidx': gidx}
+        return [[(fidx[p * B:(p + 1) * B], f_loc[p * B:(p + 1) * B], gidx[p * B:(p + 1) * B], whole, p)] for p in range(passes)]
 
     def forward(self, input_fea, input_loc):
         """input_fea [B,64,N,1], input_loc [B,3,N] -> (output_fea [B,128,N,1], node_fea [B,64,S,1],

@@ -439,14 +439,15 @@ def gather_rows(feat, idx):
 
 class _GroupMax(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, idx):
+    def forward(ctx, feat, idx, pre=None):
         _need_gpu(feat, idx)
-        feat_c, B, N, C, ld = _rows3(feat)
-        idx = _i32(idx).contiguous()
-        S, ns = idx.shape[1], idx.shape[2]
-        out = torch.empty(B, S, C, dtype=torch.float32, device=feat.device)
-        arg = torch.empty(B, S, C, dtype=torch.int32, device=feat.device)
-        check(lib().sug_group_max(_p(feat_c), ld, _p(idx), B, N, S, ns, C, _p(out), _p(arg), _st()), 'sug_group_max')
+        if pre is not None:                     # (out, arg) of this pass from sa_glue_passes: no launch here
+            out, arg = pre
+            B, N, C = feat.shape
+        else:
+            feat_c, B, N, C, ld = _rows3(feat)
+            idx = _i32(idx).contiguous()
+            out, arg = _group_max_raw(feat_c, ld, B, idx, N, C)
         ctx.save_for_backward(arg)
         ctx.shape = (B, N, C)
         return out
@@ -459,12 +460,25 @@ class _GroupMax(torch.autograd.Function):
         g = g.contiguous()
         d = torch.zeros(B, N, C, dtype=torch.float32, device=g.device)
         check(lib().sug_group_max_bwd(_p(g), _p(arg), B, N, S, C, _p(d), C, _st()), 'sug_group_max_bwd')
-        return d, None
+        return d, None, None
 
 
-def group_max(feat, idx):
-    """max_j feat[b, idx[b,s,j], :] -> [B,S,C]."""
-    return _GroupMax.apply(feat, idx)
+def _group_max_raw(feat_c, ld, Bsrc, idx, N, C):
+    """(out, arg) [B,S,C] of idx [B,S,ns] over B = P * Bsrc pass-major clouds that read feat_c [Bsrc,N,ld]."""
+    B, S, ns = idx.shape
+    out = torch.empty(B, S, C, dtype=torch.float32, device=feat_c.device)
+    arg = torch.empty(B, S, C, dtype=torch.int32, device=feat_c.device)
+    if Bsrc == B:
+        check(lib().sug_group_max(_p(feat_c), ld, _p(idx), B, N, S, ns, C, _p(out), _p(arg), _st()), 'sug_group_max')
+    else:
+        check(lib().sug_group_max_shared(_p(feat_c), ld, Bsrc, _p(idx), B, N, S, ns, C, _p(out), _p(arg), _st()),
+              'sug_group_max_shared')
+    return out, arg
+
+
+def group_max(feat, idx, pre=None):
+    """max_j feat[b, idx[b,s,j], :] -> [B,S,C].  pre: this pass's (out, arg) where sa_glue_passes has computed them."""
+    return _GroupMax.apply(feat, idx, pre)
 
 
 # ----------------------------------------------------------------------------- per-point linear
@@ -483,10 +497,14 @@ class _LinearRows(torch.autograd.Function):
     runs in sug_linear_dw instead of a rocBLAS GEMM that does not split K."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, pre=None):
         M, N = weight.shape
         x2 = x.reshape(-1, N)
-        if OWN_ROWS_GEMM and N in (64, 128) and M % 128 == 0 and x2.shape[0] >= 4096 and x2.stride(1) == 1 \
+        if pre is not None:
+            # the values an earlier pass computed from the same x and weights (a shared encoder prefix): no launch, a fresh
+            # alias of them as this node's output; the backward is this node's own
+            y = pre.detach()
+        elif OWN_ROWS_GEMM and N in (64, 128) and M % 128 == 0 and x2.shape[0] >= 4096 and x2.stride(1) == 1 \
                 and x2.stride(0) % 4 == 0 and x2.data_ptr() % 16 == 0 and weight.is_contiguous():
             # fp32 MFMA kernel of the library (the rocBLAS selection for these skinny shapes is 2-3x slower)
             y = torch.empty(x2.shape[0], M, dtype=torch.float32, device=x.device)
@@ -507,7 +525,7 @@ class _LinearRows(torch.autograd.Function):
         M, N = weight.shape
         dx, dw, db = linear_rows_backward(x.reshape(-1, N), weight, g.reshape(-1, M), ctx.needs_input_grad[0],
                                           ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
-        return (None if dx is None else dx.view(x.shape)), dw, db
+        return (None if dx is None else dx.view(x.shape)), dw, db, None
 
 
 DW_BMM = _os.environ.get('SUG_DW_BMM', '1') == '1'
@@ -577,12 +595,13 @@ def linear_rows_backward(x2, weight, g2, need_dx, need_dw, need_db):
     return dx, dw, db
 
 
-def linear_rows(x, weight, bias=None):
-    """F.linear for [..., Cin] rows with many rows and small Cin/Cout (the encoders' 1x1 convs)."""
+def linear_rows(x, weight, bias=None, pre=None):
+    """F.linear for [..., Cin] rows with many rows and small Cin/Cout (the encoders' 1x1 convs).
+    pre: the result an earlier pass of the step computed from the same x and weights; the forward GEMM is then not run."""
     _need_gpu(x, weight)
     if x.dtype != torch.float32:
         raise RuntimeError('sug_amd.ops.linear_rows: fp32 rows only (got %s)' % x.dtype)
-    return _LinearRows.apply(x, weight, bias)
+    return _LinearRows.apply(x, weight, bias, pre)
 
 
 # ----------------------------------------------------------------------------- SA-node glue
@@ -590,16 +609,14 @@ class _NodeOffset(torch.autograd.Function):
     """(node_off, node_loc) of adapt_layer_off from the projected features (sug_node_offset_*)."""
 
     @staticmethod
-    def forward(ctx, proj, loc, fidx, gidx):
+    def forward(ctx, proj, loc, fidx, gidx, pre=None):
         _need_gpu(proj, loc, fidx, gidx)
         proj, loc = proj.contiguous(), loc.detach().contiguous()
         fidx, gidx = _i32(fidx).contiguous(), _i32(gidx).contiguous()
-        B, N, _ = proj.shape
-        S, ns = gidx.shape[1], gidx.shape[2]
-        off = torch.empty(B, S, 3, dtype=torch.float32, device=proj.device)
-        nloc = torch.empty(B, S, 3, dtype=torch.float32, device=proj.device)
-        check(lib().sug_node_offset_fwd(_p(proj), _p(loc), _p(fidx), _p(gidx), B, N, S, ns, _p(off), _p(nloc), _st()),
-              'sug_node_offset_fwd')
+        if pre is not None:                     # (off, nloc) of this pass from sa_glue_passes: no launch here
+            off, nloc = pre
+        else:
+            off, nloc = _node_offset_raw(proj, loc, fidx, gidx)
         ctx.save_for_backward(proj, loc, fidx, gidx)
         ctx.set_materialize_grads(False)
         return off, nloc
@@ -610,18 +627,34 @@ class _NodeOffset(torch.autograd.Function):
         B, N, _ = proj.shape
         S, ns = gidx.shape[1], gidx.shape[2]
         if goff is None and gnloc is None:
-            return None, None, None, None
+            return None, None, None, None, None
         # nloc = loc[f] + off; an output that took no part in the loss arrives as None (no zero fill + add for it)
         g = (goff if gnloc is None else gnloc if goff is None else goff + gnloc).contiguous()
         dproj = torch.empty_like(proj)              # written (or zeroed) entirely by the entry point
         check(lib().sug_node_offset_bwd(_p(proj), _p(loc), _p(fidx), _p(gidx), _p(g), B, N, S, ns, _p(dproj), _st()),
               'sug_node_offset_bwd')
-        return dproj, None, None, None
+        return dproj, None, None, None, None
 
 
-def node_offset(proj, loc, fidx, gidx):
-    """proj [B,N,3], loc [B,N,3], fidx [B,S], gidx [B,S,ns] -> (node_off [B,S,3], node_loc [B,S,3])."""
-    return _NodeOffset.apply(proj, loc, fidx, gidx)
+def _node_offset_raw(proj, loc, fidx, gidx):
+    """(off, nloc) [B,S,3] over the B = P * Bsrc pass-major clouds of loc / fidx / gidx; proj [Bsrc,N,3] is shared by the passes."""
+    Bsrc, N, _ = proj.shape
+    B, S, ns = gidx.shape
+    off = torch.empty(B, S, 3, dtype=torch.float32, device=proj.device)
+    nloc = torch.empty(B, S, 3, dtype=torch.float32, device=proj.device)
+    if Bsrc == B:
+        check(lib().sug_node_offset_fwd(_p(proj), _p(loc), _p(fidx), _p(gidx), B, N, S, ns, _p(off), _p(nloc), _st()),
+              'sug_node_offset_fwd')
+    else:
+        check(lib().sug_node_offset_fwd_shared(_p(proj), Bsrc, _p(loc), _p(fidx), _p(gidx), B, N, S, ns, _p(off), _p(nloc),
+                                               _st()), 'sug_node_offset_fwd_shared')
+    return off, nloc
+
+
+def node_offset(proj, loc, fidx, gidx, pre=None):
+    """proj [B,N,3], loc [B,N,3], fidx [B,S], gidx [B,S,ns] -> (node_off [B,S,3], node_loc [B,S,3]).
+    pre: this pass's (node_off, node_loc) where sa_glue_passes has computed them."""
+    return _NodeOffset.apply(proj, loc, fidx, gidx, pre)
 
 
 class _Interp3Cat(torch.autograd.Function):
@@ -629,16 +662,17 @@ class _Interp3Cat(torch.autograd.Function):
     backward also carries the distance gradient back to the node positions."""
 
     @staticmethod
-    def forward(ctx, fea, node, xyz, nloc):
+    def forward(ctx, fea, node, xyz, nloc, pre=None):
         _need_gpu(fea, node, xyz, nloc)
         fea, B, N, C1, ldf = _rows3(fea)
         node = node.contiguous()
         xyz, nlocd = xyz.detach().contiguous(), nloc.detach().contiguous()
         S, C2 = node.shape[1], node.shape[2]
-        idx3, d3 = three_nn_raw(xyz, nlocd)
-        out = torch.empty(B, N, C1 + C2, dtype=torch.float32, device=fea.device)
-        check(lib().sug_interp3_cat_fwd(_p(fea) if C1 else None, ldf if C1 else 0, C1, _p(node), _p(idx3), _p(d3), B, N, S,
-                                        C2, _p(out), C1 + C2, _st()), 'sug_interp3_cat_fwd')
+        if pre is not None:                     # (out, idx3, d3) of this pass from sa_glue_passes: no launch here
+            out, idx3, d3 = pre
+        else:
+            idx3, d3 = three_nn_raw(xyz, nlocd)
+            out = _interp3_cat_raw(fea, ldf, C1, B, node, idx3, d3, N)
         ctx.save_for_backward(node, idx3, d3, xyz, nlocd)
         ctx.meta = (B, N, S, C1, C2)
         return out
@@ -666,12 +700,51 @@ class _Interp3Cat(torch.autograd.Function):
             dnloc = torch.zeros_like(nloc)
             check(L.sug_interp3_cat_bwd(_p(g), C1 + C2, C1, _p(node), _p(idx3), _p(d3), _p(xyz), _p(nloc), B, N, S, C2,
                                         _p(dnode), _p(dnloc), _st()), 'sug_interp3_cat_bwd')
-        return g[:, :, :C1], dnode, None, dnloc
+        return g[:, :, :C1], dnode, None, dnloc, None
 
 
-def interp3_cat(fea, node, xyz, nloc):
-    """fea [B,N,C1], node [B,S,C2], xyz [B,N,3], nloc [B,S,3] -> [B,N,C1+C2]."""
-    return _Interp3Cat.apply(fea, node, xyz, nloc)
+def _interp3_cat_raw(fea, ldf, C1, Bsrc, node, idx3, d3, N):
+    """out [B,N,C1+C2] over the B = P * Bsrc pass-major clouds of node / idx3 / d3; fea [Bsrc,N,ldf] is shared by the passes."""
+    B, S, C2 = node.shape
+    out = torch.empty(B, N, C1 + C2, dtype=torch.float32, device=node.device)
+    fp, ld = (_p(fea), ldf) if C1 else (None, 0)
+    if Bsrc == B:
+        check(lib().sug_interp3_cat_fwd(fp, ld, C1, _p(node), _p(idx3), _p(d3), B, N, S, C2, _p(out), C1 + C2, _st()),
+              'sug_interp3_cat_fwd')
+    else:
+        check(lib().sug_interp3_cat_fwd_shared(fp, ld, C1, Bsrc, _p(node), _p(idx3), _p(d3), B, N, S, C2, _p(out), C1 + C2,
+                                               _st()), 'sug_interp3_cat_fwd_shared')
+    return out
+
+
+def interp3_cat(fea, node, xyz, nloc, pre=None):
+    """fea [B,N,C1], node [B,S,C2], xyz [B,N,3], nloc [B,S,3] -> [B,N,C1+C2].
+    pre: this pass's (out, idx3, d3) where sa_glue_passes has computed them."""
+    return _Interp3Cat.apply(fea, node, xyz, nloc, pre)
+
+
+def sa_glue_passes(proj, res, fea, locp, fidx, gidx, k):
+    """The SA-node glue of the P passes of a step over ONE batch in one launch per stage (no autograd: the values only).
+    proj [B,N,3], res [B,N,C], fea [B,N,C1] are the passes' common operands and are read in place (cloud % B); locp [P*B,N,3],
+    fidx [P*B,S], gidx [P*B,S,ns] are pass-major.  Every virtual cloud's result is bit-identical to the per-pass calls
+    node_offset -> knn_query -> group_max -> three_nn -> interp3_cat; -> one dict of [P*B,...] tensors, which the passes
+    hand to those ops slice by slice as `pre`."""
+    _need_gpu(proj, res, fea, locp, fidx, gidx)
+    with torch.no_grad():
+        B, N, _ = proj.shape
+        proj_c, locp = proj.detach().contiguous(), locp.detach().contiguous()
+        fidx, gidx = _i32(fidx).contiguous(), _i32(gidx).contiguous()
+        if locp.shape[0] % B or fidx.shape[0] != locp.shape[0] or gidx.shape[0] != locp.shape[0] or fea.shape[0] != B or \
+                res.shape[0] != B:
+            raise RuntimeError('sa_glue_passes: %d planned clouds are not whole passes over a batch of %d' % (locp.shape[0], B))
+        off, nloc = _node_offset_raw(proj_c, locp, fidx, gidx)
+        gidx2 = knn_query(locp, nloc, k)
+        res_c, _, _, C, ldr = _rows3(res.detach())
+        node, arg = _group_max_raw(res_c, ldr, B, gidx2, N, C)
+        idx3, d3 = three_nn_raw(locp, nloc)
+        fea_c, _, _, C1, ldf = _rows3(fea.detach())
+        out = _interp3_cat_raw(fea_c, ldf, C1, B, node, idx3, d3, N)
+    return {'off': off, 'nloc': nloc, 'gidx2': gidx2, 'node': node, 'arg': arg, 'idx3': idx3, 'd3': d3, 'out': out}
 
 
 # ----------------------------------------------------------------------------- BN helpers
@@ -765,7 +838,7 @@ class _BNActRows(torch.autograd.Function):
     Train mode uses batch statistics and updates the running ones like nn.BatchNorm."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, st, slope):
+    def forward(ctx, y, gamma, beta, st, slope, pre=None):
         _need_gpu(y, gamma)
         C = y.shape[-1]
         y2 = y.reshape(-1, C)
@@ -774,13 +847,18 @@ class _BNActRows(torch.autograd.Function):
         rows = y2.shape[0]
         _check_groups('bn_act_rows', rows, 'rows', st.G)
         dev = y.device
-        g, b, coef = _bn_params(gamma, beta, st, C)
-        out = torch.empty(rows, C, dtype=torch.float32, device=dev)
-        stats = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        ws = _stats_ws(C, dev)
-        check(lib().sug_bn_act_rows_fwd(_p(y2), C, rows, C, st.G, _p(g), _p(b), st.train, st.eps, st.momentum,
-                                        float(slope), _p(st.mean), _p(st.var), _p(coef), _p(out), C,
-                                        _p(stats), _p(ws), _st()), 'sug_bn_act_rows_fwd')
+        if pre is not None:
+            # (out, coef) an earlier pass computed from the same y and parameters: no launch and no running-statistics
+            # update here (the caller replays that); the backward is this node's own
+            out, coef = pre[0].detach().reshape(rows, C), pre[1].detach()
+        else:
+            g, b, coef = _bn_params(gamma, beta, st, C)
+            out = torch.empty(rows, C, dtype=torch.float32, device=dev)
+            stats = torch.empty(2 * C, dtype=torch.float64, device=dev)
+            ws = _stats_ws(C, dev)
+            check(lib().sug_bn_act_rows_fwd(_p(y2), C, rows, C, st.G, _p(g), _p(b), st.train, st.eps, st.momentum,
+                                            float(slope), _p(st.mean), _p(st.var), _p(coef), _p(out), C,
+                                            _p(stats), _p(ws), _st()), 'sug_bn_act_rows_fwd')
         if any(ctx.needs_input_grad[i] for i in (0, 1, 2)):             # y, gamma, beta
             ctx.save_for_backward(y2, coef)
             ctx.meta = (rows, C, float(slope), st.training, tuple(y.shape), st.G)
@@ -795,7 +873,7 @@ class _BNActRows(torch.autograd.Function):
         if gout is None:                    # an undefined gradient counts as zeros, as if autograd had materialised it
             gout = torch.zeros_like(y2)
         dy, dgamma, dbeta = _bn_act_rows_backward(gout, y2, coef, rows, C, slope, training, G)
-        return dy.view(shape), dgamma, dbeta, None, None
+        return dy.view(shape), dgamma, dbeta, None, None, None
 
 
 def _bn_act_rows_backward(gout, y2, coef, rows, C, slope, training, G):
@@ -1290,8 +1368,12 @@ def bn_replay(bn, coef):
     _count_bn_call(bn, G)
 
 
-def bn_act_rows(y, bn, slope):
-    """bn: an nn.BatchNorm{1,2}d module whose parameters / running buffers are used."""
+def bn_act_rows(y, bn, slope, pre=None):
+    """bn: an nn.BatchNorm{1,2}d module whose parameters / running buffers are used.
+    pre: (out, coef) an earlier pass of the step computed from the same y and parameters (train mode): nothing is launched,
+    counted or recorded -- the caller replays the running-statistics update (replay_bn_stats)."""
+    if pre is not None:
+        return _BNActRows.apply(y, bn.weight, bn.bias, _bn_state(bn), slope, pre)[0]
     _count_bn_call(bn)
     out, coef = _BNActRows.apply(y, bn.weight, bn.bias, _bn_state(bn), slope)
     _record_bn(bn, coef)
