@@ -324,7 +324,8 @@ int sug_calayer_bwd(int layers, const float* x, int64_t ldx, int M, int C, int H
  *   pre-LayerNorm output and pro(v) = Dropout(act(LayerNorm(v; gamma[h], beta[h]))), dropout from uniform randoms u[h]
  *   [M, K] (keep when u >= p_drop, scale 1/(1-p_drop); u null: no dropout); side outputs stats[h] [M, 2] = mean | rstd of
  *   the rows of in[h] and act[h] [M, K] = the activation before the dropout (null: not written).
- *   K % 256 == 0 (pro: K <= 1024), No <= 32 or 256 or 512, M <= 128 (sug_head_linear_supported).
+ *   K % 256 == 0 (pro: K <= 1024), No <= 32, or a multiple of 4 up to 64 (a last layer: no epilogue), or 256 or 512,
+ *   M <= 128 (sug_head_linear_supported).
  * sug_head_ln_bwd: dz[h] [M, No] = gradient of a layer's Linear output z[h] from gup[h] [M, No] (row stride ldg) = the
  *   gradient of Dropout(act(LayerNorm(z))), plus gextra[h] = a gradient of the activation BEFORE the dropout (the mid
  *   feature's; may be null); also dgamma[h], dbeta[h] [No] and db[h] [No] = the column sums of dz (null: none).
@@ -723,8 +724,11 @@ int sug_mmd_rbf_rows_bwd(const float* z, int64_t ldz, const float* wt, int m, in
 
 /* SDA sample weights from class probabilities: prob_weights_soft + distance2weights,
  * model/mmd.py:134-148 and :178-202 (the reference computes them on the CPU with scipy's kl_div).
- * pred_* [m,10] logits (row strides lds/ldt), label_* int64 [m]; method 0 "none", 1 "naive_inverse",
- * 2 "exp_inverse", 3 "mean2one"; weights [m]. */
+ * pred_* [m,num_class] logits (row strides lds/ldt >= num_class), label_* int64 [m]; method 0 "none", 1 "naive_inverse",
+ * 2 "exp_inverse", 3 "mean2one"; weights [m].  2 <= num_class <= SUG_SDA_MAX_CLASSES: 10 runs the compile-time body, every
+ * other count a body that streams the row (same passes, same order of arithmetic).  A label outside [0, num_class) gets no
+ * one-hot entry and raises nothing. */
+#define SUG_SDA_MAX_CLASSES 64
 int sug_sda_prob_weights(const float* pred_s, int64_t lds, const float* pred_t, int64_t ldt,
                          const int64_t* label_s, const int64_t* label_t, int m, int num_class,
                          float label_weight, int method, float* weights, void* stream);

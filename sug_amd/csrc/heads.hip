@@ -316,7 +316,7 @@ __device__ __forceinline__ float in_elem(const BwdHead& H, const BwdArgs& a, int
   return r;
 }
 
-// Workgroup = 32 input columns [k0, k0+32) (x heads unless sum_da).  NOP: output width padded to 32 (32, 256 or 512:
+// Workgroup = 32 input columns [k0, k0+32) (x heads unless sum_da).  NOP: output width padded to 32 (32, 64, 256 or 512:
 // compile-time, so that the MFMA loops are straight-line code with static register indices).
 //   dW[n][k0 + j] = sum_i dz[i][n] a[i][k0 + j]   A = dz^T (lane = n), B = a (lane = column), k = the rows (32 per block)
 //   da[i][k0 + j] = sum_n dz[i][n] W[n][k0 + j]   A = dz (lane = row), B = W (registers), n split over the waves
@@ -454,7 +454,8 @@ int heads_ok(int heads) { return heads >= 1 && heads <= HMAX; }
 
 extern "C" int sug_head_linear_supported(int M, int K, int No, int pro, int epi) {
   if (M < 1 || M > 128 || K < 256 || K % 256 || K > 4096 || No < 1) return 0;     // (K / 8 per wave in 32-k sub-steps)
-  if (!(No <= 32 || No == 256 || No == 512)) return 0;   // (the backward kernels are instantiated for these output widths)
+  // (the backward kernels are instantiated for the padded widths 32, 64, 256, 512; 32 < No <= 64 in whole float4 rows)
+  if (!(No <= 32 || (No <= 64 && No % 4 == 0) || No == 256 || No == 512)) return 0;
   if (pro && K > 1024) return 0;                         // (row statistics pass: 4 float4 per lane and row)
   if (epi && !(No == 256 || No == 512)) return 0;
   return 1;
@@ -562,16 +563,19 @@ extern "C" int sug_head_linear_bwd(int heads, int sum_da, const float* const* dz
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(K / 32, sum_da ? 1 : heads), block(NT);
   const size_t sh = (size_t)(32 * (NoP + 1) + 32 * 33 + NW * 32 * 32) * sizeof(float);
-  static SugLdsOptIn note[6];
+  // (NoP == 64, a last layer of 33..64 classes: 32*65 + 32*33 + 8*32*32 floats = 45,312 bytes)
+  static SugLdsOptIn note[8];
 #define SUG_HEAD_BWD(PRO_, NOP_, SLOT_)                                                                             \
   do {                                                                                                              \
     if (int rc = sug_allow_dynamic_lds(note[SLOT_], &head_bwd_kernel<PRO_, NOP_>, 110 * 1024, "sug_head_linear_bwd")) return rc; \
     hipLaunchKernelGGL((head_bwd_kernel<PRO_, NOP_>), grid, block, sh, st, a);                                      \
   } while (0)
   if (pro) {
-    if (NoP == 32) SUG_HEAD_BWD(true, 32, 0); else if (NoP == 256) SUG_HEAD_BWD(true, 256, 1); else SUG_HEAD_BWD(true, 512, 2);
+    if (NoP == 32) SUG_HEAD_BWD(true, 32, 0); else if (NoP == 64) SUG_HEAD_BWD(true, 64, 6);
+    else if (NoP == 256) SUG_HEAD_BWD(true, 256, 1); else SUG_HEAD_BWD(true, 512, 2);
   } else {
-    if (NoP == 32) SUG_HEAD_BWD(false, 32, 3); else if (NoP == 256) SUG_HEAD_BWD(false, 256, 4); else SUG_HEAD_BWD(false, 512, 5);
+    if (NoP == 32) SUG_HEAD_BWD(false, 32, 3); else if (NoP == 64) SUG_HEAD_BWD(false, 64, 7);
+    else if (NoP == 256) SUG_HEAD_BWD(false, 256, 4); else SUG_HEAD_BWD(false, 512, 5);
   }
 #undef SUG_HEAD_BWD
   SUG_LAUNCH_CHECK("sug_head_linear_bwd");

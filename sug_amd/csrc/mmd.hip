@@ -480,6 +480,95 @@ __global__ __launch_bounds__(256) void sda_prob_weights_multi_kernel(SdaMulti a,
   sda_prob_weights_body(a.ps[t], a.lds[t], a.pt[t], a.ldt[t], ls, lt, m, lw, method, a.out[t]);
 }
 
+// The same for a run-time class count 2 <= C <= 64 (every count but the shipped 10, whose compile-time body above stays as
+// it is): the same three passes and the same arithmetic in the same order -- softmax as exp(x - max) / sum with the sum over
+// c ascending, the 2C KL terms c ascending, fp64 block sums in wave order -- so a row's numbers do not depend on which body
+// ran.  No per-thread q[C] array (a run-time index into one goes to scratch): a row is streamed, one walk for the max, one
+// for the sum, and exp(p[c] - mx) / sum is formed again term by term where a probability is needed; a row's logits are at
+// most 256 bytes and stay in L1.  Labels outside [0, C) get no one-hot entry and raise nothing, as above.
+__device__ __forceinline__ void sda_prob_weights_body_rt(const float* __restrict__ ps, int64_t lds,
+                                                         const float* __restrict__ pt, int64_t ldt,
+                                                         const int64_t* __restrict__ ls,
+                                                         const int64_t* __restrict__ lt, int m, int C, float lw,
+                                                         int method, float* __restrict__ out) {
+  __shared__ double s_red[4][2];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  auto block_sum2 = [&](double a, double b, double& ra, double& rb) {
+    a = wave_sum_d(a);
+    b = wave_sum_d(b);
+    __syncthreads();
+    if (lane == 0) { s_red[wv][0] = a; s_red[wv][1] = b; }
+    __syncthreads();
+    ra = ((s_red[0][0] + s_red[1][0]) + s_red[2][0]) + s_red[3][0];
+    rb = ((s_red[0][1] + s_red[1][1]) + s_red[2][1]) + s_red[3][1];
+  };
+  auto row_max_sum = [&](const float* p, float& mx, float& sum) {     // fp32 softmax as torch: exp(x - max) / sum
+    mx = p[0];
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c]);
+    sum = 0.f;
+    for (int c = 0; c < C; ++c) sum += expf(p[c] - mx);
+  };
+  // pass 1: global sums of (a + eps), (b + eps)
+  double sa = 0.0, sb = 0.0;
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const float* pa = ps + (int64_t)i * lds;
+    const float* pb = pt + (int64_t)i * ldt;
+    const int la = (int)ls[i], lb = (int)lt[i];
+    float mx, sum;
+    row_max_sum(pa, mx, sum);
+    for (int c = 0; c < C; ++c) sa += (double)(expf(pa[c] - mx) / sum + 1e-8f) + (double)((la == c ? lw : 0.f) + 1e-8f);
+    row_max_sum(pb, mx, sum);
+    for (int c = 0; c < C; ++c) sb += (double)(expf(pb[c] - mx) / sum + 1e-8f) + (double)((lb == c ? lw : 0.f) + 1e-8f);
+  }
+  double ta, tb;
+  block_sum2(sa, sb, ta, tb);
+  const float fa = (float)ta, fb = (float)tb;
+  auto kl2 = [&](float av, float bv) {
+    const float x = (av + 1e-8f) / fa, y = (bv + 1e-8f) / fb;
+    const float k1 = x * logf(x / y) - x + y, k2 = y * logf(y / x) - y + x;
+    return k1 * 0.5f + k2 * 0.5f;
+  };
+  // pass 2: distances (kept in out[]), and their sum / the sum of the inverse weights
+  double dsum = 0.0, wsum = 0.0;
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const float* pa = ps + (int64_t)i * lds;
+    const float* pb = pt + (int64_t)i * ldt;
+    const int la = (int)ls[i], lb = (int)lt[i];
+    float mxa, suma, mxb, sumb;
+    row_max_sum(pa, mxa, suma);
+    row_max_sum(pb, mxb, sumb);
+    float dist = 0.f;
+    for (int c = 0; c < C; ++c) dist += kl2(expf(pa[c] - mxa) / suma, expf(pb[c] - mxb) / sumb);
+    for (int c = 0; c < C; ++c) dist += kl2(la == c ? lw : 0.f, lb == c ? lw : 0.f);
+    out[i] = dist;
+    dsum += (double)dist;
+    wsum += method == 1 ? (double)(1.f / (dist + 1e-8f)) : (method == 2 ? (double)expf(-dist) : 0.0);
+  }
+  double td, tw;
+  block_sum2(dsum, wsum, td, tw);
+  if (method == 0) return;
+  const float mean = (float)(td / (double)m);
+  const float scale = (float)(int)(1.f / mean);           // .type(torch.int): truncation
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const float dist = out[i];
+    out[i] = method == 1 ? (1.f / (dist + 1e-8f)) / (float)tw : (method == 2 ? expf(-dist) / (float)tw : dist * scale);
+  }
+}
+
+__global__ __launch_bounds__(256) void sda_prob_weights_rt_kernel(const float* __restrict__ ps, int64_t lds,
+                                                                  const float* __restrict__ pt, int64_t ldt,
+                                                                  const int64_t* __restrict__ ls,
+                                                                  const int64_t* __restrict__ lt, int m, int C, float lw,
+                                                                  int method, float* __restrict__ out) {
+  sda_prob_weights_body_rt(ps, lds, pt, ldt, ls, lt, m, C, lw, method, out);
+}
+__global__ __launch_bounds__(256) void sda_prob_weights_multi_rt_kernel(SdaMulti a, const int64_t* __restrict__ ls,
+                                                                        const int64_t* __restrict__ lt, int m, int C, float lw,
+                                                                        int method) {
+  const int t = blockIdx.x;
+  sda_prob_weights_body_rt(a.ps[t], a.lds[t], a.pt[t], a.ldt[t], ls, lt, m, C, lw, method, a.out[t]);
+}
+
 }  // namespace
 
 extern "C" int sug_mmd_rbf_rows(const float* z, int64_t ldz, int m, int D, const float* w, const float* neg_gamma,
@@ -568,10 +657,16 @@ extern "C" int sug_sda_prob_weights(const float* pred_s, int64_t lds, const floa
                                     const int64_t* label_s, const int64_t* label_t, int m, int num_class,
                                     float label_weight, int method, float* weights, void* stream) {
   SUG_REQUIRE(pred_s && pred_t && label_s && label_t && weights, "sug_sda_prob_weights: null pointer");
-  SUG_REQUIRE(m > 0 && num_class == 10 && lds >= 10 && ldt >= 10, "sug_sda_prob_weights: bad shape (10 classes)");
+  SUG_REQUIRE(m > 0 && num_class >= 2 && num_class <= SUG_SDA_MAX_CLASSES && lds >= num_class && ldt >= num_class,
+              "sug_sda_prob_weights: bad shape (2..%d classes, rows at least that long; got %d classes, m=%d)",
+              SUG_SDA_MAX_CLASSES, num_class, m);
   SUG_REQUIRE(method >= 0 && method <= 3, "sug_sda_prob_weights: unknown weighting method");
-  hipLaunchKernelGGL(sda_prob_weights_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred_s, lds, pred_t, ldt,
-                     label_s, label_t, m, label_weight, method, weights);
+  if (num_class == 10)      // the shipped count: the compile-time body
+    hipLaunchKernelGGL(sda_prob_weights_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred_s, lds, pred_t, ldt,
+                       label_s, label_t, m, label_weight, method, weights);
+  else
+    hipLaunchKernelGGL(sda_prob_weights_rt_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred_s, lds, pred_t, ldt,
+                       label_s, label_t, m, num_class, label_weight, method, weights);
   SUG_LAUNCH_CHECK("sug_sda_prob_weights");
   return SUG_OK;
 }
@@ -754,20 +849,26 @@ extern "C" int sug_sda_prob_weights_multi(int n, const void* const* pred_s, cons
                                           int num_class, float label_weight, int method, void* const* weights, void* stream) {
   SUG_REQUIRE(pred_s && lds && pred_t && ldt && label_s && label_t && weights, "sug_sda_prob_weights_multi: null pointer");
   SUG_REQUIRE(n >= 1 && n <= SUG_MMD_MULTI, "sug_sda_prob_weights_multi: %d heads (1..%d)", n, SUG_MMD_MULTI);
-  SUG_REQUIRE(m > 0 && num_class == 10, "sug_sda_prob_weights_multi: bad shape (10 classes)");
+  SUG_REQUIRE(m > 0 && num_class >= 2 && num_class <= SUG_SDA_MAX_CLASSES,
+              "sug_sda_prob_weights_multi: bad shape (2..%d classes; got %d classes, m=%d)", SUG_SDA_MAX_CLASSES, num_class, m);
   SUG_REQUIRE(method >= 0 && method <= 3, "sug_sda_prob_weights_multi: unknown weighting method");
   SdaMulti a;
   for (int i = 0; i < SUG_MMD_MULTI; ++i) {
     const int k = i < n ? i : 0;
-    SUG_REQUIRE(pred_s[k] && pred_t[k] && weights[k] && lds[k] >= 10 && ldt[k] >= 10, "sug_sda_prob_weights_multi: bad operand %d", k);
+    SUG_REQUIRE(pred_s[k] && pred_t[k] && weights[k] && lds[k] >= num_class && ldt[k] >= num_class,
+                "sug_sda_prob_weights_multi: bad operand %d (rows of at least %d logits)", k, num_class);
     a.ps[i] = (const float*)pred_s[k];
     a.pt[i] = (const float*)pred_t[k];
     a.lds[i] = lds[k];
     a.ldt[i] = ldt[k];
     a.out[i] = (float*)weights[k];
   }
-  hipLaunchKernelGGL(sda_prob_weights_multi_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a, label_s, label_t, m,
-                     label_weight, method);
+  if (num_class == 10)
+    hipLaunchKernelGGL(sda_prob_weights_multi_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a, label_s, label_t, m,
+                       label_weight, method);
+  else
+    hipLaunchKernelGGL(sda_prob_weights_multi_rt_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a, label_s, label_t, m,
+                       num_class, label_weight, method);
   SUG_LAUNCH_CHECK("sug_sda_prob_weights_multi");
   return SUG_OK;
 }

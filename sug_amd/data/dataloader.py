@@ -29,9 +29,11 @@ def kl_divergence_distance_(x, y):
 
 
 def class_indices(labels, class_num=10):
-    """Per class the list of its sample indices (UnifiedPointDG.classes())."""
+    """Per class the list of its sample indices (UnifiedPointDG.classes()).  A label outside [0, class_num) is a ValueError."""
     indices = [[] for _ in range(class_num)]
     for i, label in enumerate(labels):
+        if not 0 <= int(label) < class_num:
+            raise ValueError('class_indices: label %d of sample %d is outside [0, class_num = %d)' % (int(label), i, class_num))
         indices[int(label)].append(i)
     return indices
 
@@ -94,13 +96,17 @@ class UnifiedPointDG:
     array or a tensor: xyz is uploaded once as fp32.  Every batch advances the device-resident batch counter by one, so
     a run is reproducible from `seed` and no two batches share a draw.  `aug`: True / False as in the reference (z-rotation
     and jitter), or a mapping that selects the stages of pc_augment and their parameters (parse_aug), e.g.
-    {'rotate_z': True, 'jitter': (0.01, 0.05), 'scale': (0.8, 1.25), 'perturb': (0.06, 0.18), 'shift': 0.1}."""
+    {'rotate_z': True, 'jitter': (0.01, 0.05), 'scale': (0.8, 1.25), 'perturb': (0.06, 0.18), 'shift': 0.1}.
+    `class_num` (the reference fixes PointDA-10's ten): the number of classes; classes() and cls_wights() have that many
+    entries, and a label outside [0, class_num) is a ValueError."""
 
     def __init__(self, dataset_type, pts, labels, status='train', pc_input_num=1024, aug=True, model="DGCNN", device=None,
-                 seed=0):
+                 seed=0, class_num=10):
         if device is None:
             device = pts.device if torch.is_tensor(pts) and pts.is_cuda else torch.device('cuda')
         device = torch.device(device)
+        if int(class_num) != class_num or class_num < 1:
+            raise ValueError('UnifiedPointDG: class_num must be a positive integer (got %r)' % (class_num,))
         if device.type != 'cuda':
             raise RuntimeError('UnifiedPointDG keeps its clouds on a HIP device only (got %s); there is no CPU fallback' % device)
         self.num_points = pc_input_num
@@ -123,7 +129,7 @@ class UnifiedPointDG:
         self.counter = torch.zeros(1, dtype=torch.int64, device=device)
         self.device = device
 
-        self.class_num = 10
+        self.class_num = int(class_num)
         self.dataset_size = pts.shape[0]
         self.indices = class_indices(self.labels, self.class_num)
         self.cls_num_counter = [len(cls_index) for cls_index in self.indices]

@@ -632,10 +632,16 @@ def _check_input(x):
 
 
 class Net_MDA(nn.Module):
-    """model/Model.py:452-520.  model_name in {'Pointnet', 'Pointnet2', 'DGCNN', 'PTran', 'KPConv'}."""
+    """model/Model.py:452-520.  model_name in {'Pointnet', 'Pointnet2', 'DGCNN', 'PTran', 'KPConv'}.  num_class (the reference
+    builds both heads for PointDA-10's ten): the width of both heads' last layer, at least 2; the default leaves the
+    state_dict as it was.  The steps read the count back from c1.mlp3.out_features."""
 
-    def __init__(self, model_name='Pointnet'):
+    def __init__(self, model_name='Pointnet', num_class=10):
         super(Net_MDA, self).__init__()
+        if int(num_class) != num_class or num_class < 2:
+            raise ValueError('Net_MDA: num_class must be an integer of at least 2 (got %r)' % (num_class,))
+        num_class = int(num_class)
+        self.num_class = num_class
         self.dgcnn_flag = False
         self.PTran_flag = False
         if model_name == 'Pointnet':
@@ -656,11 +662,11 @@ class Net_MDA(nn.Module):
         self.attention_s = CALayer(64 * 64)
         self.attention_t = CALayer(64 * 64)
         if model_name == 'KPConv':
-            self.c1 = KPConv_c()
-            self.c2 = KPConv_c()
+            self.c1 = KPConv_c(num_class=num_class)
+            self.c2 = KPConv_c(num_class=num_class)
         else:
-            self.c1 = Pointnet_c(dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
-            self.c2 = Pointnet_c(dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
+            self.c1 = Pointnet_c(num_class=num_class, dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
+            self.c2 = Pointnet_c(num_class=num_class, dgcnn_flag=self.dgcnn_flag, PTran_flag=self.PTran_flag)
 
     # `forward(..., semantic_adaption=True, node_adaptation_s=True)` (or node_adaptation_t) is the opt-in
     # single-pass dual-output call: ONE encoder evaluation feeds the two heads AND the attention layer.  The reference

@@ -33,16 +33,19 @@ def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=No
     backbone's call) uses the same Chamfer weights as KPC=False: the reference's KPC branch (model/mmd.py:122-124)
     only calls the unpinned third-party Chamfer op another way.  NAME: CL (not dispatched by the reference, whose trainer
     nevertheless builds its criterion) is contrastive_loss_weighted with `CL_criterion`, by default
-    nn.CosineEmbeddingLoss(margin=args.get('MARGIN', 0.2), reduction='none')."""
+    nn.CosineEmbeddingLoss(margin=args.get('MARGIN', 0.2), reduction='none').  The class count of the one-hot blocks,
+    the class lists and the SDA weights is the term's args.get('NUM_CLASS', 10) (the reference hard-codes 10)."""
+    num_class = int(args.get("NUM_CLASS", 10))
     sample_weights_flag = args.get("GEO_WEIGHTS", None) or args.get("SEM_WEIGHTS", None)
     if sample_weights is None and data_s is not None and sample_weights_flag:
         sample_weights = cal_sample_weights(data_s, data_t, args, label_s=label_s, label_t=label_t)
     if args["NAME"] == "SOFT_MMD":
-        return soft_mmd(label_s, feat_s, label_t, feat_t, float(args["LABEL_SCALE"]), sample_weights=sample_weights)
+        return soft_mmd(label_s, feat_s, label_t, feat_t, float(args["LABEL_SCALE"]), sample_weights=sample_weights,
+                        num_class=num_class)
     elif args["NAME"] == "HARD_MMD":
-        return hard_mmd(label_s, feat_s, label_t, feat_t)
+        return hard_mmd(label_s, feat_s, label_t, feat_t, num_class=num_class)
     elif args["NAME"] == "MAX_HARD_MMD":
-        return max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing=args.get("PAIRING", "sorted"))
+        return max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing=args.get("PAIRING", "sorted"), num_class=num_class)
     elif args["NAME"] == "OFF":
         return mix_rbf_mmd2(feat_s, feat_t, sigma_list)
     elif args["NAME"] == "CL":
@@ -51,48 +54,63 @@ def mmd_cal(label_s, feat_s, label_t, feat_t, args: dict, data_s=None, data_t=No
     raise RuntimeError("Not Supported MMD Method")
 
 
-def cal_sample_weights(data_s, data_t, args, label_s=None, label_t=None, KPC=False):
-    """model/mmd.py:44-53."""
+def cal_sample_weights(data_s, data_t, args, label_s=None, label_t=None, KPC=False, num_class=None):
+    """model/mmd.py:44-53.  num_class: the class count of the SEM_WEIGHTS branch; None reads args.get('NUM_CLASS', 10)."""
+    if num_class is None:
+        num_class = int(args.get("NUM_CLASS", 10))
     if args.get("GEO_WEIGHTS", None):
         return geometric_weights(data_s, data_t, weighting=args["GEO_WEIGHTS"], KPC=KPC)
     elif args.get("ENTROPY_WEIGHTS", None):
         return entropy_weights(data_s, data_t, weighting=args["ENTROPY_WEIGHTS"])
     elif args.get("SEM_WEIGHTS", None):
-        return prob_weights_soft(data_s, data_t, label_s, label_t, args["LABEL_WEIGHT"], args["SEM_WEIGHTS"])
+        kw = {} if num_class == 10 else {"num_class": num_class}     # (the reference's count: the reference's own call)
+        return prob_weights_soft(data_s, data_t, label_s, label_t, args["LABEL_WEIGHT"], args["SEM_WEIGHTS"], **kw)
     raise RuntimeError("Not suppprted weighting opperation")
 
 
-def sda_weights_of(args, pred_s, pred_t, label_s, label_t):
+def sda_weights_of(args, pred_s, pred_t, label_s, label_t, num_class=None):
     """The SDA weights of one semantic MMD term from (gathered) logits and labels, with mmd_cal's own rules: weights only
     if GEO_WEIGHTS or SEM_WEIGHTS is set (model/mmd.py:28), and then cal_sample_weights' precedence GEO > ENTROPY > SEM
     (:44-53).  The batch-sharded steps of SUGStep call this, so that every launch form weights a term the way
-    mmd_cal(..., data_s=pred_s, data_t=pred_t) does."""
+    mmd_cal(..., data_s=pred_s, data_t=pred_t) does.  num_class as in cal_sample_weights."""
     if not (args.get("GEO_WEIGHTS", None) or args.get("SEM_WEIGHTS", None)):
         return None
-    return cal_sample_weights(pred_s, pred_t, args, label_s=label_s, label_t=label_t)
+    return cal_sample_weights(pred_s, pred_t, args, label_s=label_s, label_t=label_t, num_class=num_class)
 
 
-def soft_mmd(label_s, feat_s, label_t, feat_t, label_weight, sample_weights=None):
-    """model/mmd.py:56-66: MMD on [features | one-hot(label) * label_weight]."""
+def soft_mmd(label_s, feat_s, label_t, feat_t, label_weight, sample_weights=None, num_class=10):
+    """model/mmd.py:56-66: MMD on [features | one-hot(label, num_class) * label_weight]."""
     m = feat_s.shape[0]
-    Z = ops.mmd_assemble(feat_s, feat_t, label_s, label_t, label_weight)    # [2m, D+10] = [feat | onehot * weight]
+    Z = ops.mmd_assemble(feat_s, feat_t, label_s, label_t, label_weight, num_class)    # [2m, D+C] = [feat | onehot * weight]
     return ops.mix_rbf_mmd2_rows(Z, m, sample_weights, sigma_list)
 
 
-def soft_mmd_multi(label_s, label_t, terms):
+def soft_mmd_multi(label_s, label_t, terms, num_class=None):
     """[mmd_cal(label_s, feat_s, label_t, feat_t, args, data_s, data_t) for (feat_s, feat_t, args, data_s, data_t) in terms]
     for SOFT_MMD terms of one batch (model/mmd.py:25-41, :56-66; the three terms of train_dg_single_gpu.py:300-322): the
-    SDA weights per term as mmd_cal forms them, then every stage of the terms in one launch (ops.soft_mmd_multi)."""
+    SDA weights per term as mmd_cal forms them, then every stage of the terms in one launch (ops.soft_mmd_multi).
+    num_class: the one class count of all terms; None reads the terms' NUM_CLASS keys (default 10), which must agree."""
     terms = list(terms)
     for _, _, args, _, _ in terms:
         if args["NAME"] != "SOFT_MMD":
             raise RuntimeError("soft_mmd_multi: SOFT_MMD terms only")
-    ws = _terms_sample_weights(label_s, label_t, terms)
+    num_class = _terms_num_class(terms, num_class, "soft_mmd_multi")
+    ws = _terms_sample_weights(label_s, label_t, terms, num_class=num_class)
     packed = [(fs, ft, float(args["LABEL_SCALE"]), w) for (fs, ft, args, _, _), w in zip(terms, ws)]
-    return ops.soft_mmd_multi(label_s, label_t, packed, sigma_list)
+    return ops.soft_mmd_multi(label_s, label_t, packed, sigma_list, num_class=num_class)
 
 
-def _terms_sample_weights(label_s, label_t, terms):
+def _terms_num_class(terms, num_class, who):
+    """The class count of a multi-term call: the caller's, or the terms' own NUM_CLASS (default 10), one for all."""
+    if num_class is not None:
+        return int(num_class)
+    counts = {int(args.get("NUM_CLASS", 10)) for _, _, args, _, _ in terms}
+    if len(counts) > 1:
+        raise ValueError("%s: the terms of one call share one class count (NUM_CLASS: %s)" % (who, sorted(counts)))
+    return counts.pop() if counts else 10
+
+
+def _terms_sample_weights(label_s, label_t, terms, num_class=10):
     """The SDA weights of every (feat_s, feat_t, args, data_s, data_t) term of one batch as mmd_cal would form them (None
     for a term without), the terms weighted from head logits by one rule in one launch."""
     ws = [None] * len(terms)
@@ -102,10 +120,10 @@ def _terms_sample_weights(label_s, label_t, terms):
         if data_s is None or not (args.get("GEO_WEIGHTS", None) or args.get("SEM_WEIGHTS", None)):
             continue
         if args.get("SEM_WEIGHTS", None) and not args.get("GEO_WEIGHTS", None) and not args.get("ENTROPY_WEIGHTS", None) \
-                and data_s.is_cuda and data_s.shape[-1] == 10:
+                and data_s.is_cuda and data_s.shape[-1] == num_class and 2 <= num_class <= ops.SDA_MAX_CLASSES:
             by_rule.setdefault((float(args["LABEL_WEIGHT"]), args["SEM_WEIGHTS"]), []).append(i)
         else:
-            ws[i] = cal_sample_weights(data_s, data_t, args, label_s=label_s, label_t=label_t)
+            ws[i] = cal_sample_weights(data_s, data_t, args, label_s=label_s, label_t=label_t, num_class=num_class)
     for (lw, rule), idx in by_rule.items():
         assert lw < 1, "For Entropy, Label weight should be less than one"
         outs = ops.sda_prob_weights_multi([(terms[i][3], terms[i][4]) for i in idx], label_s, label_t, lw, rule)
@@ -114,16 +132,16 @@ def _terms_sample_weights(label_s, label_t, terms):
     return ws
 
 
-def cl_loss_multi(label_s, label_t, terms):
+def cl_loss_multi(label_s, label_t, terms, num_class=None):
     """[mmd_cal(label_s, feat_s, label_t, feat_t, args, data_s, data_t) for (feat_s, feat_t, args, data_s, data_t) in terms]
     for NAME: CL terms of one batch, the sibling of soft_mmd_multi: the SDA weights per term as mmd_cal forms them, then
     all terms in one launch sequence (ops.cl_loss_multi) where ops.cl_loss_supported holds for every one of them, term by
-    term through contrastive_loss_weighted otherwise."""
+    term through contrastive_loss_weighted otherwise.  num_class (the SDA weights' class count) as in soft_mmd_multi."""
     terms = list(terms)
     for _, _, args, _, _ in terms:
         if args["NAME"] != "CL":
             raise RuntimeError("cl_loss_multi: CL terms only")
-    ws = _terms_sample_weights(label_s, label_t, terms)
+    ws = _terms_sample_weights(label_s, label_t, terms, num_class=_terms_num_class(terms, num_class, "cl_loss_multi"))
     margins = [float(args.get("MARGIN", 0.2)) for _, _, args, _, _ in terms]
     if all(ops.cl_loss_supported(label_s, fs, label_t, ft, mg, w) for (fs, ft, _, _, _), mg, w in zip(terms, margins, ws)):
         return ops.cl_loss_multi(label_s, label_t, [(fs, ft, mg, w) for (fs, ft, _, _, _), mg, w in zip(terms, margins, ws)])
@@ -132,22 +150,23 @@ def cl_loss_multi(label_s, label_t, terms):
 
 
 def soft_mmd_sharded(label_s, feat_s, label_t, feat_t, label_g, feat_g_s, label_tg, feat_g_t, label_weight, row0,
-                     sample_weights=None, world=1):
+                     sample_weights=None, world=1, num_class=10):
     """soft_mmd of the GLOBAL batch from a rank's shard: feat_s / feat_t [mloc, D] are this
     rank's (differentiable) features, feat_g_s / feat_g_t [M, D] the gathered values of all ranks (this
     rank's rows at row0); equals soft_mmd(label_g, feat_g_s, label_tg, feat_g_t, ...) on every rank."""
     mloc, M = feat_s.shape[0], feat_g_s.shape[0]
-    Zloc = ops.mmd_assemble(feat_s, feat_t, label_s, label_t, label_weight)
-    Zall = ops.mmd_assemble(feat_g_s.detach(), feat_g_t.detach(), label_g, label_tg, label_weight)
+    Zloc = ops.mmd_assemble(feat_s, feat_t, label_s, label_t, label_weight, num_class)
+    Zall = ops.mmd_assemble(feat_g_s.detach(), feat_g_t.detach(), label_g, label_tg, label_weight, num_class)
     return ops.mix_rbf_mmd2_rows_sharded(Zloc, Zall, mloc, M, row0, sample_weights, sigma_list, world)
 
 
-def hard_mmd(label_s, feat_s, label_t, feat_t):
+def hard_mmd(label_s, feat_s, label_t, feat_t, num_class=10):
     """model/mmd.py:69-77: MMD of the rows whose two labels agree.  On the device the rows are chosen there
     (ops.class_mmd, mode 0): no host wait, and a batch without such a row gives NaN with zero gradients as in the
-    reference; otherwise (CPU tensors, beyond ops.class_mmd_supported's limits, SUG_CLASS_MMD=0) the composed lines."""
-    if ops.class_mmd_supported(label_s, feat_s, label_t, feat_t, sigma_list):
-        return ops.class_mmd(label_s, feat_s, label_t, feat_t, 0, sigma_list)
+    reference; otherwise (CPU tensors, beyond ops.class_mmd_supported's limits, SUG_CLASS_MMD=0) the composed lines.
+    num_class only sizes the device kernel's class table: which rows agree does not depend on it."""
+    if ops.class_mmd_supported(label_s, feat_s, label_t, feat_t, sigma_list, num_class=num_class):
+        return ops.class_mmd(label_s, feat_s, label_t, feat_t, 0, sigma_list, num_class=num_class)
     same = torch.eq(label_s, label_t)
     return mix_rbf_mmd2(feat_s[same], feat_t[same], sigma_list)
 
@@ -169,20 +188,20 @@ def contrastive_loss_weighted(label_s, feat_s, label_t, feat_t, label_weight, CL
     return torch.mean(loss)
 
 
-def max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing='sorted'):
+def max_hard_mmd(label_s, feat_s, label_t, feat_t, pairing='sorted', num_class=10):
     """model/mmd.py:96-104.  pairing 'sorted' (the default) pairs the rows get_most_overlapped_element picks on the host:
     which members of an over-represented class those are follows from torch.sort's unstable order once m > 16.  pairing
     'stable' (args['PAIRING'] = 'stable') pairs the same NUMBER of rows per class but always the lowest indices
     (class_pairs_host, mode 1), chosen on the device (ops.class_mmd, mode 1: no host wait, capturable); it needs what
-    ops.class_mmd_supported states.  Labels outside [0, 10) are never paired there and raise nothing."""
+    ops.class_mmd_supported states.  Labels outside [0, num_class) are never paired there and raise nothing."""
     if pairing == 'stable':
-        if not ops.class_mmd_supported(label_s, feat_s, label_t, feat_t, sigma_list):
+        if not ops.class_mmd_supported(label_s, feat_s, label_t, feat_t, sigma_list, num_class=num_class):
             raise RuntimeError("max_hard_mmd(pairing='stable') runs on the HIP device within ops.class_mmd_supported's limits "
                                "(and not with SUG_CLASS_MMD=0)")
-        return ops.class_mmd(label_s, feat_s, label_t, feat_t, 1, sigma_list)
+        return ops.class_mmd(label_s, feat_s, label_t, feat_t, 1, sigma_list, num_class=num_class)
     if pairing != 'sorted':
         raise RuntimeError("max_hard_mmd: pairing 'sorted' or 'stable' (got %r)" % (pairing,))
-    ind_s, ind_t = get_most_overlapped_element(label_s.cpu(), label_t.cpu())
+    ind_s, ind_t = get_most_overlapped_element(label_s.cpu(), label_t.cpu(), num_class=num_class)
     assert len(ind_s) == len(ind_t), "The feature shape mis-matched"
     return mix_rbf_mmd2(feat_s[ind_s], feat_t[ind_t], sigma_list)
 
@@ -279,15 +298,22 @@ def entropy_weights(pred_s, pred_t, weighting="exp_inverse"):
     return distance2weights(distances=entropy_dis(pred_s, pred_t), method=weighting).reshape(1, -1)
 
 
-def prob_weights_soft(pred_s, pred_t, label_s, label_t, label_weight, weighting="mean2one"):
-    """model/mmd.py:134-148, on the device."""
+def prob_weights_soft(pred_s, pred_t, label_s, label_t, label_weight, weighting="mean2one", num_class=10):
+    """model/mmd.py:134-148, on the device.  num_class (10 in the reference) is the width of the logits: a mismatch is a
+    ValueError.  HIP tensors of 2 to ops.SDA_MAX_CLASSES (64) classes go through one kernel; CPU tensors and wider logits
+    through the composed lines below with the same count.  In the kernel a label outside [0, num_class) gets no one-hot
+    entry and raises nothing (the composed lines scatter with it and fail as torch does)."""
     assert label_weight < 1, "For Entropy, Label weight should be less than one"
-    if pred_s.is_cuda and pred_s.shape[-1] == 10:                      # one kernel instead of ~40 tiny ones
+    num_class = int(num_class)
+    if pred_s.shape[-1] != num_class or pred_t.shape[-1] != num_class:
+        raise ValueError("prob_weights_soft: the logits are %d / %d wide but num_class is %d"
+                         % (pred_s.shape[-1], pred_t.shape[-1], num_class))
+    if pred_s.is_cuda and 2 <= num_class <= ops.SDA_MAX_CLASSES:        # one kernel instead of ~40 tiny ones
         return ops.sda_prob_weights(pred_s, pred_t, label_s, label_t, label_weight, weighting).reshape(1, -1)
-    a = torch.cat((torch.softmax(pred_s.detach(), dim=1).view(-1, 10),
-                   create_one_hot_labels(label_s) * label_weight), dim=1)
-    b = torch.cat((torch.softmax(pred_t.detach(), dim=1).view(-1, 10),
-                   create_one_hot_labels(label_t) * label_weight), dim=1)
+    a = torch.cat((torch.softmax(pred_s.detach(), dim=1).view(-1, num_class),
+                   create_one_hot_labels(label_s, num_class) * label_weight), dim=1)
+    b = torch.cat((torch.softmax(pred_t.detach(), dim=1).view(-1, num_class),
+                   create_one_hot_labels(label_t, num_class) * label_weight), dim=1)
     a, b = normalized(a), normalized(b)
     distance = (_kl_div(a, b) * 0.5 + _kl_div(b, a) * 0.5).sum(1)
     return distance2weights(distances=distance, method=weighting).reshape(1, -1)

@@ -3572,20 +3572,33 @@ def edge_weight_split_multi(Ws):
 _SDA_METHODS = {'none': 0, 'naive_inverse': 1, 'exp_inverse': 2, 'mean2one': 3}
 
 
+SDA_MAX_CLASSES = _H['SUG_SDA_MAX_CLASSES']
+
+
+def _sda_num_class(*preds):
+    """The class count of SDA logits: their common width (the kernel states its own range, 2..SDA_MAX_CLASSES)."""
+    C = int(preds[0].shape[-1])
+    if any(int(p.shape[-1]) != C for p in preds):
+        raise RuntimeError('sda_prob_weights: logits of one width (got %s)' % sorted({int(p.shape[-1]) for p in preds}))
+    return C
+
+
 def sda_prob_weights(pred_s, pred_t, label_s, label_t, label_weight, method):
-    """SDA weights [m] from logits [m,10] and labels [m] (prob_weights_soft + distance2weights,
-    model/mmd.py:134-148, :178-202) in one kernel."""
+    """SDA weights [m] from logits [m,C] and labels [m] (prob_weights_soft + distance2weights,
+    model/mmd.py:134-148, :178-202) in one kernel.  C = the logits' width, 2..SDA_MAX_CLASSES (the reference: 10).  A label
+    outside [0, C) gets no one-hot entry and raises nothing."""
     _need_gpu(pred_s, pred_t, label_s, label_t)
     if method not in _SDA_METHODS:
         raise RuntimeError('Not supported weighting method %s' % method)
-    ps = pred_s.detach().reshape(-1, 10).float()
-    pt = pred_t.detach().reshape(-1, 10).float()
+    C = _sda_num_class(pred_s, pred_t)
+    ps = pred_s.detach().reshape(-1, C).float()
+    pt = pred_t.detach().reshape(-1, C).float()
     ps = ps if ps.stride(1) == 1 else ps.contiguous()
     pt = pt if pt.stride(1) == 1 else pt.contiguous()
     ls, lt = label_s.reshape(-1).long().contiguous(), label_t.reshape(-1).long().contiguous()
     m = ps.shape[0]
     out = torch.empty(m, dtype=torch.float32, device=ps.device)
-    check(lib().sug_sda_prob_weights(_p(ps), ps.stride(0), _p(pt), pt.stride(0), _p(ls), _p(lt), m, 10,
+    check(lib().sug_sda_prob_weights(_p(ps), ps.stride(0), _p(pt), pt.stride(0), _p(ls), _p(lt), m, C,
                                      float(label_weight), _SDA_METHODS[method], _p(out), _st()),
           'sug_sda_prob_weights')
     return out
@@ -3601,7 +3614,8 @@ def sda_prob_weights_multi(preds, label_s, label_t, label_weight, method):
             sda_prob_weights_multi(preds[4:], label_s, label_t, label_weight, method)
     if method not in _SDA_METHODS:
         raise RuntimeError('Not supported weighting method %s' % method)
-    rows = lambda p: (lambda q: q if q.stride(1) == 1 else q.contiguous())(p.detach().reshape(-1, 10).float())
+    C = _sda_num_class(*[t for pr in preds for t in pr])
+    rows = lambda p: (lambda q: q if q.stride(1) == 1 else q.contiguous())(p.detach().reshape(-1, C).float())
     ps, pt = [rows(a) for a, _ in preds], [rows(b) for _, b in preds]
     _need_gpu(label_s, label_t, *(ps + pt))
     ls, lt = label_s.reshape(-1).long().contiguous(), label_t.reshape(-1).long().contiguous()
@@ -3611,7 +3625,7 @@ def sda_prob_weights_multi(preds, label_s, label_t, label_weight, method):
     outs = [torch.empty(m, dtype=torch.float32, device=ps[0].device) for _ in range(n)]
     I64 = ctypes.c_int64 * n
     check(lib().sug_sda_prob_weights_multi(n, _ptrs(ps), I64(*[t.stride(0) for t in ps]), _ptrs(pt), I64(*[t.stride(0) for t in pt]),
-                                           _p(ls), _p(lt), m, 10, float(label_weight), _SDA_METHODS[method], _ptrs(outs), _st()),
+                                           _p(ls), _p(lt), m, C, float(label_weight), _SDA_METHODS[method], _ptrs(outs), _st()),
           'sug_sda_prob_weights_multi')
     return outs
 

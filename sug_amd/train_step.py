@@ -226,6 +226,26 @@ def _params_above_encoder(model):
     return [p for m in (model.c1, model.c2, model.attention_s, model.attention_t) for p in m.parameters()]
 
 
+def model_num_class(model):
+    """The class count of a Net_MDA-shaped model: the width of its first head's last layer."""
+    return int(model.c1.mlp3.out_features)
+
+
+def with_num_class(entries, num_class, who):
+    """The step's own copies of MMD term dicts (METHODS['GEO_MMD'] / ['SEM_MMD'], UDAStep's class_mmd), each with the
+    model's class count under NUM_CLASS.  An entry that names another count is a ValueError: the one-hot blocks and the SDA
+    weights of a term are as wide as the logits."""
+    out = []
+    for e in entries:
+        e = dict(e)
+        if int(e.setdefault('NUM_CLASS', num_class)) != num_class:
+            raise ValueError('%s: NUM_CLASS %r of the term %r differs from the model\'s %d classes'
+                             % (who, e['NUM_CLASS'], e.get('NAME'), num_class))
+        e['NUM_CLASS'] = num_class
+        out.append(e)
+    return out
+
+
 def cls_loss_coefficients(methods):
     """(a_s, a_t, a_d) with which a_s*Ls + a_t*Lt - a_d*D (Ls, Lt: the criterion of both heads summed, on source and target
     rows; D: the heads' discrepancy) is the composed classification loss of SUGStep.losses (train_dg_single_gpu.py:269-292):
@@ -269,6 +289,10 @@ class SUGStep:
         self.methods = dict(METHODS)
         if methods:
             self.methods.update(methods)
+        # the class count is the model's (Net_MDA(..., num_class=C)); every MMD term of the step carries it
+        self.num_class = model_num_class(model)
+        for k in ('GEO_MMD', 'SEM_MMD'):
+            self.methods[k] = with_num_class(self.methods[k], self.num_class, 'SUGStep: METHODS[%r]' % k)
         self.criterion = criterion if criterion is not None else nn.CrossEntropyLoss()
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # force_segmented: the multi-rank launch form (graph segments + collectives) even on ONE rank of an initialised
@@ -378,12 +402,12 @@ class SUGStep:
             w_geo = mmd.distance2weights(g[12].reshape(-1), geo['GEO_WEIGHTS']).reshape(1, -1)
         loss_geo = M_['MMD_WEIGHT'] * geo['GEO_SCALE'] * mmd.soft_mmd_sharded(
             label, node_s, label_t, node_t, label_g, fn_s, label_tg, fn_t, float(geo['LABEL_SCALE']), row0, w_geo,
-            self.world)
+            self.world, num_class=self.num_class)
         terms = []
         for (fs, ft, gs, gt, gps, gpt) in ((s1, t1, g_s1, g_t1, g_p1s, g_p1t), (s2, t2, g_s2, g_t2, g_p2s, g_p2t)):
             w = mmd.sda_weights_of(sem, gps, gpt, label_g, label_tg)      # mmd_cal's rules (GEO > ENTROPY > SEM)
             terms.append(mmd.soft_mmd_sharded(label, fs, label_t, ft, label_g, gs, label_tg, gt,
-                                              float(sem['LABEL_SCALE']), row0, w, self.world))
+                                              float(sem['LABEL_SCALE']), row0, w, self.world, num_class=self.num_class))
         return loss_geo, (0.5 * M_['MMD_WEIGHT'] * sem['SEM_SCALE']) * (terms[0] + terms[1])
 
     def _cls_loss_tail(self, rec, ys1, ys2, yt1, yt2, label):
@@ -558,7 +582,8 @@ class SUGStep:
         whole schedule); any other optimizer takes lr by value, so its lr of every group is part of the key."""
         c = self.criterion
         crit = ('ce', int(c.ignore_index)) if plain_ce(c) else (self._crit.record(c, self.max_graphs) or ('call', id(c), repr(c)))
-        key = (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()), crit)
+        key = (mmd_on, self.single_pass, tuple(tuple(t.shape) for t in tensors), tuple(hyper_key(o) for o in self._opts()), crit,
+               ('num_class', self.num_class))
         caps = getattr(self.model.g, 'level_caps', None)    # KPConv_g: the level capacities size every launch
         return key if caps is None else key + (('level_caps', caps),)
 
@@ -724,8 +749,8 @@ class SUGStep:
                 w = mmd.sda_weights_of(sem, gps, gpt, label_g, label_tg)  # mmd_cal's rules (GEO > ENTROPY > SEM)
                 specs.append((fs, ft, gs, gt, float(sem['LABEL_SCALE']), w))
             for i, (fs, ft, gs, gt, lsc, w) in enumerate(specs):
-                Zloc = ops.mmd_assemble(fs, ft, label, label_t, lsc)
-                Zall = ops.mmd_assemble(gs.detach(), gt.detach(), label_g, label_tg, lsc)
+                Zloc = ops.mmd_assemble(fs, ft, label, label_t, lsc, self.num_class)
+                Zall = ops.mmd_assemble(gs.detach(), gt.detach(), label_g, label_tg, lsc, self.num_class)
                 Za, wt = ops.mmd_rows_local_sums(Zall, M_all, row0, mloc, w, sums[i])
                 terms.append((Zloc, Za, wt))
             S['terms'], S['M_all'], S['row0'] = terms, M_all, row0

@@ -65,7 +65,10 @@ class UDAStep(ReplayedStep):
         self.a_s, self.a_t, self.r_s = recipe_constants(recipe, src_weight, target_loss)
         self.model, self.recipe = model, recipe
         self.src_weight, self.target_loss = float(src_weight), float(target_loss)
-        self.class_mmd = dict(class_mmd) if class_mmd is not None else dict(CLASS_MMD)
+        from .train_step import model_num_class, with_num_class
+        self.num_class = model_num_class(model)         # the model's class count; the node term carries it (part of the graph key)
+        self.class_mmd = with_num_class([class_mmd if class_mmd is not None else CLASS_MMD], self.num_class,
+                                        'UDAStep: class_mmd')[0]
         self.base_lr, self.lr_scaler = float(lr), float(lr_scaler)
         self.c_lr = self.base_lr * 2 if recipe == 'uda' else self.base_lr           # train_uda.py:107 / train_dg_naive_mmd.py:179
         self.remain_epoch = 50 if recipe == 'uda' else 0                            # train_uda.py:99 / train_dg_naive_mmd.py:168
