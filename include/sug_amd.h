@@ -868,6 +868,19 @@ int sug_chamfer(const float* a, const float* b, int B, int N, int M, float* out,
  * of pair b; method 1 naive_inverse, 2 exp_inverse, 3 mean2one (1 / mean truncated to an integer, :200).  Sums over the
  * batch in fp64, fixed order. */
 int sug_chamfer_weights(const float* a, const float* b, int B, int N, int M, int method, float* out, float* ws, void* stream);
+/* ChamferDistance as an op (the third-party op model/mmd.py imports; cd_distance, model/mmd.py:169-175 -- parity unpinned as
+ * above): dist1[b,i] = min_j d(a_i, b_j), idx1[b,i] = the LOWEST j attaining it, dist2 / idx2 [B,M] the same for b against a;
+ * d = ((dx*dx + dy*dy) + dz*dz) of the fp32 differences, every operation rounded once (bit-reproducible on a CPU).
+ * a [B,N,3], b [B,M,3] contiguous, 1 <= N, M <= SUG_CHAMFER_MAX_POINTS, N != M allowed, B <= 65535.  One launch, no workspace. */
+#define SUG_CHAMFER_MAX_POINTS 5000
+int sug_chamfer_nn(const float* a, const float* b, int B, int N, int M, float* dist1, float* dist2, int32_t* idx1, int32_t* idx2,
+                   void* stream);
+/* Its gradient for upstream g1 [B,N], g2 [B,M]: ga_i = 2 g1_i (a_i - b_idx1[i]) + sum_{j: idx2[j] = i} 2 g2_j (a_i - b_j) over j
+ * ascending, gb the symmetric form; written, not accumulated.  ga or gb may be null: that side is skipped.  No atomics: a
+ * point's terms are added in an order fixed by the indices inside its cloud pair (chamfer.hip), whatever B and the pair's
+ * place in the batch.  An index outside the other cloud is not followed (that point's gradient is NaN).  One launch. */
+int sug_chamfer_nn_bwd(const float* g1, const float* g2, const float* a, const float* b, const int32_t* idx1, const int32_t* idx2,
+                       int B, int N, int M, float* ga, float* gb, void* stream);
 
 /* ---- the scalar tail of a step ---------------------------------------------------------------------------
  * Cross entropy of both classifier heads on the source rows of the paired logits (train_dg_single_gpu.py:269-292 with

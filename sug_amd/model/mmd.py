@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..chamfer_distance import ChamferDistance  # noqa: F401  (model/mmd.py:9 imports the third-party op under this name)
 from ..utils.common_utils import create_one_hot_labels, get_most_overlapped_element
 
 min_var_est = 1e-8
@@ -234,6 +235,18 @@ def chamfer_distances(pc_s, pc_t):
     """Per-pair Chamfer distance [m] of paired clouds ([m,3,N(,1)] or [m,N,3]): cd_distance,
     model/mmd.py:169-175 (mean of dist1 + mean of dist2)."""
     return ops.chamfer(*_chamfer_rows(pc_s, pc_t))
+
+
+def cd_distance(pc1, pc2, chamfer_dist, batch_loss=True):
+    """model/mmd.py:169-175: the Chamfer loss of paired clouds pc1 [B,N,3], pc2 [B,M,3] through the op `chamfer_dist` (a
+    ChamferDistance()): per pair [B] (batch_loss=True) or the scalar mean(dist1) + mean(dist2).  Differentiable with respect
+    to both clouds in both forms (geometric_weights and chamfer_distances keep their detached one-launch path)."""
+    dist1, dist2, idx1, idx2 = chamfer_dist(pc1, pc2)
+    if not batch_loss:
+        loss = (torch.mean(dist1)) + (torch.mean(dist2))
+    else:
+        loss = torch.mean(dist1, dim=1) + torch.mean(dist2, dim=1)
+    return loss
 
 
 def _chamfer_rows(pc_s, pc_t):

@@ -3657,6 +3657,52 @@ def chamfer_weights(a, b, method):
     return out
 
 
+CHAMFER_MAX_POINTS = _H['SUG_CHAMFER_MAX_POINTS']
+
+
+class _ChamferNN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = a.contiguous(), b.contiguous()
+        B, N, _ = a.shape
+        M = b.shape[1]
+        dist1 = torch.empty(B, N, dtype=torch.float32, device=a.device)
+        dist2 = torch.empty(B, M, dtype=torch.float32, device=a.device)
+        idx1 = torch.empty(B, N, dtype=torch.int32, device=a.device)
+        idx2 = torch.empty(B, M, dtype=torch.int32, device=a.device)
+        check(lib().sug_chamfer_nn(_p(a), _p(b), B, N, M, _p(dist1), _p(dist2), _p(idx1), _p(idx2), _st()), 'sug_chamfer_nn')
+        ctx.save_for_backward(a, b, idx1, idx2)
+        ctx.mark_non_differentiable(idx1, idx2)
+        return dist1, dist2, idx1, idx2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g1, g2, _gi1, _gi2):
+        a, b, idx1, idx2 = ctx.saved_tensors
+        B, N, _ = a.shape
+        M = b.shape[1]
+        ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None        # a side without a gradient: a null pointer
+        gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        check(lib().sug_chamfer_nn_bwd(_p(g1.contiguous()), _p(g2.contiguous()), _p(a), _p(b), _p(idx1), _p(idx2), B, N, M,
+                                       _p(ga), _p(gb), _st()), 'sug_chamfer_nn_bwd')
+        return ga, gb
+
+
+def chamfer_nn(a, b):
+    """a [B,N,3], b [B,M,3] fp32 rows -> (dist1 [B,N], dist2 [B,M], idx1 [B,N], idx2 [B,M] int32): the squared distance of
+    every point to its nearest neighbour in the other cloud and that neighbour's index (the lowest one on exact ties).
+    dist1 / dist2 carry the gradient to both clouds (first order only; a point's terms are added in a fixed order, no
+    atomics); the indices are not differentiable.  1 <= N, M <= CHAMFER_MAX_POINTS."""
+    _need_gpu(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise RuntimeError('chamfer_nn: fp32 clouds only (got %s, %s)' % (a.dtype, b.dtype))
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
+        raise RuntimeError('chamfer_nn: clouds are rows [B,N,3] and [B,M,3] (got %s, %s)' % (tuple(a.shape), tuple(b.shape)))
+    if a.shape[0] != b.shape[0]:
+        raise RuntimeError('chamfer_nn: %d clouds against %d: the clouds are paired' % (a.shape[0], b.shape[0]))
+    return _ChamferNN.apply(a, b)
+
+
 # ----------------------------------------------------------------------------- KPConv backbone
 # Packed clouds (rows of all clouds of a level back to back) with int32 device offsets off [B+1]; neighbour tables
 # [Nq, H] int32 whose missing slots hold the shadow index Ns (sug_amd/csrc/kpconv.hip).
