@@ -219,6 +219,14 @@ int sug_col_stats_bn(const float* y, int64_t ldy, int64_t rows, int C, const flo
 int sug_col_stats_bn_grouped(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
                              const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                              float* coef, float* ws, void* stream);
+/* The same with the bits of `groups` sug_col_stats_bn calls at every size: the grouped launch above shares one workspace
+ * among the groups and, for tall inputs, cuts them into fewer workgroups than separate calls would (other fp32 partial
+ * sums).  Here every group is cut and folded exactly as a call of its own, which needs a workspace block per group:
+ * ws = groups * SUG_STATS_BLOCKS * 2*C floats (block g: the partial rows and the pivot row of group g).  One launch pair
+ * for 2..16 groups in a float4 layout, else the calls one after the other (in block 0). */
+int sug_col_stats_bn_groups_exact(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
+                                  const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                                  float* coef, float* ws, void* stream);
 
 /* Replay of the running-statistics update for G more train-mode forwards over batches whose
  * statistics are already in coef [G,5,C] (rows 2 and 4 of each group), in group order, with
@@ -294,6 +302,16 @@ int sug_gate_bn_fwd(const float* x, const float* z, int M, int C, const float* g
                     float* stat, void* stream);
 int sug_gate_bn_bwd(const float* g, const float* x, const float* z, int M, int C, const float* gamma, const float* stat,
                     int training, float* dx, float* dz, float* dgamma, float* dbeta, void* stream);
+/* The same for 1 <= layers <= 4 attention layers in one launch each way (attention_s / attention_t on the two row blocks
+ * of a paired batch): layer l owns rows [l*M, (l+1)*M) of the dense x, z, out, g, dx, dz [layers*M, C], stat + l*2C and
+ * dgb + l*2C (dgb [layers][2][C] = dgamma | dbeta); gamma, beta, running_mean, running_var are HOST arrays of `layers`
+ * device pointers (the two buffer arrays, or their entries, null: not tracked).  Per layer bit for bit the calls above. */
+int sug_gate_bn_fwd_multi(int layers, const float* x, const float* z, int M, int C, const void* const* gamma,
+                          const void* const* beta, void* const* running_mean, void* const* running_var, int training,
+                          float eps, float momentum, float* out, float* stat, void* stream);
+int sug_gate_bn_bwd_multi(int layers, const float* g, const float* x, const float* z, int M, int C,
+                          const void* const* gamma, const float* stat, int training, float* dx, float* dz, float* dgb,
+                          void* stream);
 
 /* ---- Channel attention (CALayer, model/Model.py:16-34) for up to two attention layers per launch ------------------
  * v [M, C] -> h = relu(v . W0^T + b0) [M, Hd] -> z = h . W2^T + b2 [M, C] (the two 1x1 Conv2d on a 1x1 map; the gate
@@ -562,6 +580,19 @@ int sug_bn_act_pool_layer_bwd(const float* y, int64_t ldy, const float* coef, co
                               const float* gmean, int64_t ld_pool, const int32_t* arg, int B, int N, int C, int groups,
                               float slope, int training, double* red, float* ws, float* dy, int64_t lddy,
                               float* dgb, void* stream);
+/* The same two entry points with every domain group in each launch (train mode, 2..16 groups, float4 layout; B*4 <=
+ * SUG_STATS_BLOCKS and C/4 dividing 256 for the backward): 2 + 2 launches forward and 3 backward whatever `groups` is,
+ * bit for bit the results of the per-group loops above, which run in every other case.  Other workspaces:
+ * ws_stats = groups * SUG_STATS_BLOCKS * 2*C floats (sug_col_stats_bn_groups_exact), ws_pool = 12*B*C floats. */
+int sug_bn_act_pool_groups_fwd(const float* y, int64_t ldy, int B, int N, int C, int groups,
+                               const float* gamma, const float* beta, int training, float eps, float momentum,
+                               float slope, float* running_mean, float* running_var, float* coef,
+                               float* out_max, float* out_mean, int64_t ld_pool, int32_t* arg, double* stats, float* ws_stats,
+                               float* ws_pool, void* stream);
+int sug_bn_act_pool_groups_bwd(const float* y, int64_t ldy, const float* coef, const float* gmax,
+                               const float* gmean, int64_t ld_pool, const int32_t* arg, int B, int N, int C, int groups,
+                               float slope, int training, double* red, float* ws, float* dy, int64_t lddy,
+                               float* dgb, void* stream);
 
 /* ---- per-point MLP layer fused with the max over a group of rows ------------------------------
  * replaces `conv_2d(K, Co)` (1x1 Conv2d + bias -> BatchNorm2d -> ReLU) followed by the max over the
@@ -868,6 +899,11 @@ int sug_chamfer(const float* a, const float* b, int B, int N, int M, float* out,
  * of pair b; method 1 naive_inverse, 2 exp_inverse, 3 mean2one (1 / mean truncated to an integer, :200).  Sums over the
  * batch in fp64, fixed order. */
 int sug_chamfer_weights(const float* a, const float* b, int B, int N, int M, int method, float* out, float* ws, void* stream);
+/* The two entry points above with both directions (a -> b, b -> a) in ONE launch instead of two: same workspace, same
+ * partial sums in the same places, same fold; the results are bit-identical. */
+int sug_chamfer_merged(const float* a, const float* b, int B, int N, int M, float* out, float* ws, void* stream);
+int sug_chamfer_weights_merged(const float* a, const float* b, int B, int N, int M, int method, float* out, float* ws,
+                               void* stream);
 /* ChamferDistance as an op (the third-party op model/mmd.py imports; cd_distance, model/mmd.py:169-175 -- parity unpinned as
  * above): dist1[b,i] = min_j d(a_i, b_j), idx1[b,i] = the LOWEST j attaining it, dist2 / idx2 [B,M] the same for b against a;
  * d = ((dx*dx + dy*dy) + dz*dz) of the fp32 differences, every operation rounded once (bit-reproducible on a CPU).

@@ -101,7 +101,7 @@ __device__ __forceinline__ float lrelu(float u, float slope) { return u > 0.f ? 
 // (C % 4 != 0) uses 64 scalar lanes x 4 row-lanes through the same code path (VEC = 1).
 template <int VEC>
 __global__ __launch_bounds__(256) void bn_act_pool_part_kernel(const float* __restrict__ y, int64_t ldy,
-                                                               const float* __restrict__ coef, int N,
+                                                               const float* __restrict__ coef, int Bg, int N,
                                                                int C, float slope,
                                                                float* __restrict__ pmax,
                                                                float* __restrict__ psum,
@@ -111,6 +111,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_part_kernel(const float* __re
   __shared__ float s_s[LY][64];
   __shared__ int s_a[LY][64];
   const int b = blockIdx.y, ch = blockIdx.z;
+  coef += (int64_t)(b / Bg) * 5 * C;             // coefficient set of the cloud's domain group (Bg clouds each)
   const int lx = threadIdx.x % LX, ly = threadIdx.x / LX;
   const int c = blockIdx.x * 64 + lx * VEC;
   const int n0 = (int)((int64_t)N * ch / NS), n1 = (int)((int64_t)N * (ch + 1) / NS);
@@ -190,12 +191,13 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float* __res
                                                               const float* __restrict__ coef,
                                                               const float* __restrict__ gmax,
                                                               const float* __restrict__ gmean, int64_t ldp,
-                                                              const int32_t* __restrict__ arg, int N,
+                                                              const int32_t* __restrict__ arg, int Bg, int N,
                                                               int C, float slope, float* __restrict__ ws) {
   constexpr int LX = 64 / VEC, LY = 256 / LX;
   __shared__ float s_g[LY][64];
   __shared__ float s_x[LY][64];
   const int b = blockIdx.y, ch = blockIdx.z;
+  coef += (int64_t)(b / Bg) * 5 * C;
   const int lx = threadIdx.x % LX, ly = threadIdx.x / LX;
   const int c = blockIdx.x * 64 + lx * VEC;
   const int n0 = (int)((int64_t)N * ch / NS), n1 = (int)((int64_t)N * (ch + 1) / NS);
@@ -296,11 +298,14 @@ __global__ __launch_bounds__(256) void pool_bwd_apply_rows_kernel(const float* _
                                                                   const double* __restrict__ red,
                                                                   const float* __restrict__ gmax,
                                                                   const float* __restrict__ gmean, int64_t ldp,
-                                                                  const int32_t* __restrict__ arg, int N, int C,
+                                                                  const int32_t* __restrict__ arg, int Bg, int N, int C,
                                                                   int rows_per_block, float slope, float invM,
-                                                                  float* __restrict__ dy, int64_t lddy) {
+                                                                  float* __restrict__ dy, int64_t lddy, int last_first) {
   const int CV = C >> 2;
-  const int b = blockIdx.y;
+  // last_first: clouds in descending order, so that the launch starts on the rows the reduce pass before it read last
+  const int b = last_first ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
+  coef += (int64_t)(b / Bg) * 5 * C;             // the cloud's domain group (Bg clouds each): its coefficients and sums
+  red += (int64_t)(b / Bg) * 2 * C;
   const int cg = threadIdx.x % CV, rl = threadIdx.x / CV, rstep = 256 / CV;
   const int c = cg * 4;
   float sc[4], sh[4], mu[4], rs[4], r0[4], r1[4], gme[4], gmx[4];
@@ -520,9 +525,9 @@ extern "C" int sug_bn_act_pool_fwd(const float* y, int64_t ldy, const float* coe
   int32_t* parg = reinterpret_cast<int32_t*>(ws + 2 * part);
   dim3 grid(sug_divup(C, 64), B, NS);
   if (vec4_ok(y, ldy, C))
-    hipLaunchKernelGGL((bn_act_pool_part_kernel<4>), grid, dim3(256), 0, st, y, ldy, coef, N, C, slope, pmax, psum, parg);
+    hipLaunchKernelGGL((bn_act_pool_part_kernel<4>), grid, dim3(256), 0, st, y, ldy, coef, B, N, C, slope, pmax, psum, parg);
   else
-    hipLaunchKernelGGL((bn_act_pool_part_kernel<1>), grid, dim3(256), 0, st, y, ldy, coef, N, C, slope, pmax, psum, parg);
+    hipLaunchKernelGGL((bn_act_pool_part_kernel<1>), grid, dim3(256), 0, st, y, ldy, coef, B, N, C, slope, pmax, psum, parg);
   SUG_LAUNCH_CHECK("sug_bn_act_pool_fwd");
   hipLaunchKernelGGL(pool_combine_kernel, dim3(sug_divup((int64_t)B * C, 256)), dim3(256), 0, st, pmax, psum, parg,
                      B, N, C, out_max, out_mean, ld_pool, arg);
@@ -541,9 +546,9 @@ extern "C" int sug_bn_act_pool_bwd(const float* y, int64_t ldy, const float* coe
   const bool vec = vec4_ok(y, ldy, C) && vec4_ok(dy, lddy, C);
   dim3 grid(sug_divup(C, 64), B, NS);
   if (vec)
-    hipLaunchKernelGGL((pool_bwd_reduce_kernel<4>), grid, dim3(256), 0, st, y, ldy, coef, gmax, gmean, ld_pool, arg, N, C, slope, ws);
+    hipLaunchKernelGGL((pool_bwd_reduce_kernel<4>), grid, dim3(256), 0, st, y, ldy, coef, gmax, gmean, ld_pool, arg, B, N, C, slope, ws);
   else
-    hipLaunchKernelGGL((pool_bwd_reduce_kernel<1>), grid, dim3(256), 0, st, y, ldy, coef, gmax, gmean, ld_pool, arg, N, C, slope, ws);
+    hipLaunchKernelGGL((pool_bwd_reduce_kernel<1>), grid, dim3(256), 0, st, y, ldy, coef, gmax, gmean, ld_pool, arg, B, N, C, slope, ws);
   SUG_LAUNCH_CHECK("sug_bn_act_pool_bwd(reduce)");
   hipLaunchKernelGGL(reduce_rows_kernel, dim3(sug_divup(2 * C, 16)), dim3(256), 0, st, ws, B * NS, 2 * C, red);
   SUG_LAUNCH_CHECK("sug_bn_act_pool_bwd(combine)");
@@ -551,7 +556,7 @@ extern "C" int sug_bn_act_pool_bwd(const float* y, int64_t ldy, const float* coe
   if (vec && (C / 4) <= 256 && 256 % (C / 4) == 0 && B <= 65535) {
     const int rpb = 64 > 256 / (C / 4) ? 64 : 256 / (C / 4);
     hipLaunchKernelGGL(pool_bwd_apply_rows_kernel, dim3(sug_divup(N, rpb), B), dim3(256), 0, st, y, ldy, coef, red, gmax,
-                       gmean, ld_pool, arg, N, C, rpb, slope, invM, dy, lddy);
+                       gmean, ld_pool, arg, B, N, C, rpb, slope, invM, dy, lddy, 0);
   } else if (vec)
     hipLaunchKernelGGL((pool_bwd_apply_kernel<4>), dim3(ew_grid((int64_t)B * N * C / 4)), dim3(256), 0, st, y, ldy,
                        coef, red, gmax, gmean, ld_pool, arg, B, N, C, slope, invM, dy, lddy);
@@ -562,6 +567,78 @@ extern "C" int sug_bn_act_pool_bwd(const float* y, int64_t ldy, const float* coe
   return SUG_OK;
 }
 
+// ---- the same two stages for `groups` domain groups of Bg = B / groups clouds, one launch per kernel instead of one
+// per group: the pooling kernels already work cloud by cloud, so a workgroup only has to pick the coefficient set (and
+// the backward sums) of its cloud's group.  Every float operation and its order are those of the per-group launches.
+namespace {
+// reduce_rows_kernel per group (blockIdx.y: its nrow = Bg * NS rows, the same 16 strided partials in the same order) into
+// red [groups][W]; the workgroups of group 0 also form dgb[i] = (float) sum_g red[g][i] (fold_groups_kernel's fp64 sum in
+// group order) from their own re-fold of every group's rows, so no launch has to wait for red
+__global__ __launch_bounds__(256) void reduce_rows_groups_kernel(const float* __restrict__ ws, int nrow, int W, int groups,
+                                                                 double* __restrict__ out, float* __restrict__ dgb) {
+  __shared__ double s_p[16][17];
+  const int cl = threadIdx.x & 15, p = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  const int gfirst = blockIdx.y, glast = (blockIdx.y == 0 && dgb) ? groups : gfirst + 1;
+  double fold = 0.0;
+  for (int g = gfirst; g < glast; ++g) {
+    const float* wg = ws + (size_t)g * nrow * W;
+    double acc = 0.0;
+    if (c < W)
+      for (int b = p; b < nrow; b += 16) acc += (double)wg[(size_t)b * W + c];
+    __syncthreads();
+    s_p[p][cl] = acc;
+    __syncthreads();
+    if (p == 0 && c < W) {
+      double t = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) t += s_p[i][cl];
+      if (g == gfirst) out[(size_t)g * W + c] = t;
+      fold += t;
+    }
+  }
+  if (blockIdx.y == 0 && dgb && p == 0 && c < W) dgb[c] = (float)fold;
+}
+}  // namespace
+
+// 0 = launched, 1 = this layout is not handled here (the caller goes group by group).  ws: 12 * B * C floats
+int sug_bn_act_pool_fwd_groups(const float* y, int64_t ldy, const float* coef, int B, int groups, int N, int C, float slope,
+                               float* out_max, float* out_mean, int64_t ld_pool, int32_t* arg, float* ws, hipStream_t st) {
+  if (!vec4_ok(y, ldy, C) || B > 65535) return 1;
+  const size_t part = (size_t)B * NS * C;
+  float* pmax = ws;
+  float* psum = ws + part;
+  int32_t* parg = reinterpret_cast<int32_t*>(ws + 2 * part);
+  hipLaunchKernelGGL((bn_act_pool_part_kernel<4>), dim3(sug_divup(C, 64), B, NS), dim3(256), 0, st, y, ldy, coef, B / groups, N, C,
+                     slope, pmax, psum, parg);
+  SUG_LAUNCH_CHECK("sug_bn_act_pool_groups_fwd");
+  hipLaunchKernelGGL(pool_combine_kernel, dim3(sug_divup((int64_t)B * C, 256)), dim3(256), 0, st, pmax, psum, parg,
+                     B, N, C, out_max, out_mean, ld_pool, arg);
+  SUG_LAUNCH_CHECK("sug_bn_act_pool_groups_fwd(combine)");
+  return SUG_OK;
+}
+
+// train mode only.  red [groups][2C]; ws: B * NS partial rows of 2C floats (B * NS <= SUG_STATS_BLOCKS); dgb may be null
+int sug_bn_act_pool_bwd_groups(const float* y, int64_t ldy, const float* coef, const float* gmax, const float* gmean,
+                               int64_t ld_pool, const int32_t* arg, int B, int groups, int N, int C, float slope, double* red,
+                               float* ws, float* dy, int64_t lddy, float* dgb, hipStream_t st) {
+  if (!(vec4_ok(y, ldy, C) && vec4_ok(dy, lddy, C) && (C / 4) <= 256 && 256 % (C / 4) == 0 && B <= 65535 &&
+        B * NS <= SUG_STATS_BLOCKS))
+    return 1;
+  const int Bg = B / groups;
+  hipLaunchKernelGGL((pool_bwd_reduce_kernel<4>), dim3(sug_divup(C, 64), B, NS), dim3(256), 0, st, y, ldy, coef, gmax, gmean,
+                     ld_pool, arg, Bg, N, C, slope, ws);
+  SUG_LAUNCH_CHECK("sug_bn_act_pool_groups_bwd(reduce)");
+  hipLaunchKernelGGL(reduce_rows_groups_kernel, dim3(sug_divup(2 * C, 16), groups), dim3(256), 0, st, ws, Bg * NS, 2 * C, groups,
+                     red, dgb);
+  SUG_LAUNCH_CHECK("sug_bn_act_pool_groups_bwd(combine)");
+  const float invM = (float)(1.0 / ((double)Bg * N));
+  const int rpb = 64 > 256 / (C / 4) ? 64 : 256 / (C / 4);
+  hipLaunchKernelGGL(pool_bwd_apply_rows_kernel, dim3(sug_divup(N, rpb), B), dim3(256), 0, st, y, ldy, coef, red, gmax, gmean,
+                     ld_pool, arg, Bg, N, C, rpb, slope, invM, dy, lddy, 1);
+  SUG_LAUNCH_CHECK("sug_bn_act_pool_groups_bwd(apply)");
+  return SUG_OK;
+}
 
 // out[i] = (float) sum_g red[g][i]: the per-domain-group BatchNorm gradient sums (dbeta | dgamma, fp64) of a
 // layer folded into the fp32 parameter gradients, in group order.
@@ -662,13 +739,11 @@ __device__ __forceinline__ float gate_val(float x, float z) {
 // MR: rows kept in registers (M <= MR: one batch of loads, the three passes run on registers -- with a loop over the rows every
 // pass waited for its own loads: 13.6 us for 512 KB); MR = 0: any M, rows re-read per pass.
 template <int MR>
-__global__ __launch_bounds__(64) void gate_bn_fwd_kernel(const float* __restrict__ x, const float* __restrict__ z, int M, int C,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float* __restrict__ rmean, float* __restrict__ rvar, int training,
-                                                         float eps, float momentum, float* __restrict__ out,
-                                                         float* __restrict__ stat) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c >= C) return;
+__device__ __forceinline__ void gate_bn_fwd_body(const int c, const float* __restrict__ x, const float* __restrict__ z, int M, int C,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 float* __restrict__ rmean, float* __restrict__ rvar, int training,
+                                                 float eps, float momentum, float* __restrict__ out,
+                                                 float* __restrict__ stat) {
   float gv[MR > 0 ? MR : 1];
   if constexpr (MR > 0) {
     float xv[MR], zv[MR];
@@ -725,13 +800,44 @@ __global__ __launch_bounds__(64) void gate_bn_fwd_kernel(const float* __restrict
 }
 
 template <int MR>
-__global__ __launch_bounds__(64) void gate_bn_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
-                                                         const float* __restrict__ z, int M, int C,
-                                                         const float* __restrict__ gamma, const float* __restrict__ stat,
-                                                         int training, float* __restrict__ dx, float* __restrict__ dz,
-                                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
+__global__ __launch_bounds__(64) void gate_bn_fwd_kernel(const float* __restrict__ x, const float* __restrict__ z, int M, int C,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         float* __restrict__ rmean, float* __restrict__ rvar, int training,
+                                                         float eps, float momentum, float* __restrict__ out,
+                                                         float* __restrict__ stat) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= C) return;
+  gate_bn_fwd_body<MR>(c, x, z, M, C, gamma, beta, rmean, rvar, training, eps, momentum, out, stat);
+}
+
+// The gate + BatchNorm1d of up to SUG_GATE_BN_MULTI attention layers in one launch (attention_s / attention_t on the two
+// row blocks of a paired batch): blockIdx.y = layer, rows [l*M, (l+1)*M) of x / z / out / g / dx / dz, stat + l*2C, its own
+// parameters and running buffers from the by-value table.  Per layer the body and the lanes of the single-layer kernels.
+#define SUG_GATE_BN_MULTI 4
+struct GateBNMulti {
+  const float* gamma[SUG_GATE_BN_MULTI];
+  const float* beta[SUG_GATE_BN_MULTI];
+  float* rmean[SUG_GATE_BN_MULTI];
+  float* rvar[SUG_GATE_BN_MULTI];
+};
+
+template <int MR>
+__global__ __launch_bounds__(64) void gate_bn_fwd_multi_kernel(const float* __restrict__ x, const float* __restrict__ z, int M, int C,
+                                                               GateBNMulti t, int training, float eps, float momentum,
+                                                               float* __restrict__ out, float* __restrict__ stat) {
+  const int c = blockIdx.x * 64 + threadIdx.x, l = blockIdx.y;
+  if (c >= C) return;
+  const int64_t o = (int64_t)l * M * C;
+  gate_bn_fwd_body<MR>(c, x + o, z + o, M, C, t.gamma[l], t.beta[l], t.rmean[l], t.rvar[l], training, eps, momentum, out + o,
+                       stat + (int64_t)l * 2 * C);
+}
+
+template <int MR>
+__device__ __forceinline__ void gate_bn_bwd_body(const int c, const float* __restrict__ g, const float* __restrict__ x,
+                                                 const float* __restrict__ z, int M, int C,
+                                                 const float* __restrict__ gamma, const float* __restrict__ stat,
+                                                 int training, float* __restrict__ dx, float* __restrict__ dz,
+                                                 float* __restrict__ dgamma, float* __restrict__ dbeta) {
   const float mean = stat[c], invstd = stat[C + c];
   float sb = 0.f, sg = 0.f;
   float xr[MR > 0 ? MR : 1], sr[MR > 0 ? MR : 1], hr[MR > 0 ? MR : 1], gr[MR > 0 ? MR : 1];      // x, sigmoid(z), x_hat, g
@@ -787,6 +893,31 @@ __global__ __launch_bounds__(64) void gate_bn_bwd_kernel(const float* __restrict
   }
 }
 
+template <int MR>
+__global__ __launch_bounds__(64) void gate_bn_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                         const float* __restrict__ z, int M, int C,
+                                                         const float* __restrict__ gamma, const float* __restrict__ stat,
+                                                         int training, float* __restrict__ dx, float* __restrict__ dz,
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  gate_bn_bwd_body<MR>(c, g, x, z, M, C, gamma, stat, training, dx, dz, dgamma, dbeta);
+}
+
+// dgb [layers][2][C] = dgamma | dbeta of each layer
+template <int MR>
+__global__ __launch_bounds__(64) void gate_bn_bwd_multi_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                               const float* __restrict__ z, int M, int C, GateBNMulti t,
+                                                               const float* __restrict__ stat, int training,
+                                                               float* __restrict__ dx, float* __restrict__ dz,
+                                                               float* __restrict__ dgb) {
+  const int c = blockIdx.x * 64 + threadIdx.x, l = blockIdx.y;
+  if (c >= C) return;
+  const int64_t o = (int64_t)l * M * C;
+  gate_bn_bwd_body<MR>(c, g + o, x + o, z + o, M, C, t.gamma[l], stat + (int64_t)l * 2 * C, training, dx + o, dz + o,
+                       dgb + (int64_t)l * 2 * C, dgb + (int64_t)l * 2 * C + C);
+}
+
 }  // namespace
 
 extern "C" int sug_gate_bn_fwd(const float* x, const float* z, int M, int C, const float* gamma, const float* beta,
@@ -818,6 +949,62 @@ extern "C" int sug_gate_bn_bwd(const float* g, const float* x, const float* z, i
     hipLaunchKernelGGL(gate_bn_bwd_kernel<0>, dim3((unsigned)sug_divup(C, 64)), dim3(64), 0, (hipStream_t)stream, g, x, z, M, C,
                        gamma, stat, training, dx, dz, dgamma, dbeta);
   SUG_LAUNCH_CHECK("sug_gate_bn_bwd");
+  return SUG_OK;
+}
+
+extern "C" int sug_gate_bn_fwd_multi(int layers, const float* x, const float* z, int M, int C, const void* const* gamma,
+                                     const void* const* beta, void* const* running_mean, void* const* running_var, int training,
+                                     float eps, float momentum, float* out, float* stat, void* stream) {
+  SUG_REQUIRE(x && z && gamma && beta && out && stat, "sug_gate_bn_fwd_multi: null pointer");
+  SUG_REQUIRE(layers >= 1 && layers <= SUG_GATE_BN_MULTI, "sug_gate_bn_fwd_multi: %d layers (1..%d)", layers, SUG_GATE_BN_MULTI);
+  SUG_REQUIRE(M >= 1 && M <= 1024 && C >= 1, "sug_gate_bn_fwd_multi: bad shape M=%d C=%d", M, C);
+  GateBNMulti t;
+  for (int i = 0; i < SUG_GATE_BN_MULTI; ++i) {
+    const int k = i < layers ? i : 0;
+    float* rm = running_mean ? (float*)running_mean[k] : nullptr;
+    float* rv = running_var ? (float*)running_var[k] : nullptr;
+    SUG_REQUIRE(gamma[k] && beta[k], "sug_gate_bn_fwd_multi: null parameter of layer %d", k);
+    SUG_REQUIRE(training || (rm && rv), "sug_gate_bn_fwd_multi: eval mode needs the running buffers");
+    SUG_REQUIRE(!rm == !rv, "sug_gate_bn_fwd_multi: running_mean and running_var come together");
+    t.gamma[i] = (const float*)gamma[k];
+    t.beta[i] = (const float*)beta[k];
+    t.rmean[i] = rm;
+    t.rvar[i] = rv;
+  }
+  const dim3 grid((unsigned)sug_divup(C, 64), layers);
+  if (M <= 32)
+    hipLaunchKernelGGL(gate_bn_fwd_multi_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, x, z, M, C, t, training, eps, momentum,
+                       out, stat);
+  else
+    hipLaunchKernelGGL(gate_bn_fwd_multi_kernel<0>, grid, dim3(64), 0, (hipStream_t)stream, x, z, M, C, t, training, eps, momentum,
+                       out, stat);
+  SUG_LAUNCH_CHECK("sug_gate_bn_fwd_multi");
+  return SUG_OK;
+}
+
+extern "C" int sug_gate_bn_bwd_multi(int layers, const float* g, const float* x, const float* z, int M, int C,
+                                     const void* const* gamma, const float* stat, int training, float* dx, float* dz, float* dgb,
+                                     void* stream) {
+  SUG_REQUIRE(g && x && z && gamma && stat && dx && dz && dgb, "sug_gate_bn_bwd_multi: null pointer");
+  SUG_REQUIRE(layers >= 1 && layers <= SUG_GATE_BN_MULTI, "sug_gate_bn_bwd_multi: %d layers (1..%d)", layers, SUG_GATE_BN_MULTI);
+  SUG_REQUIRE(M >= 1 && M <= 1024 && C >= 1, "sug_gate_bn_bwd_multi: bad shape M=%d C=%d", M, C);
+  GateBNMulti t;
+  for (int i = 0; i < SUG_GATE_BN_MULTI; ++i) {
+    const int k = i < layers ? i : 0;
+    SUG_REQUIRE(gamma[k], "sug_gate_bn_bwd_multi: null parameter of layer %d", k);
+    t.gamma[i] = (const float*)gamma[k];
+    t.beta[i] = nullptr;
+    t.rmean[i] = nullptr;
+    t.rvar[i] = nullptr;
+  }
+  const dim3 grid((unsigned)sug_divup(C, 64), layers);
+  if (M <= 32)
+    hipLaunchKernelGGL(gate_bn_bwd_multi_kernel<32>, grid, dim3(64), 0, (hipStream_t)stream, g, x, z, M, C, t, stat, training, dx,
+                       dz, dgb);
+  else
+    hipLaunchKernelGGL(gate_bn_bwd_multi_kernel<0>, grid, dim3(64), 0, (hipStream_t)stream, g, x, z, M, C, t, stat, training, dx,
+                       dz, dgb);
+  SUG_LAUNCH_CHECK("sug_gate_bn_bwd_multi");
   return SUG_OK;
 }
 

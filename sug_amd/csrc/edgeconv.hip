@@ -435,6 +435,84 @@ __global__ __launch_bounds__(1024) void stats_finalize_groups_kernel(const float
   }
 }
 
+// stats_finalize_kernel for `groups` domain groups that each own a SUG_STATS_BLOCKS * 2C workspace block (nblk partial
+// rows + the pivot row at SUG_PIVOT_OFFSET): every group's rows are folded in stats_finalize_kernel's own association
+// (16 strided row lanes, then the 16 lane sums in ascending order), so coef and the running buffers carry the bits of
+// `groups` stats_finalize_kernel launches; the running statistics take the groups' updates in group order from the one
+// thread that owns the channel.  blockDim = 256 * GT: the GT = min(groups, SUG_FIN_GT) groups of a pass over the rows
+// are folded side by side, by 256 threads each.
+#define SUG_FIN_GT 4
+__global__ __launch_bounds__(256 * SUG_FIN_GT) void stats_finalize_own_ws_kernel(const float* __restrict__ ws, int nblk, int C,
+                                                                                 int groups, const float* __restrict__ gamma,
+                                                                                 const float* __restrict__ beta, double count,
+                                                                                 float eps, float momentum,
+                                                                                 float* __restrict__ rmean, float* __restrict__ rvar,
+                                                                                 float* __restrict__ coef) {
+  constexpr int UN = 32;
+  __shared__ double s_p[SUG_FIN_GT][16][17];
+  __shared__ double s_tot[SUG_FIN_GT][16];
+  const int GT = blockDim.x >> 8, gl = threadIdx.x >> 8, t = threadIdx.x & 255;
+  const int cl = t & 15, p = t >> 4;
+  const int ch = blockIdx.x * 8 + (cl & 7);                 // cl < 8: sum column, cl >= 8: sum of squares
+  const int col = (cl < 8) ? ch : C + ch;
+  const int W = 2 * C;
+  const size_t gstride = (size_t)SUG_STATS_BLOCKS * W;
+  const bool fin = threadIdx.x < 8 && ch < C;
+  float rm = (fin && rmean) ? rmean[ch] : 0.f, rv = (fin && rvar) ? rvar[ch] : 0.f;
+  for (int g0 = 0; g0 < groups; g0 += GT) {
+    const int ng = groups - g0 < GT ? groups - g0 : GT;
+    double acc = 0.0;
+    if (ch < C && gl < ng) {
+      // UN rows loaded before the first add (row index clamped, so that no load hangs on a branch: one dependent load
+      // per row made this launch 44 us); the adds keep their order, b ascending
+      const float* wg = ws + (size_t)(g0 + gl) * gstride + col;
+      for (int b = p; b < nblk; b += 16 * UN) {
+        float v[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) v[u] = wg[(size_t)(b + 16 * u < nblk ? b + 16 * u : b) * W];
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+          if (b + 16 * u < nblk) acc += (double)v[u];
+      }
+    }
+    __syncthreads();                               // the previous pass has read s_tot
+    s_p[gl][p][cl] = acc;
+    __syncthreads();
+    if (p == 0 && gl < ng) {
+      double tt = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) tt += s_p[gl][i][cl];
+      s_tot[gl][cl] = tt;
+    }
+    __syncthreads();
+    if (fin) {
+      const int c = ch;
+      for (int g = 0; g < ng; ++g) {
+        float* cg = coef + (size_t)(g0 + g) * 5 * C;
+        const float* pivot = ws + (size_t)(g0 + g) * gstride + SUG_PIVOT_OFFSET(C);
+        const double m1 = s_tot[g][threadIdx.x] / count;      // mean of (x - pivot)
+        double var = s_tot[g][8 + threadIdx.x] / count - m1 * m1;
+        if (var < 0) var = 0;
+        const double mean = (double)pivot[c] + m1;
+        const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float scale = gamma[c] * rstd;
+        cg[c] = scale;
+        cg[C + c] = beta[c] - (float)mean * scale;
+        cg[2 * C + c] = (float)mean;
+        cg[3 * C + c] = rstd;
+        const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
+        cg[4 * C + c] = (float)unb;
+        rm = (1.f - momentum) * rm + momentum * (float)mean;
+        rv = (1.f - momentum) * rv + momentum * (float)unb;
+      }
+    }
+  }
+  if (fin) {
+    if (rmean) rmean[ch] = rm;
+    if (rvar) rvar[ch] = rv;
+  }
+}
+
 // The running-statistics update of G more train-mode forwards on batches whose statistics are
 // already known (coef rows 2 and 4), applied in group order with bn_finalize's arithmetic.
 __global__ __launch_bounds__(256) void bn_replay_kernel(const float* __restrict__ coef, int G, int C,
@@ -606,9 +684,12 @@ __global__ __launch_bounds__(256) void col_reduce_vec4_kernel(const float* __res
                                                               int64_t rows, int C, float slope,
                                                               float* __restrict__ a,
                                                               float* __restrict__ ws, int LX,
-                                                              int rows_per_block, int pivoted) {
+                                                              int rows_per_block, int pivoted, int own_ws) {
   extern __shared__ __attribute__((aligned(16))) float s_red[];  // [LY][2*C]
-  float* const ws_pivot = ws + SUG_PIVOT_OFFSET(C) + (size_t)blockIdx.y * C;      // pivot row of this group
+  // own_ws: every group has a whole SUG_STATS_BLOCKS * 2C workspace block (partial rows from its start, its pivot row
+  // at SUG_PIVOT_OFFSET inside it), so that a group may use as many partial rows as a single-group call
+  if (own_ws) ws += (size_t)blockIdx.y * SUG_STATS_BLOCKS * 2 * C;
+  float* const ws_pivot = ws + SUG_PIVOT_OFFSET(C) + (own_ws ? (size_t)0 : (size_t)blockIdx.y * C);      // pivot row of this group
   // blockIdx.y = domain group: `rows` rows each, consecutive in y / z / a; coefficient set g; partial rows
   // [g * gridDim.x + blockIdx.x]
   const int64_t g0 = (int64_t)blockIdx.y * rows;
@@ -618,7 +699,7 @@ __global__ __launch_bounds__(256) void col_reduce_vec4_kernel(const float* __res
     if (MODE == 1) a += g0 * C;
     coef += (int64_t)blockIdx.y * 5 * C;
   }
-  ws += (size_t)blockIdx.y * gridDim.x * 2 * C;
+  if (!own_ws) ws += (size_t)blockIdx.y * gridDim.x * 2 * C;
   const int LY = 256 / LX;
   const int lx = threadIdx.x % LX, ly = threadIdx.x / LX;
   const int C4 = C >> 2;
@@ -1087,7 +1168,8 @@ extern "C" int sug_affine_act(const float* z, int64_t ldz, const float* coef, in
 // Launch the column reduction (vectorised when layout allows); returns the number of partial rows.
 template <int MODE>
 static int launch_col_reduce(const float* y, int64_t ldy, const float* z, const float* coef, int64_t rows,
-                             int C, float slope, float* a, float* ws, hipStream_t st, int groups = 1, int pivoted = 0);
+                             int C, float slope, float* a, float* ws, hipStream_t st, int groups = 1, int pivoted = 0,
+                             int own_ws = 0);
 
 // rows per block such that the grid stays within SUG_STATS_BLOCKS
 static int col_rows_per_block(int64_t rows, int cw) {
@@ -1097,23 +1179,25 @@ static int col_rows_per_block(int64_t rows, int cw) {
 }
 
 // rows = rows per group; groups > 1 (vectorised layout only, else -1): one launch over all groups, partial rows
-// [group][block]; returns the number of partial rows PER GROUP
+// [group][block]; returns the number of partial rows PER GROUP.  own_ws: ws holds one SUG_STATS_BLOCKS * 2C block per
+// group (partial rows + that group's pivot row) and every group is cut into workgroups exactly as a single-group call
+// over its rows would cut it: the partial sums, and with them the statistics, equal those of `groups` separate calls
 template <int MODE>
 static int launch_col_reduce(const float* y, int64_t ldy, const float* z, const float* coef, int64_t rows,
-                             int C, float slope, float* a, float* ws, hipStream_t st, int groups, int pivoted) {
+                             int C, float slope, float* a, float* ws, hipStream_t st, int groups, int pivoted, int own_ws) {
   const bool vec = (C % 4 == 0) && (ldy % 4 == 0) && ((uintptr_t)y % 16 == 0) &&
                    (MODE == 0 || (((uintptr_t)z % 16 == 0) && (MODE == 2 || (uintptr_t)a % 16 == 0) && ((uintptr_t)coef % 16 == 0)));
   if (vec) {
     int lx = 1;
     while (lx < (C >> 2) && lx < 256) lx <<= 1;
     const int ly = 256 / lx;
-    int64_t rpb = (rows * groups + SUG_STATS_ROWS - 1) / SUG_STATS_ROWS;
+    int64_t rpb = (rows * (own_ws ? 1 : groups) + SUG_STATS_ROWS - 1) / SUG_STATS_ROWS;
     if (rpb < 4 * ly) rpb = 4 * ly;
     rpb = (rpb + ly - 1) / ly * ly;
     const int grid = sug_divup(rows, rpb);
-    if ((int64_t)grid * groups > SUG_STATS_ROWS || groups > 16) return -1;
+    if ((int64_t)grid * (own_ws ? 1 : groups) > SUG_STATS_ROWS || groups > 16) return -1;
     hipLaunchKernelGGL((col_reduce_vec4_kernel<MODE>), dim3(grid, groups), dim3(256), (size_t)ly * 2 * C * sizeof(float),
-                       st, y, ldy, z, coef, rows, C, slope, a, ws, lx, (int)rpb, pivoted);
+                       st, y, ldy, z, coef, rows, C, slope, a, ws, lx, (int)rpb, pivoted, own_ws);
     return grid;
   }
   if (groups > 1 || MODE == 2) return -1;
@@ -1164,6 +1248,21 @@ int sug_col_stats_bn_groups(const float* y, int64_t ldy, int64_t rows, int C, in
   hipLaunchKernelGGL(stats_finalize_groups_kernel, dim3(sug_divup(C, 8)), dim3(1024), 0, st, ws, grid, C, groups, gamma, beta,
                      (double)rows, eps, momentum, running_mean, running_var, coef, ws + SUG_PIVOT_OFFSET(C));
   SUG_LAUNCH_CHECK("sug_bn_act_rows_fwd(finalize)");
+  return SUG_OK;
+}
+//   the same with the bits of `groups` sug_col_stats_bn calls, at any size: each group is cut into workgroups as a call
+//   of its own would be and folded in that call's order.  ws: groups * SUG_STATS_BLOCKS * 2C floats (a block per group)
+int sug_col_stats_bn_own_ws(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
+                            const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                            float* coef, float* ws, hipStream_t st) {
+  if (groups < 2) return 1;
+  const int grid = launch_col_reduce<0>(y, ldy, nullptr, nullptr, rows, C, 0.f, nullptr, ws, st, groups, 1, 1);
+  if (grid < 0) return 1;
+  SUG_LAUNCH_CHECK("sug_col_stats_bn_groups_exact(stats)");
+  hipLaunchKernelGGL(stats_finalize_own_ws_kernel, dim3(sug_divup(C, 8)), dim3(256 * (groups < SUG_FIN_GT ? groups : SUG_FIN_GT)), 0,
+                     st, ws, grid, C, groups, gamma, beta,
+                     (double)rows, eps, momentum, running_mean, running_var, coef);
+  SUG_LAUNCH_CHECK("sug_col_stats_bn_groups_exact(finalize)");
   return SUG_OK;
 }
 //   out = act(coef_g . z) with the coefficient set of each row's group

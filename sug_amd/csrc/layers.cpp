@@ -22,6 +22,14 @@ int sug_bwd_reduce_groups(const float* gout, int64_t ldg, const float* z, const 
 int sug_bn_bwd_apply_groups(const float* a, int64_t lda, int from_g, float slope, const float* y, int64_t ldy,
                             const float* coef, const double* red, int64_t rows_g, int groups, int C, float* dy,
                             int64_t lddy, ihipStream_t* st);
+int sug_col_stats_bn_own_ws(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
+                            const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                            float* coef, float* ws, ihipStream_t* st);
+int sug_bn_act_pool_fwd_groups(const float* y, int64_t ldy, const float* coef, int B, int groups, int N, int C, float slope,
+                               float* out_max, float* out_mean, int64_t ld_pool, int32_t* arg, float* ws, ihipStream_t* st);
+int sug_bn_act_pool_bwd_groups(const float* y, int64_t ldy, const float* coef, const float* gmax, const float* gmean,
+                               int64_t ld_pool, const int32_t* arg, int B, int groups, int N, int C, float slope, double* red,
+                               float* ws, float* dy, int64_t lddy, float* dgb, ihipStream_t* st);
 int sug_edgeconv_fwd_bn_act_groups(const float* pq, int64_t ldpq, const int32_t* idx, const float* gamma,
                                    const float* beta, int B, int N, int k, int Co, int groups, float eps, float momentum,
                                    float slope, float* running_mean, float* running_var, float* z, uint8_t* arg,
@@ -214,4 +222,72 @@ extern "C" int sug_bn_act_pool_layer_bwd(const float* y, int64_t ldy, const floa
                                   red + (int64_t)g * 2 * C, ws, dy + g * rg * lddy, lddy, stream));
   if (dgb) LAYER_TRY(sug_fold_groups(red, groups, 2 * C, dgb, stream));
   return SUG_OK;
+}
+
+// ---- the bn5 stage with every domain group in each launch (train mode, 2..16 groups, float4 layout; anything else runs
+// the entry points above): two statistics launches, two pooling launches, three backward launches, whatever `groups` is.
+// Bit for bit what the per-group loops give: each group's statistics are cut into workgroups and folded as a call of
+// its own would (hence the workspace block per group), the pooling kernels take their cloud's coefficient set.
+extern "C" int sug_col_stats_bn_groups_exact(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
+                                             const float* beta, float eps, float momentum, float* running_mean,
+                                             float* running_var, float* coef, float* ws, void* stream) {
+  LAYER_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_col_stats_bn_groups_exact: %lld rows do not split into %d groups",
+                (long long)rows, groups);
+  LAYER_REQUIRE(y && gamma && beta && coef && ws, "sug_col_stats_bn_groups_exact: null pointer");
+  LAYER_REQUIRE(C > 0 && C <= 4096 && ldy >= C, "sug_col_stats_bn_groups_exact: bad shape");
+  const int64_t rg = rows / groups;
+  if (groups > 1 && groups <= 16) {
+    const int rc = sug_col_stats_bn_own_ws(y, ldy, rg, C, groups, gamma, beta, eps, momentum, running_mean, running_var, coef, ws,
+                                           (ihipStream_t*)stream);
+    if (rc <= 0) return rc;
+  }
+  for (int g = 0; g < groups; ++g)
+    LAYER_TRY(sug_col_stats_bn(y + g * rg * ldy, ldy, rg, C, gamma, beta, eps, momentum, running_mean, running_var,
+                               coef + (int64_t)g * 5 * C, ws, stream));
+  return SUG_OK;
+}
+
+extern "C" int sug_bn_act_pool_groups_fwd(const float* y, int64_t ldy, int B, int N, int C, int groups, const float* gamma,
+                                          const float* beta, int training, float eps, float momentum, float slope,
+                                          float* running_mean, float* running_var, float* coef, float* out_max, float* out_mean,
+                                          int64_t ld_pool, int32_t* arg, double* stats, float* ws_stats, float* ws_pool,
+                                          void* stream) {
+  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_groups_fwd: B=%d does not split into %d groups", B, groups);
+  if (training && groups > 1 && groups <= 16) {
+    LAYER_REQUIRE(y && gamma && beta && coef && out_max && out_mean && arg && ws_stats && ws_pool,
+                  "sug_bn_act_pool_groups_fwd: null pointer");
+    LAYER_REQUIRE(N > 0 && C > 0 && C <= 4096 && ldy >= C && ld_pool >= C, "sug_bn_act_pool_groups_fwd: bad shape");
+    ihipStream_t* st = (ihipStream_t*)stream;
+    const int Bg = B / groups;
+    const int64_t rg = (int64_t)Bg * N;
+    int rc = sug_col_stats_bn_own_ws(y, ldy, rg, C, groups, gamma, beta, eps, momentum, running_mean, running_var, coef, ws_stats, st);
+    if (rc < 0) return rc;
+    if (rc == 0) {
+      rc = sug_bn_act_pool_fwd_groups(y, ldy, coef, B, groups, N, C, slope, out_max, out_mean, ld_pool, arg, ws_pool, st);
+      if (rc <= 0) return rc;
+      for (int g = 0; g < groups; ++g)      // statistics done, pooling not launched as one: finish group by group
+        LAYER_TRY(sug_bn_act_pool_fwd(y + g * rg * ldy, ldy, coef + (int64_t)g * 5 * C, Bg, N, C, slope,
+                                      out_max + (int64_t)g * Bg * ld_pool, out_mean + (int64_t)g * Bg * ld_pool, ld_pool,
+                                      arg + (int64_t)g * Bg * C, ws_pool, stream));
+      return SUG_OK;
+    }
+  }
+  return sug_bn_act_pool_layer_fwd(y, ldy, B, N, C, groups, gamma, beta, training, eps, momentum, slope, running_mean, running_var,
+                                   coef, out_max, out_mean, ld_pool, arg, stats, ws_stats, ws_pool, stream);
+}
+
+extern "C" int sug_bn_act_pool_groups_bwd(const float* y, int64_t ldy, const float* coef, const float* gmax, const float* gmean,
+                                          int64_t ld_pool, const int32_t* arg, int B, int N, int C, int groups, float slope,
+                                          int training, double* red, float* ws, float* dy, int64_t lddy, float* dgb,
+                                          void* stream) {
+  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_groups_bwd: B=%d does not split into %d groups", B, groups);
+  if (training && groups > 1 && groups <= 16) {
+    LAYER_REQUIRE(y && coef && gmax && gmean && arg && red && ws && dy, "sug_bn_act_pool_groups_bwd: null pointer");
+    LAYER_REQUIRE(N > 0 && C > 0 && ldy >= C && lddy >= C && ld_pool >= C, "sug_bn_act_pool_groups_bwd: bad shape");
+    const int rc = sug_bn_act_pool_bwd_groups(y, ldy, coef, gmax, gmean, ld_pool, arg, B, groups, N, C, slope, red, ws, dy, lddy,
+                                              dgb, (ihipStream_t*)stream);
+    if (rc <= 0) return rc;
+  }
+  return sug_bn_act_pool_layer_bwd(y, ldy, coef, gmax, gmean, ld_pool, arg, B, N, C, groups, slope, training, red, ws, dy, lddy,
+                                   dgb, stream);
 }

@@ -233,9 +233,9 @@ __global__ void mmd_value_multi_kernel(const double* __restrict__ sums, int n, d
 
 // part[b][blockIdx.x] = sum over this workgroup's points i of min_j |a_i - b_j|^2   (one direction; called twice, then
 // chamfer_fold_kernel adds a cloud's partial sums in block order: no float atomics, the result is reproducible)
-__global__ __launch_bounds__(256) void chamfer_dir_kernel(const float* __restrict__ a,
-                                                          const float* __restrict__ bpts, int N, int M,
-                                                          float* __restrict__ part) {
+// (nb: the direction's workgroups per cloud, the row length of part)
+__device__ __forceinline__ void chamfer_dir_body(const float* __restrict__ a, const float* __restrict__ bpts, int N, int M,
+                                                 float* __restrict__ part, int nb) {
   extern __shared__ __attribute__((aligned(16))) float s_p[];  // M x (x, y, z, pad): one b128 broadcast read per candidate
   const int b = blockIdx.y;                                    // (three b32 reads per candidate made this LDS-issue bound)
   const float* bb = bpts + (int64_t)b * M * 3;
@@ -275,7 +275,28 @@ __global__ __launch_bounds__(256) void chamfer_dir_kernel(const float* __restric
   const float s = wave_sum_f(best);
   if ((threadIdx.x & (WAVE - 1)) == 0) s_w[threadIdx.x / WAVE] = s;
   __syncthreads();
-  if (threadIdx.x == 0) part[(int64_t)b * gridDim.x + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  if (threadIdx.x == 0) part[(int64_t)b * nb + blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+__global__ __launch_bounds__(256) void chamfer_dir_kernel(const float* __restrict__ a,
+                                                          const float* __restrict__ bpts, int N, int M,
+                                                          float* __restrict__ part) {
+  chamfer_dir_body(a, bpts, N, M, part, gridDim.x);
+}
+
+// Both directions in one launch: blockIdx.z = 0 is a -> b into pn [B][nbn], 1 is b -> a (operands swapped) into pm
+// [B][nbm]; gridDim.x = max(nbn, nbm), the shorter direction's surplus workgroups leave at once.  Dynamic LDS: the
+// larger of the two candidate sets.  Every workgroup computes and stores what its chamfer_dir_kernel twin does.
+__global__ __launch_bounds__(256) void chamfer_both_kernel(const float* __restrict__ a, const float* __restrict__ bpts, int N,
+                                                           int M, int nbn, int nbm, float* __restrict__ pn,
+                                                           float* __restrict__ pm) {
+  if (blockIdx.z == 0) {
+    if ((int)blockIdx.x >= nbn) return;
+    chamfer_dir_body(a, bpts, N, M, pn, nbn);
+  } else {
+    if ((int)blockIdx.x >= nbm) return;
+    chamfer_dir_body(bpts, a, M, N, pm, nbm);
+  }
 }
 
 // out[b] = (sum of the nbn partial sums of direction a -> b) / N + (sum of the nbm partial sums of b -> a) / M, block order
@@ -637,6 +658,21 @@ extern "C" int sug_chamfer(const float* a, const float* b, int B, int N, int M, 
   return SUG_OK;
 }
 
+extern "C" int sug_chamfer_merged(const float* a, const float* b, int B, int N, int M, float* out, float* ws, void* stream) {
+  SUG_REQUIRE(a && b && out && ws, "sug_chamfer_merged: null pointer");
+  SUG_REQUIRE(B > 0 && N > 0 && M > 0 && N <= 5000 && M <= 5000 && B <= 65535, "sug_chamfer_merged: bad shape");
+  hipStream_t st = (hipStream_t)stream;
+  const int nbn = sug_divup(4 * N, 256), nbm = sug_divup(4 * M, 256);
+  float* pm = ws + (int64_t)B * nbn;
+  hipLaunchKernelGGL(chamfer_both_kernel, dim3(nbn > nbm ? nbn : nbm, B, 2), dim3(256), (size_t)(N > M ? N : M) * 4 * sizeof(float),
+                     st, a, b, N, M, nbn, nbm, ws, pm);
+  SUG_LAUNCH_CHECK("sug_chamfer_merged(directions)");
+  hipLaunchKernelGGL(chamfer_fold_kernel, dim3(sug_divup(B, 256)), dim3(256), 0, st, ws, nbn, pm, nbm, B, 1.0f / (float)N,
+                     1.0f / (float)M, out);
+  SUG_LAUNCH_CHECK("sug_chamfer_merged");
+  return SUG_OK;
+}
+
 extern "C" int sug_mmd_rbf_rows_bwd(const float* z, int64_t ldz, const float* wt, int m, int D, int row0, int mloc,
                                     const float* gscale, float gmul, float* dz, int64_t lddz, void* stream) {
   SUG_REQUIRE(z && wt && gscale && dz, "sug_mmd_rbf_bwd: null pointer");
@@ -886,6 +922,24 @@ extern "C" int sug_chamfer_weights(const float* a, const float* b, int B, int N,
   hipLaunchKernelGGL(chamfer_fold_weights_kernel, dim3(1), dim3(256), 0, st, ws, nbn, pm, nbm, B, 1.0f / (float)N,
                      1.0f / (float)M, method, out);
   SUG_LAUNCH_CHECK("sug_chamfer_weights");
+  return SUG_OK;
+}
+
+extern "C" int sug_chamfer_weights_merged(const float* a, const float* b, int B, int N, int M, int method, float* out,
+                                          float* ws, void* stream) {
+  SUG_REQUIRE(a && b && out && ws, "sug_chamfer_weights_merged: null pointer");
+  SUG_REQUIRE(B > 0 && N > 0 && M > 0 && N <= 5000 && M <= 5000 && B <= 65535, "sug_chamfer_weights_merged: bad shape");
+  SUG_REQUIRE(method >= 1 && method <= 3, "sug_chamfer_weights_merged: weighting method %d (1 naive_inverse, 2 exp_inverse, 3 mean2one)",
+              method);
+  hipStream_t st = (hipStream_t)stream;
+  const int nbn = sug_divup(4 * N, 256), nbm = sug_divup(4 * M, 256);
+  float* pm = ws + (int64_t)B * nbn;
+  hipLaunchKernelGGL(chamfer_both_kernel, dim3(nbn > nbm ? nbn : nbm, B, 2), dim3(256), (size_t)(N > M ? N : M) * 4 * sizeof(float),
+                     st, a, b, N, M, nbn, nbm, ws, pm);
+  SUG_LAUNCH_CHECK("sug_chamfer_weights_merged(directions)");
+  hipLaunchKernelGGL(chamfer_fold_weights_kernel, dim3(1), dim3(256), 0, st, ws, nbn, pm, nbm, B, 1.0f / (float)N,
+                     1.0f / (float)M, method, out);
+  SUG_LAUNCH_CHECK("sug_chamfer_weights_merged");
   return SUG_OK;
 }
 

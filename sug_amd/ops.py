@@ -1380,6 +1380,11 @@ def bn_act_rows(y, bn, slope, pre=None):
     return out
 
 
+# A/B knob: 0 = the bn5 stage (statistics, pooling, its backward, bn_update_stats) launches once per domain group; 1 = every
+# group in each launch (sug_bn_act_pool_groups_* / sug_col_stats_bn_groups_exact), bit for bit the same results
+BN_POOL_GROUPED = _os.environ.get('SUG_BN_POOL_GROUPED', '1') != '0'
+
+
 class _BNActPool(torch.autograd.Function):
     """y [B,N,C] -> (max_n, mean_n) of LeakyReLU(slope)(BatchNorm(y)); one read of y forward,
     two backward (sug_bn_act_pool_*)."""
@@ -1396,20 +1401,25 @@ class _BNActPool(torch.autograd.Function):
         omax, omean = pooled[:, :C], pooled[:, C:]
         arg = torch.empty(B, C, dtype=torch.int32, device=dev)
         stats = torch.empty(2 * C, dtype=torch.float64, device=dev)
-        wss = _stats_ws(C, dev)
-        wsp = torch.empty(12 * (B // G) * C, dtype=torch.float32, device=dev)
-        check(lib().sug_bn_act_pool_layer_fwd(_p(y), ld, B, N, C, G, _p(g), _p(b), st.train, st.eps, st.momentum,
-                                              float(slope), _p(st.mean), _p(st.var), _p(coef), _p(omax),
-                                              _p(omean), 2 * C, _p(arg), _p(stats), _p(wss), _p(wsp), _st()),
-              'sug_bn_act_pool_layer_fwd')
+        grouped = BN_POOL_GROUPED and G > 1
+        if grouped:                       # a statistics workspace block per group, pooling partials of all B clouds
+            wss = torch.empty(G * STATS_BLOCKS * 2 * C, dtype=torch.float32, device=dev)
+            wsp = torch.empty(12 * B * C, dtype=torch.float32, device=dev)
+            fwd, name = lib().sug_bn_act_pool_groups_fwd, 'sug_bn_act_pool_groups_fwd'
+        else:
+            wss = _stats_ws(C, dev)
+            wsp = torch.empty(12 * (B // G) * C, dtype=torch.float32, device=dev)
+            fwd, name = lib().sug_bn_act_pool_layer_fwd, 'sug_bn_act_pool_layer_fwd'
+        check(fwd(_p(y), ld, B, N, C, G, _p(g), _p(b), st.train, st.eps, st.momentum, float(slope), _p(st.mean), _p(st.var),
+                  _p(coef), _p(omax), _p(omean), 2 * C, _p(arg), _p(stats), _p(wss), _p(wsp), _st()), name)
         ctx.save_for_backward(y, coef, arg)
-        ctx.meta = (B, N, C, ld, float(slope), st.train, G)
+        ctx.meta = (B, N, C, ld, float(slope), st.train, G, grouped)
         return pooled
 
     @staticmethod
     def backward(ctx, g):
         y, coef, arg = ctx.saved_tensors
-        B, N, C, ld, slope, train, G = ctx.meta
+        B, N, C, ld, slope, train, G, grouped = ctx.meta
         dev = y.device
         if g.stride(1) != 1 or g.stride(0) < 2 * C:
             g = g.contiguous()
@@ -1418,9 +1428,10 @@ class _BNActPool(torch.autograd.Function):
         ws = _stats_ws(C, dev)
         dy = torch.empty(B, N, C, dtype=torch.float32, device=dev)
         rf = torch.empty(2 * C, dtype=torch.float32, device=dev)
-        check(lib().sug_bn_act_pool_layer_bwd(_p(y), ld, _p(coef), _p(gmax), _p(gmean), ldp, _p(arg), B, N, C, G, slope,
-                                              train, _p(red), _p(ws), _p(dy), C, _p(rf), _st()),
-              'sug_bn_act_pool_layer_bwd')
+        bwd, name = (lib().sug_bn_act_pool_groups_bwd, 'sug_bn_act_pool_groups_bwd') if grouped else \
+            (lib().sug_bn_act_pool_layer_bwd, 'sug_bn_act_pool_layer_bwd')
+        check(bwd(_p(y), ld, _p(coef), _p(gmax), _p(gmean), ldp, _p(arg), B, N, C, G, slope, train, _p(red), _p(ws), _p(dy), C,
+                  _p(rf), _st()), name)
         return (dy,) + _dgamma_dbeta(rf) + (None, None)
 
 
@@ -1439,6 +1450,14 @@ def bn_update_stats(y, bn):
     _check_groups('bn_update_stats', rows, 'rows', G)
     rg = rows // G
     g, b = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
+    if BN_POOL_GROUPED and G > 1:           # every group in one launch pair, the bits of the loop below
+        coef = torch.empty(G, 5, C, dtype=torch.float32, device=y.device)
+        ws = torch.empty(G * STATS_BLOCKS * 2 * C, dtype=torch.float32, device=y.device)
+        check(lib().sug_col_stats_bn_groups_exact(_p(y2), y2.stride(0), rows, C, G, _p(g), _p(b), bn.eps, bn.momentum,
+                                                  _p(bn.running_mean), _p(bn.running_var), _p(coef), _p(ws), _st()),
+              'sug_col_stats_bn_groups_exact')
+        _count_bn_call(bn)
+        return
     coef = torch.empty(5, C, dtype=torch.float32, device=y.device)
     ws = _stats_ws(C, y.device)
     for i in range(G):
@@ -2182,6 +2201,7 @@ def ptran_attention(xyz, nbr, q, kf, vf, fc_delta, fc_gamma, dtype=None):
 
 # ----------------------------------------------------------------------------- channel attention (CALayer)
 CALAYER_FUSED = _os.environ.get('SUG_CALAYER_FUSED', '1') != '0'    # A/B knob: 0 = library GEMMs + relu + gate_bn per layer
+GATE_BN_MULTI = _os.environ.get('SUG_GATE_BN_MULTI', '1') != '0'    # A/B knob: 0 = one sug_gate_bn_fwd / _bwd launch per layer
 
 
 def calayer_supported(layers, x):
@@ -2227,17 +2247,22 @@ class _CALayers(torch.autograd.Function):
         out = torch.empty(nl * M, C, dtype=torch.float32, device=dev)
         stat = torch.empty(nl, 2, C, dtype=torch.float32, device=dev)
         xc = x if x.stride(0) == C else x.contiguous()            # (sug_gate_bn_* take dense rows)
-        for a in range(nl):
+        multi = GATE_BN_MULTI and 1 < nl <= 4
+        if multi:                         # both layers' gate + BatchNorm in one launch
+            check(L.sug_gate_bn_fwd_multi(nl, _p(xc), _p(z), M, C, _ptrs(gam), _ptrs(bet), _ptrs([p[6] for p in P]),
+                                          _ptrs([p[7] for p in P]), 1 if training else 0, float(eps), float(momentum), _p(out),
+                                          _p(stat), _st()), 'sug_gate_bn_fwd_multi')
+        for a in range(0 if multi else nl):
             check(L.sug_gate_bn_fwd(_p(xc[a * M:]), _p(z[a * M:]), M, C, _p(gam[a]), _p(bet[a]), _p(P[a][6]), _p(P[a][7]),
                                     1 if training else 0, float(eps), float(momentum), _p(out[a * M:]), _p(stat[a]), _st()),
                   'sug_gate_bn_fwd')
         ctx.save_for_backward(xc, h, z, stat, *W0, *W2, *gam)
-        ctx.meta = (nl, M, C, Hd, bool(training))
+        ctx.meta = (nl, M, C, Hd, bool(training), multi)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        nl, M, C, Hd, training = ctx.meta
+        nl, M, C, Hd, training, multi = ctx.meta
         sv = ctx.saved_tensors
         x, h, z, stat = sv[:4]
         W0, W2, gam = sv[4:4 + nl], sv[4 + nl:4 + 2 * nl], sv[4 + 2 * nl:4 + 3 * nl]
@@ -2246,7 +2271,10 @@ class _CALayers(torch.autograd.Function):
         g = g.contiguous()
         dxg, dz = torch.empty_like(x), torch.empty_like(x)
         dgb = torch.empty(nl, 2, C, dtype=torch.float32, device=dev)
-        for a in range(nl):
+        if multi:
+            check(L.sug_gate_bn_bwd_multi(nl, _p(g), _p(x), _p(z), M, C, _ptrs(gam), _p(stat), 1 if training else 0, _p(dxg), _p(dz),
+                                          _p(dgb), _st()), 'sug_gate_bn_bwd_multi')
+        for a in range(0 if multi else nl):
             check(L.sug_gate_bn_bwd(_p(g[a * M:]), _p(x[a * M:]), _p(z[a * M:]), M, C, _p(gam[a]), _p(stat[a]), 1 if training else 0,
                                     _p(dxg[a * M:]), _p(dz[a * M:]), _p(dgb[a, 0]), _p(dgb[a, 1]), _st()), 'sug_gate_bn_bwd')
         f32 = torch.float32
@@ -3630,6 +3658,9 @@ def sda_prob_weights_multi(preds, label_s, label_t, label_weight, method):
     return outs
 
 
+CHAMFER_MERGED = _os.environ.get('SUG_CHAMFER_MERGED', '1') != '0'  # A/B knob: 0 = one launch per direction (a -> b, b -> a)
+
+
 def chamfer(a, b):
     """a [B,N,3], b [B,M,3] -> [B]: mean_i min_j d + mean_j min_i d."""
     _need_gpu(a, b)
@@ -3638,7 +3669,8 @@ def chamfer(a, b):
     M = b.shape[1]
     out = torch.empty(B, dtype=torch.float32, device=a.device)
     ws = torch.empty(lib().sug_chamfer_workspace(B, N, M), dtype=torch.float32, device=a.device)
-    check(lib().sug_chamfer(_p(a), _p(b), B, N, M, _p(out), _p(ws), _st()), 'sug_chamfer')
+    fn, name = (lib().sug_chamfer_merged, 'sug_chamfer_merged') if CHAMFER_MERGED else (lib().sug_chamfer, 'sug_chamfer')
+    check(fn(_p(a), _p(b), B, N, M, _p(out), _p(ws), _st()), name)
     return out
 
 
@@ -3653,7 +3685,9 @@ def chamfer_weights(a, b, method):
     M = b.shape[1]
     out = torch.empty(B, dtype=torch.float32, device=a.device)
     ws = torch.empty(lib().sug_chamfer_workspace(B, N, M), dtype=torch.float32, device=a.device)
-    check(lib().sug_chamfer_weights(_p(a), _p(b), B, N, M, _SDA_METHODS[method], _p(out), _p(ws), _st()), 'sug_chamfer_weights')
+    fn, name = (lib().sug_chamfer_weights_merged, 'sug_chamfer_weights_merged') if CHAMFER_MERGED else \
+        (lib().sug_chamfer_weights, 'sug_chamfer_weights')
+    check(fn(_p(a), _p(b), B, N, M, _SDA_METHODS[method], _p(out), _p(ws), _st()), name)
     return out
 
 
