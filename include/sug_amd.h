@@ -1257,6 +1257,52 @@ int sug_icp_fitness(const float* src, int64_t src_batch_stride, const float* tgt
                     double max_corr_dist, int max_iteration, double rel_fitness, double rel_rmse, int32_t* count,
                     double* rmse, int32_t* iters, double* transform, void* stream);
 
+/* ---- Point Feature Histograms and the histogram cloud distance (utils/pfh.py: PFH.calc_normals :270-301, PFH.calcHistArray
+ * :303-348, pfh_hist_distance :146-159) --------------------------------------------------------------------------------------
+ * sug_pfh_descriptors: M clouds pts [M, N, 3] fp32 in one launch, one workgroup per cloud -> hist [M, N, div^3] fp64,
+ * normals [M, N, 3] fp64, nbr_idx [M, N, k] int32 (padded with -1), nbr_cnt [M, N] int32, used_cnt [M] int32, with
+ * k = nneighbors.  All arithmetic is fp64 on the fp32 coordinates converted once (the reference works in double and the bin
+ * decisions are thresholds), without fma; every sum in one fixed order, no atomics: bit-identical from run to run, and a
+ * cloud's result does not depend on the batch it is launched in.
+ *   neighbours (getNeighbors :253-268): the candidates of point i are all j, j = i included, with
+ *     sqrt((dx*dx + dy*dy) + dz*dz) <= rad on direct differences; ordered by (distance, index); the FIRST of that order is
+ *     dropped -- normally i itself; with an exact duplicate of lower index it is the duplicate, and i stays its own
+ *     neighbour, as in the reference -- and the next k are the neighbours, in that order.  A point left without a neighbour
+ *     is UNUSED.
+ *   normal (:289-299): the covariance of the neighbours only (not the point), centred on their mean, divided by their
+ *     count; the eigenvector of its smallest eigenvalue by a cyclic Jacobi iteration (at most 12 sweeps; equal eigenvalues
+ *     -> the lowest column); negated when normal . (-p_i) < 0.  With fewer than three non-collinear neighbours the null space
+ *     is more than a line: the reference returns whatever LAPACK leaves there, here the result is deterministic, finite and
+ *     of unit length, but not pinned to anything.
+ *   histogram (:303-348): p_list = [i] + neighbours; for every unordered pair (z before p in the list), with
+ *     a = n_p . (p_z - p_p) and b = n_z . (p_p - p_z), p is the source iff arccos(a) <= arccos(b), i.e. iff |a| <= 1 and
+ *     |b| <= 1 and a >= b (a NaN from |.| > 1 makes the comparison false); u = n_s, d = (p_t - p_s) / |p_t - p_s|,
+ *     v = d x u, w = u x v, alpha = v . n_t, phi = u . d, theta = atan((w . n_t) / (u . n_t)); dot products as
+ *     (x*x' + y*y') + z*z'.  IEEE semantics throughout: a zero distance gives NaN features, a division by zero +-pi/2.
+ *     bin = step(alpha) + div * step(phi) + div^2 * step(theta), step(f) = the number of thresholds <= f with the
+ *     thresholds -1 + i * (2 / div) for alpha and phi and -pi/2 + i * (pi / div) for theta, i = 1 .. div - 1 (:441-495);
+ *     a NaN compares false everywhere and lands in the last bin.  row = counts / comb(k + 1, 2) with the CONFIGURED k, not
+ *     the found count (:311), one correctly rounded fp64 division: bit-identical to numpy's.
+ *   unused points: the reference means to drop them (pc_[used_idx]) while its neighbour indices still refer to the full
+ *     cloud, so a cloud with an isolated point raises there or is "skipped".  Here an unused point has a zero histogram row,
+ *     nbr_cnt 0 and a zero normal and takes no part in distances; no other point can have it as a neighbour, so the rest of
+ *     the cloud is unaffected.  used_cnt[m] == N marks the clouds the reference itself can process.
+ * sug_pfh_hist_distance: B (source, target) pairs in one launch, one workgroup per pair.  histS [B or 1, Ns, D] fp64 and
+ * cntS [B or 1, Ns] int32 (the nbr_cnt above: a row is used iff its count is > 0) with src_batch_stride in doubles: 0 = one
+ * source for all pairs (the splitter's anchor), else Ns*D; histT [B, Nt, D], cntT [B, Nt] -> out [B] fp64: over the used rows
+ * i of S the minimum over the used rows j of T of sqrt(sum_d (hS_i[d] - hT_j[d])^2) (d ascending), then np.median of those
+ * minima (an even count: the mean of the two middle values); NaN when either side has no used row.  Finite histograms
+ * are assumed.
+ * Checked on the host before the launch: no null pointer, M, B >= 1, 1 <= N, Ns, Nt <= SUG_PFH_MAX_POINTS,
+ * 1 <= nneighbors <= SUG_PFH_MAX_NEIGHBORS, 2 <= div <= 5 (D one of 8, 27, 64, 125), rad positive and finite,
+ * src_batch_stride 0 or Ns*D. */
+#define SUG_PFH_MAX_POINTS 1024
+#define SUG_PFH_MAX_NEIGHBORS 16
+int sug_pfh_descriptors(const float* pts, int M, int N, double rad, int nneighbors, int div, double* hist, double* normals,
+                        int32_t* nbr_idx, int32_t* nbr_cnt, int32_t* used_cnt, void* stream);
+int sug_pfh_hist_distance(const double* histS, const int32_t* cntS, int64_t src_batch_stride, const double* histT,
+                          const int32_t* cntT, int B, int Ns, int Nt, int D, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

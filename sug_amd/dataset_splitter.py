@@ -22,6 +22,7 @@ from .model.mmd import cal_probs2entropy
 
 MAX_TRIES = 5                    # anchor draws per class (dataset_splitter.py:76)
 MAX_CORR_DIST = 0.15             # icp_distance's max_correspondence_distance (:230)
+PFH_DIV, PFH_NNEIGHBORS, PFH_RAD = 2, 8, 0.2     # metric='pfh': get_pfh_descriptor's PFH(0.1, 2, 8, 0.2) (utils/pfh.py:117)
 
 GeometricSplit = collections.namedtuple('GeometricSplit', 'indices cluster_labels distances anchors tries')
 GeometricSplit.__doc__ = """Per class (lists of num_class entries): `indices` int64 [n] = the class's clouds in the order of
@@ -92,13 +93,31 @@ def _split_class(n, distance_of, draw, use_hist=False, what='class'):
     return labels, d, anchor, tries
 
 
+def _pfh_distance_of(processed):
+    """metric='pfh': the descriptors of a class's processed clouds, computed once -> distance_of(anchor), ONE
+    sug_pfh_hist_distance launch of the anchor's histograms against all of them (utils/pfh.py's pfh_hist_distance)."""
+    hist, _, _, cnt, _ = ops.pfh_descriptors(processed, PFH_RAD, PFH_NNEIGHBORS, PFH_DIV)
+
+    def distance_of(anchor):
+        d = ops.pfh_hist_distance(hist[anchor], cnt[anchor], hist, cnt).cpu().numpy()
+        if np.isnan(d).any():
+            raise ValueError('split_dataset_geometric: metric=\'pfh\': cloud(s) %s of the class have no point with a neighbour '
+                             'inside %g, so no histogram distance' % (np.flatnonzero(np.isnan(d)).tolist()[:8], PFH_RAD))
+        return d
+    return distance_of
+
+
 def split_dataset_geometric(pts, labels, cluster_num=2, use_hist=False, num_class=10, generator=None, anchors=None,
-                            pt_num=500):
+                            pt_num=500, metric='icp'):
     """split_dataset_geometric of dataset_splitter.py:32-84 on a resident dataset: pts [M, P, 3] device tensor, labels [M]
     (host or device).  Per class: stable sort by the smallest raw x, process_pts, an anchor drawn from
     arange(n // 4, n // 2) of that order with `generator` (a numpy.random.Generator; default: a fresh default_rng()) or
     taken from anchors[cls] (up to five positions, used in order), the distances of all clouds to it in one launch, and the
-    cut of _geometric_labels().  One host read of the n distances per try.  -> GeometricSplit."""
+    cut of _geometric_labels().  One host read of the n distances per try.  metric: 'icp' (the reference's, 1 - fitness) or
+    'pfh' (the histogram distance of utils/pfh.py between the anchor's and every cloud's Point Feature Histograms, the
+    descriptors computed once per class).  -> GeometricSplit."""
+    if metric not in ('icp', 'pfh'):
+        raise ValueError('split_dataset_geometric: metric=%r: \'icp\' or \'pfh\'' % (metric,))
     if cluster_num != 2:
         raise ValueError('Geometric Split Only Support 2 clusters (cluster_num=%r)' % (cluster_num,))
     lab = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).reshape(-1)
@@ -130,8 +149,9 @@ def split_dataset_geometric(pts, labels, cluster_num=2, use_hist=False, num_clas
             except StopIteration:
                 raise ValueError('split_dataset_geometric: anchors[%d] ran out before a try was accepted' % cls) from None
 
-        labels_c, d, anchor, tries = _split_class(n, lambda a: icp_distance(processed[a], processed).cpu().numpy(), draw,
-                                                 use_hist, 'class %d' % cls)
+        distance_of = (_pfh_distance_of(processed) if metric == 'pfh'
+                       else lambda a: icp_distance(processed[a], processed).cpu().numpy())
+        labels_c, d, anchor, tries = _split_class(n, distance_of, draw, use_hist, 'class %d' % cls)
         out.indices.append(members.index_select(0, order))
         out.cluster_labels.append(torch.as_tensor(labels_c).to(x.device))
         out.distances.append(torch.as_tensor(d).to(x.device))

@@ -4212,6 +4212,66 @@ def icp_fitness(src, tgt, max_corr_dist=0.15, max_iteration=30, rel_fitness=1e-6
     return count, rmse, iters, transform
 
 
+PFH_MAX_POINTS = _H['SUG_PFH_MAX_POINTS']
+PFH_MAX_NEIGHBORS = _H['SUG_PFH_MAX_NEIGHBORS']
+
+
+def pfh_descriptors(pts, rad=0.2, nneighbors=8, div=2):
+    """Point Feature Histograms of M clouds in one launch (sug_pfh_descriptors; PFH.calc_normals and PFH.calcHistArray of
+    utils/pfh.py, restated in include/sug_amd.h): pts [M, N, 3] fp32 -> (hist fp64 [M, N, div^3], normals fp64 [M, N, 3],
+    nbr_idx int32 [M, N, k] padded with -1, nbr_cnt int32 [M, N], used_cnt int32 [M]).  A point without a neighbour inside
+    `rad` is unused: a zero row, nbr_cnt 0.  No host synchronisation."""
+    _need_gpu(pts)
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise ValueError('pfh_descriptors: pts must be [M, N, 3], got %s' % (tuple(pts.shape),))
+    if pts.dtype != torch.float32:
+        raise ValueError('pfh_descriptors: fp32 clouds only, got %s' % pts.dtype)
+    M, N, _ = pts.shape
+    k, div = int(nneighbors), int(div)
+    if not 1 <= k <= PFH_MAX_NEIGHBORS or not 2 <= div <= 5:
+        raise ValueError('pfh_descriptors: nneighbors=%d outside 1 .. %d or div=%d outside 2 .. 5' % (k, PFH_MAX_NEIGHBORS, div))
+    pts = pts.detach().contiguous()
+    dev = pts.device
+    hist = torch.empty(M, N, div ** 3, dtype=torch.float64, device=dev)
+    normals = torch.empty(M, N, 3, dtype=torch.float64, device=dev)
+    nbr_idx = torch.empty(M, N, k, dtype=torch.int32, device=dev)
+    nbr_cnt = torch.empty(M, N, dtype=torch.int32, device=dev)
+    used_cnt = torch.empty(M, dtype=torch.int32, device=dev)
+    check(_timed('pfh_descriptors', {'M': M, 'N': N, 'k': k, 'div': div},
+                 lambda: lib().sug_pfh_descriptors(_p(pts), M, N, float(rad), k, div, _p(hist), _p(normals), _p(nbr_idx),
+                                                   _p(nbr_cnt), _p(used_cnt), _st())), 'sug_pfh_descriptors')
+    return hist, normals, nbr_idx, nbr_cnt, used_cnt
+
+
+def pfh_hist_distance(histS, cntS, histT, cntT):
+    """pfh_hist_distance of utils/pfh.py:146-159 for B (source, target) descriptor sets in one launch
+    (sug_pfh_hist_distance): histS [Ns, D] with cntS [Ns] (one source for every pair) or [B, Ns, D] with [B, Ns]; histT
+    [B, Nt, D], cntT [B, Nt]; fp64 histograms, int32 neighbour counts (a row is used iff its count is > 0) -> fp64 [B]: the
+    median over the used source rows of the distance to the nearest used target row, NaN when either side has none.  No
+    host synchronisation."""
+    _need_gpu(histS, cntS, histT, cntT)
+    if histT.dim() != 3 or histS.dim() not in (2, 3) or histS.shape[-1] != histT.shape[-1]:
+        raise ValueError('pfh_hist_distance: histS must be [Ns, D] or [B, Ns, D] and histT [B, Nt, D], got %s and %s'
+                         % (tuple(histS.shape), tuple(histT.shape)))
+    if tuple(cntS.shape) != tuple(histS.shape[:-1]) or tuple(cntT.shape) != tuple(histT.shape[:-1]):
+        raise ValueError('pfh_hist_distance: counts %s and %s do not match the histograms %s and %s'
+                         % (tuple(cntS.shape), tuple(cntT.shape), tuple(histS.shape), tuple(histT.shape)))
+    if histS.dtype != torch.float64 or histT.dtype != torch.float64 or cntS.dtype != torch.int32 or cntT.dtype != torch.int32:
+        raise ValueError('pfh_hist_distance: fp64 histograms and int32 counts only, got %s, %s, %s, %s'
+                         % (histS.dtype, histT.dtype, cntS.dtype, cntT.dtype))
+    B, Nt, D = histT.shape
+    if histS.dim() == 3 and histS.shape[0] != B:
+        raise ValueError('pfh_hist_distance: %d sources for %d targets' % (histS.shape[0], B))
+    histS, cntS, histT, cntT = (x.detach().contiguous() for x in (histS, cntS, histT, cntT))
+    Ns = histS.shape[-2]
+    stride = 0 if histS.dim() == 2 else Ns * D
+    out = torch.empty(B, dtype=torch.float64, device=histT.device)
+    check(_timed('pfh_hist_distance', {'B': B, 'Ns': Ns, 'Nt': Nt, 'D': D},
+                 lambda: lib().sug_pfh_hist_distance(_p(histS), _p(cntS), stride, _p(histT), _p(cntT), B, Ns, Nt, D, _p(out),
+                                                     _st())), 'sug_pfh_hist_distance')
+    return out
+
+
 def _ctx_property(field):
     return property(lambda self: getattr(CTX, field), lambda self, v: setattr(CTX, field, v))
 
