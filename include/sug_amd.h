@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added).  A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -1040,6 +1040,62 @@ int sug_loss_combine_bwd(const float* g, float wg, float ws, float* out4, void* 
 int sug_eval_accumulate(const float* logits1, const float* logits2, int64_t ld, const int64_t* label, int B, int C,
                         const float* loss_in, int ce_mode, int64_t ignore_index, float label_smoothing, float* out,
                         int64_t* pred, int cls_eval, void* state, int cap, void* stream);
+
+/* ---- dense prediction: per-point cross entropy and the part-IoU books (csrc/seg.hip) ------------------------------
+ * F.cross_entropy(logits [M, C], label [M], weight=class_weight, ignore_index, reduction='mean') of a segmentation batch's
+ * rows: loss[0] = sum_r w[y_r] * (lse_r - z_r[y_r]) / sum_r w[y_r] over the counting rows (class_weight: device fp32 [C],
+ * null = all ones).  logits fp32 with any row stride ld >= C, label int64.  Labels as sug_ce_fwd takes them: a row labelled
+ * ignore_index contributes nothing; any other label outside [0, C) makes the loss NaN and that row's gradient NaN: no row is
+ * ever scored as some class; no counting row: NaN, as torch.  lse [2M + 1], kept for the backward: the rows' maxima, then the
+ * rows' log sum_c exp(z_c - max) (the log-sum-exp as two floats: their fp32 sum would round away, at the logits' size, the
+ * digits that are the whole loss and gradient of a confidently right row), then lse[2M] = the denominator.  pred [M] (int32, may be null): the arg-max of every row, ignored ones included, the lowest
+ * index on ties.  Two launches: workgroups of SUG_POINT_CE_BLOCK_ROWS rows each write ONE partial of
+ * SUG_POINT_CE_PARTIAL_WORDS doubles (weighted loss sum, weight sum, counting rows; the rows' fp32 terms summed in fp64 in a
+ * fixed order) into workspace -- sug_point_ce_workspace(M) doubles, or -1 --, then one workgroup adds the partials in block
+ * order and writes loss (fp32) and lse[2M].  totals (device double[2], may be null) is advanced by the fold:
+ * totals[0] += (double)loss * counting rows, totals[1] += counting rows.  1 <= M <= SUG_POINT_CE_MAX_ROWS,
+ * 2 <= C <= SUG_POINT_CE_MAX_CLASSES, checked on the host before any launch (-1, sug_last_error()).  No float atomics, no
+ * memset node: capturable, bit-reproducible. */
+#define SUG_POINT_CE_MAX_ROWS 4194304
+#define SUG_POINT_CE_MAX_CLASSES 64
+#define SUG_POINT_CE_BLOCK_ROWS 128
+#define SUG_POINT_CE_PARTIAL_WORDS 3
+int sug_point_ce_workspace(int M);
+int sug_point_ce_fwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index,
+                     const float* class_weight, float* loss, float* lse, int32_t* pred, double* workspace, double* totals,
+                     void* stream);
+/* Its gradient, one launch: dlogits [M, C] (dense) = g[0] * w[y] * (softmax - onehot) / lse[2M] in the counting rows, zero in
+ * ignored rows. */
+int sug_point_ce_bwd(const float* logits, int64_t ld, const int64_t* label, int M, int C, int64_t ignore_index,
+                     const float* class_weight, const float* g, const float* lse, float* dlogits, void* stream);
+/* The ShapeNet-Part protocol for one batch, on the device, no host synchronisation (capturable).  logits [B, N, C] fp32
+ * (dense), label [B, N] int64, category [B] int64 on the device; part_first, part_count [K] int32 are HOST arrays (they
+ * travel by value with the launch and are checked before it): category k owns the parts
+ * [part_first[k], part_first[k] + part_count[k]).  Per cloud: the prediction of a point is the arg-max over its category's
+ * range ONLY (lowest index on ties); for every part p of the range I = #(pred == p and label == p), U = #(pred == p or
+ * label == p), the part's IoU is 1 where U == 0, else (double)I / (double)U; the shape's IoU is their fp64 sum in part order
+ * divided by part_count.  A cloud whose category is outside [0, K), or with a label outside its category's range, is NOT
+ * scored: it raises the error word by one and changes nothing else.  Two launches: a workgroup per cloud writes the cloud's
+ * record (records: B * SUG_SEG_RECORD_WORDS 64-bit words of scratch), one workgroup adds the records to state in cloud
+ * order.  state: SUG_SEG_STATE_WORDS int64 / fp64 words, zeroed by the caller before the first batch.
+ * 1 <= B <= SUG_SEG_MAX_CLOUDS, N >= 1, C <= SUG_SEG_MAX_PARTS, K <= SUG_SEG_MAX_CATEGORIES,
+ * 1 <= part_count[k] <= SUG_SEG_MAX_CATEGORY_PARTS and every range inside [0, C): checked on the host before any launch. */
+#define SUG_SEG_MAX_PARTS 64
+#define SUG_SEG_MAX_CATEGORIES 64
+#define SUG_SEG_MAX_CATEGORY_PARTS 16
+#define SUG_SEG_MAX_CLOUDS 1024
+#define SUG_SEG_RECORD_WORDS 40
+#define SUG_SEG_SHAPES 0              /* int64: clouds scored */
+#define SUG_SEG_POINTS 1              /* int64: their points */
+#define SUG_SEG_CORRECT 2             /* int64: of them predicted as labelled */
+#define SUG_SEG_ERROR 3               /* int64: clouds not scored */
+#define SUG_SEG_CAT_IOU 8             /* fp64 [64]: sum of the shape IoUs of a category */
+#define SUG_SEG_CAT_SHAPES 72         /* int64 [64] */
+#define SUG_SEG_PART_POINTS 136       /* int64 [64]: points labelled with a part */
+#define SUG_SEG_PART_CORRECT 200      /* int64 [64]: of them predicted as it */
+#define SUG_SEG_STATE_WORDS 264
+int sug_part_iou_accumulate(const float* logits, const int64_t* label, const int64_t* category, const int32_t* part_first,
+                            const int32_t* part_count, int B, int N, int C, int K, void* records, void* state, void* stream);
 
 
 /* ---- KPConv backbone (model/KPConv_model.py, model/KPConv_blocks.py; rigid kernel points, linear influence, sum) ----

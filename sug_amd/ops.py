@@ -2721,6 +2721,138 @@ def eval_accumulate(state, logits1, label, logits2=None, loss=None, ce=None, out
           'sug_eval_accumulate')
 
 
+# ----------------------------------------------------------------------------- dense prediction (csrc/seg.hip)
+(POINT_CE_MAX_ROWS, POINT_CE_MAX_CLASSES, POINT_CE_BLOCK_ROWS, POINT_CE_PARTIAL_WORDS) = (_H['SUG_POINT_CE_' + _n] for _n in (
+    'MAX_ROWS', 'MAX_CLASSES', 'BLOCK_ROWS', 'PARTIAL_WORDS'))
+(SEG_MAX_PARTS, SEG_MAX_CATEGORIES, SEG_MAX_CATEGORY_PARTS, SEG_MAX_CLOUDS, SEG_RECORD_WORDS, SEG_SHAPES, SEG_POINTS, SEG_CORRECT,
+ SEG_ERROR, SEG_CAT_IOU, SEG_CAT_SHAPES, SEG_PART_POINTS, SEG_PART_CORRECT, SEG_STATE_WORDS) = (_H['SUG_SEG_' + _n] for _n in (
+     'MAX_PARTS', 'MAX_CATEGORIES', 'MAX_CATEGORY_PARTS', 'MAX_CLOUDS', 'RECORD_WORDS', 'SHAPES', 'POINTS', 'CORRECT', 'ERROR',
+     'CAT_IOU', 'CAT_SHAPES', 'PART_POINTS', 'PART_CORRECT', 'STATE_WORDS'))
+
+
+class _PointCE(torch.autograd.Function):
+    """F.cross_entropy(logits [M, C], label [M], weight, ignore_index, reduction='mean') over sug_point_ce_fwd (two launches)
+    and sug_point_ce_bwd (one); the forward's fold also advances the caller's `totals` and, when asked, writes the arg-max."""
+
+    @staticmethod
+    def forward(ctx, y, label, weight, ignore_index, totals, want_pred):
+        _need_gpu(y, label, weight, totals)
+        if y.dim() != 2 or y.dtype != torch.float32 or label.numel() != y.shape[0]:
+            raise RuntimeError('ops.point_ce: fp32 logits [..., C] and one label per row (got %s %s, %d labels)'
+                               % (tuple(y.shape), y.dtype, label.numel()))
+        M, C = y.shape
+        if weight is not None and (weight.dtype != torch.float32 or weight.numel() != C):
+            raise RuntimeError('ops.point_ce: weight is an fp32 tensor of C = %d elements' % C)
+        if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 2 or not totals.is_contiguous()):
+            raise RuntimeError('ops.point_ce: totals is a contiguous float64 tensor of 2 elements')
+        a = y if (y.stride(1) == 1 and y.stride(0) >= C) else y.contiguous()
+        lab = label.reshape(-1).long().contiguous()
+        w = None if weight is None else weight.detach().reshape(-1).contiguous()
+        words = -(-M // POINT_CE_BLOCK_ROWS) * POINT_CE_PARTIAL_WORDS             # sug_point_ce_workspace(M), without the call
+        loss = torch.empty((), dtype=torch.float32, device=y.device)
+        lse = torch.empty(2 * M + 1, dtype=torch.float32, device=y.device)      # maxima | log-sums | the denominator
+        pred = torch.empty(M, dtype=torch.int32, device=y.device) if want_pred else None
+        ws = torch.empty(words, dtype=torch.float64, device=y.device)
+        check(lib().sug_point_ce_fwd(_p(a), a.stride(0), _p(lab), M, C, int(ignore_index), _p(w), _p(loss), _p(lse), _p(pred),
+                                     _p(ws), _p(totals), _st()), 'sug_point_ce_fwd')
+        ctx.save_for_backward(a, lab, lse, w)
+        ctx.meta = (M, C, int(ignore_index))
+        if want_pred:
+            ctx.mark_non_differentiable(pred)
+            return loss, pred
+        return loss, None
+
+    @staticmethod
+    def backward(ctx, g, _gpred=None):
+        a, lab, lse, w = ctx.saved_tensors
+        M, C, ign = ctx.meta
+        gs = g.detach().to(dtype=torch.float32).reshape(1)
+        d = torch.empty(M, C, dtype=torch.float32, device=a.device)
+        check(lib().sug_point_ce_bwd(_p(a), a.stride(0), _p(lab), M, C, ign, _p(w), _p(gs), _p(lse), _p(d), _st()),
+              'sug_point_ce_bwd')
+        return d, None, None, None, None, None
+
+
+def point_ce_supported(logits, label):
+    """What point_ce takes: fp32 logits [..., C] on the HIP device with 2 <= C <= 64 and 1 <= rows <= 2^22, one label per row."""
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() >= 1):
+        return False
+    C = logits.shape[-1]
+    if not 2 <= C <= POINT_CE_MAX_CLASSES:
+        return False
+    M = logits.numel() // C
+    return 1 <= M <= POINT_CE_MAX_ROWS and label.is_cuda and label.numel() == M and not label.is_floating_point()
+
+
+def point_ce(logits, label, weight=None, ignore_index=-100, totals=None, want_pred=False):
+    """logits [..., C] fp32 (the leading dimensions are flattened to rows), label: one integer per row -> the 0-d loss
+    F.cross_entropy(rows, label, weight=weight, ignore_index=ignore_index) -- the mean divides by the sum of weight[label]
+    over the counting rows -- and, with want_pred, (loss, pred): the rows' arg-max (int32, lowest index on ties, ignored rows
+    included) in the leading dimensions' shape.  Labels as ops.ce takes them (ignore_index rows skipped, any other label
+    outside [0, C) -> NaN).  totals: None or a device float64 [2] that the forward advances by (loss * counting rows,
+    counting rows).  1 <= rows <= 2^22, 2 <= C <= 64 (the library refuses anything else)."""
+    _need_gpu(logits, label, weight, totals)
+    if logits.dim() < 1 or logits.shape[-1] < 1:
+        raise RuntimeError('ops.point_ce: logits [..., C] (got %s)' % (tuple(logits.shape),))
+    lead = logits.shape[:-1]
+    loss, pred = _PointCE.apply(logits.reshape(-1, logits.shape[-1]), label, weight, ignore_index, totals, bool(want_pred))
+    return (loss, pred.view(lead)) if want_pred else loss
+
+
+def part_iou_state(device):
+    """A zeroed state block of sug_part_iou_accumulate (SUG_SEG_STATE_WORDS int64 / fp64 words, held as int64)."""
+    return torch.zeros(SEG_STATE_WORDS, dtype=torch.int64, device=device)
+
+
+def part_iou_state_fields(state):
+    """The accumulators of a part-IoU state block (on the host: the one read), as a dict of numpy values."""
+    s = state.cpu()
+    d = s.view(torch.float64).numpy()
+    i = s.numpy()
+    K, C = SEG_MAX_CATEGORIES, SEG_MAX_PARTS
+    return {'shapes': int(i[SEG_SHAPES]), 'points': int(i[SEG_POINTS]), 'correct': int(i[SEG_CORRECT]), 'error': int(i[SEG_ERROR]),
+            'cat_iou': d[SEG_CAT_IOU:SEG_CAT_IOU + K].copy(), 'cat_shapes': i[SEG_CAT_SHAPES:SEG_CAT_SHAPES + K].copy(),
+            'part_points': i[SEG_PART_POINTS:SEG_PART_POINTS + C].copy(),
+            'part_correct': i[SEG_PART_CORRECT:SEG_PART_CORRECT + C].copy()}
+
+
+def part_table(part_first, part_count):
+    """The categories' part ranges as the two host int32 arrays sug_part_iou_accumulate takes (lists, numpy arrays or CPU
+    tensors; they travel by value with every launch, so they are never read back from a device)."""
+    import numpy as np
+    out = []
+    for v in (part_first, part_count):
+        if isinstance(v, torch.Tensor):
+            if v.is_cuda:
+                raise RuntimeError('ops.part_iou_accumulate: part_first / part_count are host arrays (a device tensor would have '
+                                   'to be read back)')
+            v = v.numpy()
+        out.append(np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.int32))
+    if out[0].shape != out[1].shape:
+        raise RuntimeError('ops.part_iou_accumulate: part_first and part_count differ in length')
+    return out[0], out[1]
+
+
+def part_iou_accumulate(logits, label, category, part_first, part_count, state):
+    """One batch of the ShapeNet-Part protocol into `state` (sug_part_iou_accumulate): logits [B, N, C] fp32, label [B, N] and
+    category [B] int64 on the HIP device; category k owns the parts [part_first[k], part_first[k] + part_count[k]) (host
+    arrays, see part_table).  No host synchronisation."""
+    _need_gpu(logits, label, category, state)
+    if logits.dim() != 3 or logits.dtype != torch.float32:
+        raise RuntimeError('ops.part_iou_accumulate: fp32 logits [B, N, C] (got %s %s)' % (tuple(logits.shape), logits.dtype))
+    B, N, C = logits.shape
+    if label.dtype != torch.int64 or label.shape != (B, N) or category.dtype != torch.int64 or category.shape != (B,):
+        raise RuntimeError('ops.part_iou_accumulate: label int64 [B, N] and category int64 [B] (got %s %s, %s %s)'
+                           % (tuple(label.shape), label.dtype, tuple(category.shape), category.dtype))
+    if state.dtype != torch.int64 or state.numel() != SEG_STATE_WORDS or not state.is_contiguous():
+        raise RuntimeError('ops.part_iou_accumulate: state is the block ops.part_iou_state() returns')
+    first, count = part_table(part_first, part_count)
+    records = torch.empty(max(B, 1) * SEG_RECORD_WORDS, dtype=torch.int64, device=logits.device)
+    check(lib().sug_part_iou_accumulate(_p(logits.contiguous()), _p(label.contiguous()), _p(category.contiguous()),
+                                        first.ctypes.data_as(ctypes.c_void_p), count.ctypes.data_as(ctypes.c_void_p), B, N, C,
+                                        first.shape[0], _p(records), _p(state), _st()), 'sug_part_iou_accumulate')
+
+
 class _SplitHalves(torch.autograd.Function):
     """The two domain halves of a paired [2B, ...] tensor as views.  Backward: when the two gradients are adjacent row
     blocks of one buffer (what mmd_assemble's and the paired kernels' backwards hand back) the pair's gradient is that
