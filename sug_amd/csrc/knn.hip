@@ -204,141 +204,186 @@ int dispatch_knn_c(const float* x, int64_t ldx, int B, int N, int C, int k, int3
 }
 
 // ---- reverse lists ---------------------------------------------------------
-// A workgroup owns the destinations [lo, hi) of one cloud (RS ranges per cloud, so that 64 clouds fill the chip),
-// everything in LDS: it scans the cloud's N*k neighbour entries, counts those that point into its range (and those
-// that point below it: its base offset in the cloud's entry array), exclusive scan -> fill (atomic cursor, arbitrary
-// order) -> rank sort of every destination's list straight into its final place, so that float sums downstream
-// are deterministic: a half-wave per list (lane u counts the entries smaller than entry u: the reads of one list
-// are LDS broadcasts with no dependence between them), a whole wave for lists longer than 32 (hub points).
-// LDS: 2*Nr + BLOCK/64 ints + the worst case of N*k entries (82 KB).
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void knn_reverse_kernel(const int32_t* __restrict__ idx, int N,
-                                                            int E, int RS, int sorted, int32_t* __restrict__ rev_off,
-                                                            int32_t* __restrict__ rev_ent) {
+// A stable counting placement, no atomics and no per-list sort: every entry goes straight to its final place.
+// A workgroup owns the destinations [lo, hi) of one cloud (RS ranges per cloud, so that 64 clouds fill the chip):
+//   1. it loads the cloud's E entries ONCE into registers (wave w holds the contiguous span of U*64 entries behind
+//      w*U*64, U = ceil(E / 1024), every load in flight before the first use);
+//   2. it compacts the entries that point into its range into LDS IN ENTRY ORDER (ballot + prefix popcount per 64
+//      entries, wave totals scanned across the waves), packed as (destination - lo) << 16 | entry; the entries that
+//      point below the range are counted the same way: the range's base offset in the cloud's entry array;
+//   3. LSD radix sort of the compacted array by the local destination, two bits a pass: a thread owns a contiguous
+//      run of R = ceil(count / 1024) items, which it keeps in registers between the read and the scatter (the sort is
+//      in place), and a private 4-bin histogram in one 64-bit register (16-bit fields, which cannot carry: no bin of
+//      the workgroup holds 65536 items); the (digit-major, thread-minor) scan is a DPP wave scan of that register and,
+//      in every wave, a scan of the 4 x 16 wave totals.  The scanned register is the thread's four running write
+//      positions.  Stable, so the entries of a destination stay ascending;
+//   4. rev_off by a binary search of every destination in the sorted array, rev_ent copied out coalesced.
+// The work depends on the number of entries in the range (R), not on how they are spread over its destinations.
+// LDS: 32 ints of scratch + E packed items (a range may hold every entry), always within what
+// sug_reverse_lists_lds_bytes reports; E < 65536 and the range < 32768 destinations follow from its 160 KB bound.
+constexpr int REV_BLOCK = 1024;
+constexpr int REV_NW = REV_BLOCK / 64;
+static_assert(REV_NW == 16, "4 bins x 16 waves: the 64 totals a wave scans, 8 bytes a wave in the 32 scratch ints");
+
+// inclusive prefix sums over the lanes through the DPP paths (no LDS-crossbar shuffles): lanes without a source add 0
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned rev_dpp0(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ unsigned rev_row_scan(unsigned x) {          // over each row of 16 lanes
+  x += rev_dpp0<0x111, 0xf>(x);                                         // row_shr:1
+  x += rev_dpp0<0x112, 0xf>(x);                                         // row_shr:2
+  x += rev_dpp0<0x114, 0xf>(x);                                         // row_shr:4
+  x += rev_dpp0<0x118, 0xf>(x);                                         // row_shr:8
+  return x;
+}
+__device__ __forceinline__ unsigned rev_wave_scan(unsigned x) {         // over the 64 lanes
+  x = rev_row_scan(x);
+  x += rev_dpp0<0x142, 0xa>(x);                                         // row_bcast:15 into rows 1, 3
+  x += rev_dpp0<0x143, 0xc>(x);                                         // row_bcast:31 into rows 2, 3
+  return x;
+}
+
+template <int UMAX>
+__global__ __launch_bounds__(REV_BLOCK) void reverse_lists_kernel(const int32_t* __restrict__ idx, int N, int E, int RS,
+                                                                  int32_t* __restrict__ rev_off,
+                                                                  int32_t* __restrict__ rev_ent) {
   // E entries per cloud (N*k for a kNN graph, S*nsample for ball-query lists), destinations in [0, N)
-  extern __shared__ int s_i[];  // cnt[Nr] | cur[Nr] | per-wave scratch[2*BLOCK/64] | ent[E]
-  constexpr int NW = BLOCK / 64;
+  extern __shared__ int s_i[];                  // scratch[32] | item[E]
+  int* scr = s_i;
+  unsigned* tot = reinterpret_cast<unsigned*>(s_i);                    // [REV_NW] x 4 digit totals of 16 bits
+  const unsigned short* tot16 = reinterpret_cast<const unsigned short*>(s_i);
+  unsigned* item = reinterpret_cast<unsigned*>(s_i + 2 * REV_NW);
   const int Nr = (N + RS - 1) / RS;
-  int* cnt = s_i;
-  int* cur = s_i + Nr;
-  int* scr = s_i + 2 * Nr;
-  int* ent = s_i + 2 * Nr + 2 * NW;
-  const int b = blockIdx.x / RS, r = blockIdx.x % RS;
-  const int lo = r * Nr, hi = (lo + Nr < N) ? lo + Nr : N;
-  const int nr = hi > lo ? hi - lo : 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // workgroups x and x + 8 are observed to share an L2 (speed only, nothing depends on it): the RS workgroups of a cloud,
+  // which all read its whole entry array, are made neighbours in that sense when the grid divides by 8
+  const int G = gridDim.x;
+  const int wg = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+  const int b = wg / RS, r = wg % RS;
+  const int lo = min(r * Nr, N), hi = min(lo + Nr, N);
+  const int nr = hi - lo;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int32_t* ib = idx + (int64_t)b * E;
   int32_t* off = rev_off + (int64_t)b * (N + 1);
   int32_t* gent = rev_ent + (int64_t)b * E;
-  for (int i = threadIdx.x; i < nr; i += BLOCK) cnt[i] = 0;
-  __syncthreads();
-  const int total = E;
-  int below = 0;
-  // the neighbour entries are read U at a time (all loads of a batch in flight before the first use: one load per
-  // iteration, each waiting for the atomic behind it, made this kernel latency-bound)
-  constexpr int U = 5;
-  for (int e0 = threadIdx.x; e0 < total; e0 += BLOCK * U) {
-    int mv[U];
+
+  const int U = (E + REV_BLOCK - 1) / REV_BLOCK;                       // <= UMAX (the launcher's choice)
+  const int e0 = wave * U * 64 + lane;
+  int mv[UMAX];
 #pragma unroll
-    for (int u = 0; u < U; ++u) mv[u] = (e0 + u * BLOCK < total) ? ib[e0 + u * BLOCK] : -1;
+  for (int u = 0; u < UMAX; ++u) {
+    const int e = e0 + u * 64;
+    mv[u] = (u < U && e < E) ? ib[e] : -1;
+  }
+  // counts of this wave: entries into the range, valid entries below it (ballots: wave-uniform, integer, order-free)
+  int mine = 0, below = 0;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int m = mv[u];
-      if (m >= 0 && m < lo) ++below;
-      if (m >= lo && m < hi) atomicAdd(&cnt[m - lo], 1);
+  for (int u = 0; u < UMAX; ++u) {
+    if (u < U) {
+      const unsigned m = (unsigned)mv[u];
+      mine += __popcll(__ballot(m - (unsigned)lo < (unsigned)nr));
+      below += __popcll(__ballot(m < (unsigned)lo));
     }
   }
-  // base = number of valid entries that point below this range (integer sums: order-free)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
-  if (lane == 0) scr[wave] = below;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) base += scr[w];
-  // exclusive scan of the counts: PER consecutive destinations per thread, wave scan, then across waves
-  const int PER = (nr + BLOCK - 1) / BLOCK;
-  const int t0 = threadIdx.x * PER;
-  int local = 0;
-  for (int i = t0; i < t0 + PER && i < nr; ++i) local += cnt[i];
-  int incl = local;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
+  if (lane == 0) {
+    scr[wave] = mine;
+    scr[REV_NW + wave] = below;
   }
-  if (lane == 63) scr[NW + wave] = incl;
   __syncthreads();
-  int wbase = 0, filled = 0;
+  // row 0 of every wave scans the 16 counts, row 1 the 16 counts below the range
+  const unsigned sc = rev_row_scan(lane < 2 * REV_NW ? (unsigned)scr[lane] : 0u);
+  const int count = __builtin_amdgcn_readlane((int)sc, REV_NW - 1);
+  const int base = __builtin_amdgcn_readlane((int)sc, 2 * REV_NW - 1);
+  int run = wave > 0 ? __builtin_amdgcn_readlane((int)sc, max(wave - 1, 0)) : 0;
 #pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const int t = scr[NW + w];
-    if (w < wave) wbase += t;
-    filled += t;
-  }
-  int run = wbase + incl - local;
-  for (int i = t0; i < t0 + PER && i < nr; ++i) {
-    const int c = cnt[i];
-    cur[i] = run;
-    off[lo + i] = base + run;
-    run += c;
-  }
-  if (r == RS - 1 && threadIdx.x == 0) off[N] = base + filled;
-  __syncthreads();
-  for (int e0 = threadIdx.x; e0 < total; e0 += BLOCK * U) {
-    int mv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) mv[u] = (e0 + u * BLOCK < total) ? ib[e0 + u * BLOCK] : -1;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int m = mv[u];
-      if (m >= lo && m < hi) ent[atomicAdd(&cur[m - lo], 1)] = e0 + u * BLOCK;
+  for (int u = 0; u < UMAX; ++u) {
+    if (u < U) {
+      const unsigned key = (unsigned)mv[u] - (unsigned)lo;
+      const bool in = key < (unsigned)nr;
+      const unsigned long long bal = __ballot(in);
+      const unsigned at = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, (unsigned)run));
+      if (in) item[at] = (key << 16) | (unsigned)(e0 + u * 64);
+      run += __popcll(bal);
     }
   }
-  __syncthreads();
-  // lists up to 32 entries: two per wave (one per half-wave); the loop bound is made uniform over the wave
-  // (sorted = 0: the consumer does not need a fixed order -- the lists go out as the atomics left them)
-  const int half = lane >> 5, hl = lane & 31;
-  for (int i0 = wave * 2; sorted && i0 < nr; i0 += NW * 2) {
-    const int i = i0 + half;
-    const int n = i < nr ? cnt[i] : 0;
-    const int s = i < nr ? cur[i] - n : 0;
-    const int nn = n <= 32 ? n : 0;
-    const int nmax = max(nn, __shfl_xor(nn, 32));
-    const int nlast = nn > 0 ? nn - 1 : 0;
-    const int key = ent[s + min(hl, nlast)];
-    int rank = 0;
-    for (int j0 = 0; j0 < nmax; j0 += 8) {           // 8 independent LDS reads in flight
-      int v[8];
+  __syncthreads();                              // the scratch is the sort's behind this barrier
+
+  const int R = (count + REV_BLOCK - 1) / REV_BLOCK;                   // <= U
+  const int p0 = threadIdx.x * R;
+  const int own = min(max(count - p0, 0), R);                          // items of this thread's run
+  int keybits = 0;
+  while ((1 << keybits) < nr) ++keybits;
+  for (int sh = 16; sh < 16 + keybits; sh += 2) {
+    unsigned it[UMAX];
+    unsigned long long h = 0;                   // bins 0 .. 3, 16 bits each
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = ent[s + min(j0 + u, nlast)];   // unconditional (a guarded read is a branch + wait)
-#pragma unroll
-      for (int u = 0; u < 8; ++u) rank += (j0 + u < nn && v[u] < key) ? 1 : 0;      // entries are distinct
-    }
-    // in place: every read of this list (same half-wave, program order) is behind us
-    if (hl < nn) ent[s + rank] = key;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < filled; e += BLOCK) gent[base + e] = ent[e];
-  __syncthreads();            // the long lists below overwrite their (unsorted) copy
-  // longer lists (hub points): a wave per list
-  for (int i = wave; sorted && i < nr; i += NW) {
-    const int n = cnt[i];
-    if (n <= 32) continue;                           // uniform over the wave
-    const int s = cur[i] - n;
-    for (int u = lane; u < n; u += 64) {
-      const int key = ent[s + u];
-      int rank = 0;
-      for (int j0 = 0; j0 < n; j0 += 8) {
-        int v[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = ent[s + min(j0 + t, n - 1)];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) rank += (j0 + t < n && v[t] < key) ? 1 : 0;
+    for (int u = 0; u < UMAX; ++u) {
+      if (u < R) {                              // uniform over the workgroup
+        if (u < own) {
+          it[u] = item[p0 + u];
+          h += 1ull << ((it[u] >> (sh - 4)) & 0x30u);
+        }
       }
-      gent[base + s + rank] = key;
     }
+    // inclusive over the wave's lanes (a wave holds at most 64 * UMAX items)
+    const unsigned ilo = rev_wave_scan((unsigned)h), ihi = rev_wave_scan((unsigned)(h >> 32));
+    if (lane == 63) {
+      tot[2 * wave] = ilo;
+      tot[2 * wave + 1] = ihi;
+    }
+    __syncthreads();                            // every item of this pass is in registers behind this barrier
+    // every wave scans the 64 totals for itself, digit-major: lane d*16 + w holds bin d of wave w
+    const unsigned v = tot16[(lane & 15) * 4 + (lane >> 4)];
+    const unsigned x = rev_wave_scan(v) - v;
+    const unsigned s0 = (unsigned)__builtin_amdgcn_readlane((int)x, wave);
+    const unsigned s1 = (unsigned)__builtin_amdgcn_readlane((int)x, 16 + wave);
+    const unsigned s2 = (unsigned)__builtin_amdgcn_readlane((int)x, 32 + wave);
+    const unsigned s3 = (unsigned)__builtin_amdgcn_readlane((int)x, 48 + wave);
+    // the thread's four write positions: bins before + waves before + lanes before, field by field (all <= count)
+    const unsigned clo = (s0 | (s1 << 16)) + (ilo - (unsigned)h), chi = (s2 | (s3 << 16)) + (ihi - (unsigned)(h >> 32));
+    unsigned long long cur = ((unsigned long long)chi << 32) | clo;
+#pragma unroll
+    for (int u = 0; u < UMAX; ++u) {
+      if (u < R) {
+        if (u < own) {
+          const unsigned sft = (it[u] >> (sh - 4)) & 0x30u;
+          item[(unsigned)(cur >> sft) & 0xffffu] = it[u];
+          cur += 1ull << sft;
+        }
+      }
+    }
+    __syncthreads();
   }
+
+  for (int p = threadIdx.x; p < count; p += REV_BLOCK) gent[base + p] = (int)(item[p] & 0xffffu);
+  // rev_off[lo + i] = base + the first position whose destination is >= i (behind the stores above, which drain meanwhile)
+  for (int i = threadIdx.x; i < nr; i += REV_BLOCK) {
+    int a = 0, n = count;
+    while (n > 0) {
+      const int half = n >> 1;
+      if ((int)(item[a + half] >> 16) < i) {
+        a += half + 1;
+        n -= half + 1;
+      } else {
+        n = half;
+      }
+    }
+    off[lo + i] = base + a;
+  }
+  if (r == RS - 1 && threadIdx.x == 0) off[N] = base + count;
+}
+
+template <int UMAX>
+int reverse_lists_launch(const int32_t* idx, int B, int E, int N, int RS, int32_t* rev_off, int32_t* rev_ent,
+                         hipStream_t st) {
+  static SugLdsOptIn note;
+  if (int rc = sug_allow_dynamic_lds(note, &reverse_lists_kernel<UMAX>, 160 * 1024, "sug_reverse_lists")) return rc;
+  const size_t sh = (size_t)(2 * REV_NW + E) * sizeof(int);
+  hipLaunchKernelGGL((reverse_lists_kernel<UMAX>), dim3(B * RS), dim3(REV_BLOCK), sh, st, idx, N, E, RS, rev_off,
+                     rev_ent);
+  SUG_LAUNCH_CHECK("sug_reverse_lists");
+  return SUG_OK;
 }
 
 }  // namespace
@@ -357,8 +402,11 @@ extern "C" int sug_knn(const float* x, int64_t ldx, int B, int N, int C, int k, 
   return dispatch_knn_c<32>(x, ldx, B, N, C, k, idx, st);
 }
 
-// LDS bytes of the reverse-list build for B clouds of E entries into N destinations (and its destination ranges per cloud):
-// callers that need to know beforehand whether sug_reverse_lists will take the shape compare this with 160 KB
+// LDS bytes that decide whether the reverse-list build takes B clouds of E entries into N destinations (and its destination
+// ranges per cloud): callers that need to know beforehand whether sug_reverse_lists will take the shape compare this with
+// 160 KB.  The formula is that of the build the list-based backwards were shaped around (two counters per destination of a
+// range); it is kept as it is because it chooses between a list-based backward and its fallback, which sum in different
+// orders.  reverse_lists_kernel needs no more than it for any shape (32 + E ints).
 size_t sug_reverse_lists_lds_bytes(int B, int E, int N, int* ranges) {
   int RS = 1;                                    // destination ranges per cloud: >= 256 workgroups when B allows
   while (RS < 8 && B * RS < 256 && N / (RS * 2) >= 64) RS *= 2;
@@ -367,21 +415,26 @@ size_t sug_reverse_lists_lds_bytes(int B, int E, int N, int* ranges) {
   return (size_t)(2 * Nr + 2 * (1024 / 64) + (size_t)E) * sizeof(int);
 }
 
-// reverse lists of B clouds with E index entries each, destinations in [0, N)
+// reverse lists of B clouds with E index entries each, destinations in [0, N); the lists always come out ascending
+// (sorted = 0 only says that the consumer would not need it: the stable placement has no cheaper unordered form)
 int sug_reverse_lists(const int32_t* idx, int B, int E, int N, int sorted, int32_t* rev_off, int32_t* rev_ent,
                       hipStream_t st) {
+  (void)sorted;
   SUG_REQUIRE(idx && rev_off && rev_ent, "sug_reverse_lists: null pointer");
   SUG_REQUIRE(B > 0 && N > 0 && E > 0, "sug_reverse_lists: bad shape");
-  constexpr int BLOCK = 1024;
   int RS = 0;
   const size_t sh = sug_reverse_lists_lds_bytes(B, E, N, &RS);
   SUG_REQUIRE(sh <= 160 * 1024, "sug_reverse_lists: %d entries per cloud are too many for the LDS-resident build", E);
-  static SugLdsOptIn note;
-  if (int rc = sug_allow_dynamic_lds(note, &knn_reverse_kernel<BLOCK>, 160 * 1024, "sug_reverse_lists")) return rc;
-  hipLaunchKernelGGL((knn_reverse_kernel<BLOCK>), dim3(B * RS), dim3(BLOCK), sh, st, idx, N, E, RS, sorted, rev_off,
-                     rev_ent);
-  SUG_LAUNCH_CHECK("sug_reverse_lists");
-  return SUG_OK;
+  const int U = sug_divup(E, REV_BLOCK);         // entries a thread holds in registers: <= 40 by the bound above
+  if (U <= 8) return reverse_lists_launch<8>(idx, B, E, N, RS, rev_off, rev_ent, st);
+  if (U <= 20) return reverse_lists_launch<20>(idx, B, E, N, RS, rev_off, rev_ent, st);
+  SUG_REQUIRE(U <= 40, "sug_reverse_lists: %d entries per cloud are too many for the LDS-resident build", E);
+  return reverse_lists_launch<40>(idx, B, E, N, RS, rev_off, rev_ent, st);
+}
+
+extern "C" int sug_reverse_lists_build(const int32_t* idx, int B, int E, int N, int sorted, int32_t* rev_off,
+                                       int32_t* rev_ent, void* stream) {
+  return sug_reverse_lists(idx, B, E, N, sorted, rev_off, rev_ent, (hipStream_t)stream);
 }
 
 extern "C" int sug_knn_reverse(const int32_t* idx, int B, int N, int k, int32_t* rev_off,

@@ -232,6 +232,23 @@ def knn_reverse(idx):
     return off, ent
 
 
+def reverse_lists(idx, n_dest, sorted=True, ent=None):
+    """idx [B,E] int32 with destinations in [0, n_dest) (others are skipped) -> (rev_off [B,n_dest+1], rev_ent [B,E]):
+    per cloud the valid entries in ascending (destination, entry) order and the exclusive prefix of the counts
+    (sug_reverse_lists_build).  rev_ent behind rev_off[b, n_dest] entries is not written: `ent`, when given, is the
+    [B,E] int32 buffer to fill."""
+    _need_gpu(idx)
+    idx = _i32(idx).contiguous()
+    B, E = idx.shape
+    off = torch.empty(B, n_dest + 1, dtype=torch.int32, device=idx.device)
+    if ent is None:
+        ent = torch.empty(B, E, dtype=torch.int32, device=idx.device)
+    assert ent.shape == (B, E) and ent.dtype == torch.int32 and ent.is_contiguous() and ent.device == idx.device
+    check(lib().sug_reverse_lists_build(_p(idx), B, E, n_dest, 1 if sorted else 0, _p(off), _p(ent), _st()),
+          'sug_reverse_lists_build')
+    return off, ent
+
+
 def fps(xyz, npoint, start):
     """xyz [B,N,3], start [B] (any int dtype/device) -> [B,npoint] int32."""
     _need_gpu(xyz)
