@@ -1288,6 +1288,52 @@ int sug_prepare_batch_aug(const float* pts, int M, int P, const int32_t* idx, in
                           float* angles_out, float* noise_out, int32_t* sel_out, float* scales_out, float* perturb_out,
                           float* shifts_out, void* stream);
 
+/* The part-segmentation batch: sug_prepare_batch_aug for clouds of different lengths that carry extra channels and one part
+ * label per point, in one launch, one workgroup per cloud (a second kernel; the one above is untouched).
+ * Resident data: pts [M, P, 3] fp32; extra [M, P, E] fp32 (null when E == 0, 0 <= E <= SUG_PREP_SEG_MAX_EXTRA);
+ * point_label [M, P] uint8 (part ids, below SUG_SEG_MAX_PARTS); category [M] int64 (may be null when category_out is);
+ * lengths [M] int32: the valid points of cloud m are its rows 0 .. lengths[m]-1 (null: every cloud has P points).
+ * Outputs: out [B, 3 + E, N] fp32 (xyz, then the extra channels: Pointnet2PartSeg.forward's input), label_out [B, N] int64,
+ * category_out [B] int64 (may be null).  With ci = idx[b] and L = lengths[ci], in stage order:
+ *   1. SUG_PREP_NORMALIZE: normal_pc over the first L points only, sug_prepare_batch's arithmetic and summation order with L
+ *      in place of P.  A cloud whose L points coincide has a largest norm of 0 and comes out NaN, as the reference's
+ *      normal_pc gives; it is not special-cased.
+ *   2. The source point src of output row n -- every row has one, there are no padding rows:
+ *        sel [B, N] given: src = sel[b, n]; values may repeat, N <= P is not required;
+ *        L > N:  the subset rule above: keys from SUG_PREP_DRAW_SUBSET (points >= L keyed ~0), the first N in ascending
+ *                (word, point) order;
+ *        L <= N: rows 0 .. L-1 are the points in index order (in sorted-key order with SUG_PREP_SHUFFLE); rows L .. N-1 are
+ *                drawn with replacement: row n takes word (n - L) % 4 of the Philox block at purpose SUG_PREP_DRAW_FILL,
+ *                index (n - L) / 4, and src = (uint64(word) * L) >> 32.
+ *      Whether a cloud sorts is decided in its workgroup from L; the host never reads a length.
+ *   3. Coordinates: pre_rot, z-rotation, jitter, scale, perturbation, shift, in sug_prepare_batch_aug's order and arithmetic.
+ *      In-kernel jitter normals are per OUTPUT row (a point taken twice jitters independently); supplied noise [B, P, 3] is
+ *      indexed by the source point.
+ *   4. Extra channels: out[b, 3 + e, n] = extra[ci, src, e], copied through.  With SUG_PREP_NORMALS (needs E >= 3) channels
+ *      0..2 are a direction: they go through pre_rot, the z-rotation and the perturbation matrix in the coordinates'
+ *      forms ((x R0j + y R1j) + z R2j; x c + y s, y c - x s), and through nothing else (no normalise, jitter, scale, shift).
+ *   5. label_out[b, n] = point_label[ci, src]; category_out[b] = category[ci].
+ * Bad inputs are never dereferenced and never silently scored.  idx[b] outside [0, M) or L outside [1, P]: the whole cloud
+ * is NaN, its labels are -1 and its category is -1 (debug outputs: sel -1, the draws those of a launch with every stage
+ * off).  A sel entry outside [0, L): that row is NaN and its label -1.  A label of -1 makes sug_point_ce_fwd's loss NaN and
+ * sug_part_iou_accumulate raise its error word.
+ * The draws, seed, counter and aug_params are sug_prepare_batch_aug's; the old purposes and words of the generator do not
+ * move.  counter may be null only when sel is given and no other draw is needed.  Debug outputs (each may be null): those
+ * of sug_prepare_batch_aug, with sel_out [B, N] the source of every row, fill rows included.
+ * With lengths null, E == 0 and P >= N, out equals sug_prepare_batch_aug's bit for bit (P < N: rows 0 .. P-1).
+ * Limits, checked on the host before the launch: B, M, P, N >= 1; P, N <= SUG_PREP_MAX_POINTS.  Vector stores only, no
+ * atomics; bit-reproducible from (inputs, seed, *counter); a cloud's output depends on the batch only through its slot b. */
+#define SUG_PREP_NORMALS 128
+#define SUG_PREP_DRAW_FILL 0x60000000u
+#define SUG_PREP_SEG_MAX_EXTRA 8
+int sug_prepare_seg_batch(const float* pts, const float* extra, const uint8_t* point_label, const int64_t* category,
+                          const int32_t* lengths, int M, int P, int E, const int32_t* idx, int B, int N, int stages,
+                          const float* pre_rot, const float* angles, const float* noise, const int32_t* sel,
+                          const float* scales, const float* perturb, const float* shifts, uint64_t seed,
+                          const uint64_t* counter, float sigma, float clip, const float* aug_params, float* out,
+                          int64_t* label_out, int64_t* category_out, float* angles_out, float* noise_out, int32_t* sel_out,
+                          float* scales_out, float* perturb_out, float* shifts_out, void* stream);
+
 /* ---- Batched point-to-point ICP fitness (the geometric sub-domain splitter, dataset_splitter.py:217-231) ----------------
  * icp_distance() calls open3d's registration_icp(source, target, max_correspondence_distance=0.15) once per cloud; this
  * entry point registers B (source, target) pairs in one launch, one workgroup per pair.  src [B or 1, Ns, 3] fp32 with

@@ -171,7 +171,8 @@ class UnifiedPointDG:
 
 class DeviceLoader:
     """Stands in for DataLoader(dataset, batch_size=.., shuffle=.., drop_last=..) and DataLoader(dataset,
-    batch_sampler=..) over a UnifiedPointDG: same number and composition of batches.  The shuffle order comes from a
+    batch_sampler=..) over a UnifiedPointDG -- or any dataset with `batch(indices)`, `seed`, `device` and `__len__`, such as
+    partseg.PartSegDataset, whose batches are (points, category, label): same number and composition of batches.  The shuffle order comes from a
     host torch.Generator seeded with the dataset's seed (one randperm per epoch).  An epoch's index order goes to the
     device in one copy; a batch is a slice of it, one kernel launch and a label gather -- no host wait.  `sampler`: any
     iterable of indices with a length (a DistributedSampler: this rank's share), read once per epoch."""

@@ -4328,6 +4328,81 @@ def prepare_batch_aug(pts, idx, num_points, pre_rotate, aug, *, angles=None, noi
     return (out, *draws) if return_draws else out
 
 
+PREP_NORMALS, PREP_SEG_MAX_EXTRA = _H['SUG_PREP_NORMALS'], _H['SUG_PREP_SEG_MAX_EXTRA']   # sug_prepare_seg_batch
+
+
+def prepare_seg_batch(pts, extra, point_label, category, lengths, idx, num_points, *, angles=None, noise=None, sel=None,
+                      scales=None, perturb=None, shifts=None, seed=None, counter=None, out=None, label_out=None,
+                      category_out=None, sigma=0.01, clip=0.05, scale_low=0.8, scale_high=1.25, shift_range=0.1,
+                      angle_sigma=0.06, angle_clip=0.18, return_draws=False, stages=None, pre_matrix=None):
+    """The part-segmentation batch in one launch (sug_prepare_seg_batch): pts [M,P,3] fp32, extra [M,P,E] fp32 or None,
+    point_label [M,P] uint8, category [M] int64, lengths [M] int32 or None (every cloud has P points), idx [B] int32 ->
+    (points [B,3+E,num_points] fp32, category [B] int64, label [B,num_points] int64), the argument order of SegStep.step.
+    Every output row is a real point: a cloud longer than num_points gives a random ordered subset, a shorter one all its
+    points and then draws with replacement.  `stages` (default PREP_NORMALIZE) selects prepare_batch_aug's stage bits and
+    PREP_NORMALS, which turns extra channels 0..2 with the cloud; the draws come from the keywords when given (`sel` may
+    repeat points), else from the in-kernel generator at (`seed`, `counter`).  return_draws: the three outputs, then
+    prepare_batch_aug's draws, with sel [B,N] the source point of every row.  No host synchronisation; with `out`,
+    `label_out`, `category_out` and `counter` given the call is one kernel launch and can be captured."""
+    _need_gpu(pts, extra, point_label, category, lengths, idx, angles, noise, sel, scales, perturb, shifts, counter, out,
+              label_out, category_out)
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise ValueError('prepare_seg_batch: pts must be a contiguous fp32 [M, P, 3] tensor, got %s %s' % (tuple(pts.shape), pts.dtype))
+    if idx.dim() != 1 or idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise ValueError('prepare_seg_batch: idx must be a contiguous int32 [B] tensor')
+    M, P, _ = pts.shape
+    B, N = idx.shape[0], int(num_points)
+    dev = pts.device
+    if extra is not None and (extra.dim() != 3 or tuple(extra.shape[:2]) != (M, P)):
+        raise ValueError('prepare_seg_batch: extra must be [M, P, E] = [%d, %d, E], got %s' % (M, P, tuple(extra.shape)))
+    E = 0 if extra is None else int(extra.shape[2])
+    if E == 0:
+        extra = None
+    if stages is None:
+        stages = PREP_NORMALIZE
+    pre = (ctypes.c_float * 9)(*pre_matrix) if pre_matrix is not None else None
+    params = (ctypes.c_float * PREP_AUG_PARAMS)()
+    for slot, v in zip(_PREP_AUG_SLOTS, (scale_low, scale_high, shift_range, angle_sigma, angle_clip)):
+        params[slot] = v
+
+    def given(t, shape, dtype, name):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError('prepare_seg_batch: %s must be a contiguous %s tensor of shape %s, got %s %s'
+                             % (name, dtype, shape, t.dtype, tuple(t.shape)))
+    if point_label is None or category is None:
+        raise ValueError('prepare_seg_batch: point_label [M, P] uint8 and category [M] int64 are required')
+    given(extra, (M, P, E), torch.float32, 'extra')
+    given(point_label, (M, P), torch.uint8, 'point_label')
+    given(category, (M,), torch.int64, 'category')
+    given(lengths, (M,), torch.int32, 'lengths')
+    given(angles, (B,), torch.float32, 'angles')
+    given(noise, (B, P, 3), torch.float32, 'noise')
+    given(sel, (B, N), torch.int32, 'sel')
+    given(scales, (B,), torch.float32, 'scales')
+    given(perturb, (B, 3), torch.float32, 'perturb')
+    given(shifts, (B, 3), torch.float32, 'shifts')
+    given(out, (B, 3 + E, N), torch.float32, 'out')
+    given(label_out, (B, N), torch.int64, 'label_out')
+    given(category_out, (B,), torch.int64, 'category_out')
+    given(counter, (1,), torch.int64, 'counter')
+    if out is None:
+        out = torch.empty(B, 3 + E, N, dtype=torch.float32, device=dev)
+    if label_out is None:
+        label_out = torch.empty(B, N, dtype=torch.int64, device=dev)
+    if category_out is None:
+        category_out = torch.empty(B, dtype=torch.int64, device=dev)
+    draws = [None] * 6
+    if return_draws:
+        f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        draws = [f32(B), f32(B, N, 3), torch.empty(B, N, dtype=torch.int32, device=dev), f32(B), f32(B, 3), f32(B, 3)]
+    seed = 0 if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(lib().sug_prepare_seg_batch(_p(pts), _p(extra), _p(point_label), _p(category), _p(lengths), M, P, E, _p(idx), B, N,
+                                      stages, pre, _p(angles), _p(noise), _p(sel), _p(scales), _p(perturb), _p(shifts), seed,
+                                      _p(counter), sigma, clip, params, _p(out), _p(label_out), _p(category_out),
+                                      *[_p(d) for d in draws], _st()), 'sug_prepare_seg_batch')
+    return (out, category_out, label_out, *draws) if return_draws else (out, category_out, label_out)
+
+
 # ----------------------------------------------------------------------------- sub-domain splitter
 ICP_MAX_POINTS = _H['SUG_ICP_MAX_POINTS']
 
