@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -667,6 +667,39 @@ int64_t sug_pointmlp_max_bwd_workspace(int64_t rows, int K, int Co, int seg);
 int sug_pointmlp_max_bwd_sparse(const float* a, const int32_t* arg, const float* x, int64_t ldx, const float* w,
                                 int64_t rows, int K, int Co, int seg, float* dx, int64_t lddx, float* dw,
                                 float* ws, void* stream);
+
+/* ---- two-layer EdgeConv block --------------------------------------------------------------------
+ * The EdgeConv block with TWO 1x1 convolutions in front of the max over the k neighbours: the blocks of the DGCNN
+ * part-segmentation network, and transform_net's DGCNN form (model/model_utils.py:70-77).  With [P | Q] formed by the
+ * caller as for sug_edgeconv_fwd (bias on the Q half):
+ *   y1[b,i,j,c] = P[b, idx[b,i,j], c] + Q[b,i,c]                   one fp32 add
+ *   a1          = LeakyReLU_s1(scale1 * y1 + shift1)               BatchNorm 1 over all B*N*k values
+ *   y2[b,i,j,:] = a1[b,i,j,:] . w^T (+ bias)                       fp32 matrix pipe, ascending-k chain (sug_pointmlp_max_fwd)
+ *   out[b,i,c]  = LeakyReLU_s2(scale2 * ext_j y2 + shift2)         BatchNorm 2 over all B*N*k values
+ * ext = max_j where gamma2[c] >= 0, min_j where gamma2[c] < 0; arg = the lowest such j.  The edge feature [B,N,k,2C],
+ * y2 and a2 are never formed.  Statistics as sug_pointmlp_max_layer_fwd: sums about a pivot row, one fp32 partial row
+ * per workgroup in ws, folded in fp64 in a fixed order; no float atomics; training = 0 reads coef (caller fills it).
+ * sug_edgemlp_supported: 2 <= k <= 32, C1 == 64, Co in {64, 128}.
+ * sug_edge_expand_fwd: y1 [B,N,k,C1] (dense) and, training != 0, coef [5,C1] of BatchNorm 1 + its running-buffer
+ *   update; idx [B,N,k] entries are clamped into [0,N); ws: SUG_STATS_BLOCKS*2*C1 floats.
+ * sug_edgemlp_max_layer_fwd_xf: the short-segment sibling of sug_pointmlp_max_layer_fwd_xf, same arguments and
+ *   outputs (zext / arg [rows/seg, Co], coef [5,Co], out [rows/seg, Co] with row stride ldo, zout = a1 or null) for
+ *   segments of `seg` = k consecutive rows that do not line up with the 32-row tiles; any number of whole segments;
+ *   groups must be 1; ws: SUG_STATS_BLOCKS*2*Co floats.
+ * sug_edge_expand_bwd: dpq[b,m,0:C1) = sum of dy1 over the entries e = i*k + j with idx[b,i,j] == m in ascending e
+ *   (rev_off / rev_ent = sug_knn_reverse(idx)); dpq[b,i,C1:2C1) = sum_j dy1[b,i,j,:] in ascending j; dpq has row
+ *   stride lddpq; a point that no list names gets zeros; every row is written. */
+int sug_edgemlp_supported(int k, int C1, int Co);
+int sug_edge_expand_fwd(const float* pq, int64_t ldpq, const int32_t* idx, int B, int N, int k, int C1,
+                        const float* gamma, const float* beta, int training, float eps, float momentum,
+                        float* running_mean, float* running_var, float* y1, float* coef, float* ws, void* stream);
+int sug_edgemlp_max_layer_fwd_xf(const float* y, int64_t ldy, int64_t rows, int K, const float* xcoef, float xslope,
+                                 float* zout, int64_t ldz, const float* w, const float* bias, const float* gamma,
+                                 const float* beta, int Co, int seg, int groups, int training, float eps, float momentum,
+                                 float slope, float* running_mean, float* running_var, float* zext, int32_t* arg,
+                                 float* coef, float* out, int64_t ldo, float* ws, void* stream);
+int sug_edge_expand_bwd(const float* dy1, const int32_t* rev_off, const int32_t* rev_ent, int B, int N, int k, int C1,
+                        float* dpq, int64_t lddpq, void* stream);
 
 /* ---- Point Transformer vector attention (BASELINE config 5) --------------------------------------
  * The memory-bound parts of TransformerBlock.forward (model/Ptran_transformer.py:32-45) around the three

@@ -205,6 +205,18 @@ class transform_net(nn.Module):
             return self.rows_tail(y.squeeze(-1).transpose(1, 2))
         return self.rows(x.squeeze(-1).transpose(1, 2))
 
+    def edge_rows(self, x, idx):
+        """forward(get_graph_feature(x, idx=idx), DGCNN_Flag=True) on rows: x [B,N,C] with in_ch = 2C, idx [B,N,k] ->
+        [B,K,K].  conv2d1 + conv2d2 + the max over k are one two-layer EdgeConv block (ops.edgeconv2): neither the
+        [B,2C,N,k] edge feature nor conv2d2's [B,128,N,k] output is formed."""
+        c1, c2 = self.conv2d1, self.conv2d2
+        pq = ops.linear_rows(x, edge_wcats((c1,))[0])                    # [B,N,128] = [P | Q]
+        if c1.conv[0].bias is not None:                                   # bias rides on the Q half
+            pq = pq + torch.cat((torch.zeros_like(c1.conv[0].bias), c1.conv[0].bias))
+        y = ops.edgeconv2(pq, idx, c1.conv[1], _ACT_SLOPE[c1.activation], c2.weight2d(), c2.conv[0].bias, c2.conv[1],
+                          _ACT_SLOPE[c2.activation])
+        return self.rows_tail(y)
+
     def rows_tail(self, y):
         y = self.conv2d3.rows_max(y)
         y = self.fc3(self.fc2(self.fc1(y)))

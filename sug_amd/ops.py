@@ -1887,6 +1887,120 @@ def bn_act_pointmlp_max(y, bn1, slope1, weight, bias, bn2, slope2, seg, want_z=F
     return out, z
 
 
+# ----------------------------------------------------------------------------- two-layer EdgeConv block
+# The EdgeConv block with two 1x1 convolutions in front of the max over k (DGCNN part segmentation, transform_net's DGCNN
+# form): sug_edge_expand_fwd + sug_edgemlp_max_layer_fwd_xf.  SUG_EDGE2_FUSED=0 selects the composed form below (A/B).
+EDGE2_FUSED = _os.environ.get('SUG_EDGE2_FUSED', '1') != '0'
+
+
+def edgeconv2_supported(k, C1, Co):
+    return EDGE2_FUSED and bool(lib().sug_edgemlp_supported(int(k), int(C1), int(Co)))
+
+
+class _EdgeConv2(torch.autograd.Function):
+    """out [B,N,Co] = act2(BN2(ext_j (act1(BN1(P[idx] + Q)) . W^T + b))) from pq [B,N,2*C1] = [P | Q] and idx [B,N,k].
+    Forward: y1 written once with the BatchNorm-1 sums (sug_edge_expand_fwd); a1 formed on y1's way into LDS and written
+    once when a backward follows; y2 exists only as accumulator tiles (sug_edgemlp_max_layer_fwd_xf).  Backward = the
+    pieces of _BNActPointMLPMax unchanged -- _pointmlp_max_backward on (a1, gout) with seg = k, _bn_act_rows_backward
+    through BN1 -- then sug_edge_expand_bwd folds dY1 into [dP | dQ] over the reverse lists."""
+
+    @staticmethod
+    def forward(ctx, pq, idx, g1, be1, weight, bias, g2, be2, st1, slope1, st2, slope2, out_holder, grad_on):
+        _need_gpu(pq, idx, weight, g1, g2)
+        pq, B, N, C2, ld = _rows3(pq)
+        if ld % 4 or pq.data_ptr() % 16:
+            pq, ld = pq.contiguous(), C2
+        C1 = C2 // 2
+        idx = _i32(idx).contiguous()
+        k = idx.shape[2]
+        Co = weight.shape[0]
+        rows = B * N * k
+        dev = pq.device
+        L = lib()
+        training = st1.training
+        g1c, be1c, coef1 = _bn_params(g1, be1, st1, C1)
+        g2c, be2c, coef2 = _bn_params(g2, be2, st2, Co)
+        ws = _stats_ws(max(C1, Co), dev)
+        y1 = torch.empty(rows, C1, dtype=torch.float32, device=dev)
+        check(L.sug_edge_expand_fwd(_p(pq), ld, _p(idx), B, N, k, C1, _p(g1c), _p(be1c), st1.train, st1.eps, st1.momentum,
+                                    _p(st1.mean), _p(st1.var), _p(y1), _p(coef1), _p(ws), _st()), 'sug_edge_expand_fwd')
+        need_bwd = grad_on and any(ctx.needs_input_grad[i] for i in (0, 2, 3, 4, 5, 6, 7))
+        z = torch.empty(rows, C1, dtype=torch.float32, device=dev) if need_bwd else None
+        w2 = weight.detach().reshape(Co, C1).contiguous()
+        b1 = None if bias is None else bias.detach().contiguous()
+        zext = torch.empty(B * N, Co, dtype=torch.float32, device=dev)
+        arg = torch.empty(B * N, Co, dtype=torch.int32, device=dev)
+        out = _edgeconv_out(out_holder, B, N, Co, dev)
+        check(_timed('edgemlp_max_Co%d' % Co, {'B': B, 'N': N, 'k': k, 'Co': Co},
+                     lambda: L.sug_edgemlp_max_layer_fwd_xf(_p(y1), C1, rows, C1, _p(coef1), float(slope1), _p(z), C1, _p(w2),
+                                                            _p(b1), _p(g2c), _p(be2c), Co, k, 1, st2.train, st2.eps,
+                                                            st2.momentum, float(slope2), _p(st2.mean), _p(st2.var), _p(zext),
+                                                            _p(arg), _p(coef2), _p(out), out.stride(1), _p(ws), _st())),
+              'sug_edgemlp_max_layer_fwd_xf')
+        if need_bwd:
+            ctx.save_for_backward(idx, y1, coef1, z, w2, b1, zext, arg, coef2)
+            ctx.meta = (B, N, k, C1, Co, float(slope1), float(slope2), training, tuple(weight.shape))
+        ctx.need_bwd = need_bwd
+        ctx.mark_non_differentiable(coef1, coef2)
+        ctx.set_materialize_grads(False)
+        return out, coef1, coef2
+
+    @staticmethod
+    def backward(ctx, gout, _gcoef1, _gcoef2):
+        if gout is None or not ctx.need_bwd:
+            return (None,) * 14
+        idx, y1, coef1, z, w2, b1, zext, arg, coef2 = ctx.saved_tensors
+        B, N, k, C1, Co, slope1, slope2, training, wshape = ctx.meta
+        rows = B * N * k
+        gout = gout.reshape(B * N, Co)
+        dz, dw, db, dg2, db2 = _pointmlp_max_backward(gout, z, w2, b1, zext, arg, coef2, rows, C1, Co, k, 1, slope2, training)
+        dy1, dg1, db1 = _bn_act_rows_backward(dz, y1, coef1, rows, C1, slope1, training, 1)
+        dpq = None
+        if ctx.needs_input_grad[0]:
+            off, ent = knn_reverse(idx)
+            dpq = torch.empty(B, N, 2 * C1, dtype=torch.float32, device=gout.device)
+            check(lib().sug_edge_expand_bwd(_p(dy1), _p(off), _p(ent), B, N, k, C1, _p(dpq), 2 * C1, _st()), 'sug_edge_expand_bwd')
+        return (dpq, None, dg1, db1, dw.view(wshape), db, dg2, db2) + (None,) * 6
+
+
+def _edgeconv2_composed(pq, idx, bn1, slope1, weight, bias, bn2, slope2):
+    """The block from the single-layer ops, every k-expanded tensor stored: y1 (gather + add), a1, y2, a2, then torch.max."""
+    C1 = pq.shape[-1] // 2
+    y1 = gather_rows(pq[:, :, :C1], idx) + pq[:, :, C1:].unsqueeze(2)        # [B,N,k,C1]
+    a1 = bn_act_rows(y1, bn1, slope1)
+    a2 = bn_act_rows(linear_rows(a1, weight.reshape(weight.shape[0], C1), bias), bn2, slope2)
+    return a2.max(dim=2)[0]
+
+
+def edgeconv2(pq, idx, bn1, slope1, weight, bias, bn2, slope2, out=None):
+    """pq [B,N,2*C1] = x . [W1 ; W2-W1]^T (bias on the Q half, as conv_2d.edge_rows forms it), idx [B,N,k], bn1 / bn2
+    nn.BatchNorm modules, weight [Co, C1(,1,1)] -> [B,N,Co] = max over the k neighbours of
+    LeakyReLU_slope2(bn2(LeakyReLU_slope1(bn1(P[idx] + Q)) . W^T + b)).  out: a [B,N,Co] column slice to write into.
+    Shapes outside edgeconv2_supported (or SUG_EDGE2_FUSED=0) run the composed GPU form."""
+    _need_gpu(pq, idx, weight)
+    if bn1.training != bn2.training:
+        raise RuntimeError('edgeconv2: the two BatchNorm layers must be in the same mode (train / eval)')
+    if CTX.bn_groups != 1:
+        raise RuntimeError('edgeconv2: one domain group only (got bn_groups = %d)' % CTX.bn_groups)
+    if pq.dim() != 3 or idx.dim() != 3 or pq.shape[:2] != idx.shape[:2] or pq.shape[2] % 2 or \
+            weight.reshape(weight.shape[0], -1).shape[1] * 2 != pq.shape[2]:
+        raise RuntimeError('edgeconv2: pq [B,N,2*C1], idx [B,N,k], weight [Co,C1] (got %s, %s, %s)'
+                           % (tuple(pq.shape), tuple(idx.shape), tuple(weight.shape)))
+    if not edgeconv2_supported(idx.shape[2], pq.shape[2] // 2, weight.shape[0]):
+        res = _edgeconv2_composed(pq, idx, bn1, slope1, weight, bias, bn2, slope2)
+        if out is not None:
+            res = assemble_rows(out, (res,)) if out.shape == res.shape else res
+        return res
+    _count_bn_call(bn1)
+    _count_bn_call(bn2)
+    res, coef1, coef2 = _EdgeConv2.apply(pq, idx, bn1.weight, bn1.bias, weight, bias, bn2.weight, bn2.bias, _bn_state(bn1),
+                                         slope1, _bn_state(bn2), slope2, None if out is None else [out],
+                                         torch.is_grad_enabled())
+    _record_bn(bn1, coef1[0])
+    _record_bn(bn2, coef2[0])
+    return res
+
+
 # Step-scoped cache of 16-bit copies of weights / biases (opt-in: SUGStep sets a dict before the forwards of a step and
 # drops it after them).  Without it every call re-casts its operands: ~280 tiny launches per step at config 5.
 
