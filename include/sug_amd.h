@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 7
 int sug_abi_version(void);
 
@@ -61,7 +61,9 @@ int sug_knn(const float* x, int64_t ldx, int B, int N, int C, int k,
  * for every destination point m the entries e = n*k + j with idx[b,n,j] == m,
  * ascending in e.  rev_off: [B,N+1] (exclusive prefix, per cloud), rev_ent:
  * [B,N*k].  No reference counterpart (autograd's index_put_ does this
- * implicitly, model/model_utils.py:204). */
+ * implicitly, model/model_utils.py:204).  The LDS-resident build of
+ * sug_reverse_lists_build where that takes B clouds of N*k entries, else
+ * sug_reverse_lists_tiled with its own choice of tile (same lists). */
 int sug_knn_reverse(const int32_t* idx, int B, int N, int k,
                     int32_t* rev_off, int32_t* rev_ent, void* stream);
 
@@ -73,6 +75,23 @@ int sug_knn_reverse(const int32_t* idx, int B, int N, int k,
  * everything in LDS: fails with SUG_ERR_ARG, launching nothing, when 4 * (2 * ceil(N / R) + 32 + E) exceeds 160 KB,
  * R the destination ranges per cloud (doubled from 1 while R < 8, B * R < 256 and N / (2 R) >= 64). */
 int sug_reverse_lists_build(const int32_t* idx, int B, int E, int N, int sorted,
+                            int32_t* rev_off, int32_t* rev_ent, void* stream);
+
+/* The same lists, to the same contract (ascending (destination, e) order, rev_off the exclusive prefix, rev_off[b,N] the
+ * valid count, destinations outside [0,N) skipped, rev_ent behind the valid count and everything outside the two arrays
+ * not written), for clouds beyond the LDS-resident build: N <= SUG_REV_TILED_MAX_DEST destinations and
+ * E <= SUG_REV_TILED_MAX_ENTRIES entries per cloud.  A workgroup owns a destination range of one cloud and streams the
+ * cloud's entries through LDS in tiles, twice (counts, then a stable placement at one running cursor per destination):
+ * one launch, no workspace, no atomics on global memory, no host wait (capturable), the same integers run to run.
+ * tile: the entries of a cloud one streaming step holds; 0 = the library's choice (the cloud rounded up to 1024, at most
+ * SUG_REV_TILED_MAX_TILE), else a multiple of 1024 in [1024, SUG_REV_TILED_MAX_TILE], taken as given.  SUG_ERR_ARG,
+ * launching nothing, for a null pointer, a shape outside the limits or another tile.
+ * sug_reverse_lists_tiled_supported: 1 for B > 0 clouds inside the two limits, else 0. */
+#define SUG_REV_TILED_MAX_DEST 32768
+#define SUG_REV_TILED_MAX_ENTRIES 2097152
+#define SUG_REV_TILED_MAX_TILE 20480
+int sug_reverse_lists_tiled_supported(int B, int E, int N);
+int sug_reverse_lists_tiled(const int32_t* idx, int B, int E, int N, int tile,
                             int32_t* rev_off, int32_t* rev_ent, void* stream);
 
 /* ---- farthest point sampling -------------------------------------------

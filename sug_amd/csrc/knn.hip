@@ -440,5 +440,11 @@ extern "C" int sug_reverse_lists_build(const int32_t* idx, int B, int E, int N, 
 extern "C" int sug_knn_reverse(const int32_t* idx, int B, int N, int k, int32_t* rev_off,
                                int32_t* rev_ent, void* stream) {
   SUG_REQUIRE(B > 0 && N > 0 && k > 0, "sug_knn_reverse: bad shape");
-  return sug_reverse_lists(idx, B, N * k, N, 1, rev_off, rev_ent, (hipStream_t)stream);
+  const int64_t E = (int64_t)N * k;
+  // the LDS-resident build where it takes the shape (what it launches does not change), the tiled build behind it
+  if (E <= 40 * REV_BLOCK && sug_reverse_lists_lds_bytes(B, (int)E, N, nullptr) <= 160 * 1024)
+    return sug_reverse_lists(idx, B, (int)E, N, 1, rev_off, rev_ent, (hipStream_t)stream);
+  SUG_REQUIRE(E <= SUG_REV_TILED_MAX_ENTRIES, "sug_knn_reverse: N * k = %lld entries per cloud exceed SUG_REV_TILED_MAX_ENTRIES=%d",
+              (long long)E, SUG_REV_TILED_MAX_ENTRIES);
+  return sug_reverse_lists_tiled(idx, B, (int)E, N, 0, rev_off, rev_ent, stream);
 }

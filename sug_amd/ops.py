@@ -249,6 +249,27 @@ def reverse_lists(idx, n_dest, sorted=True, ent=None):
     return off, ent
 
 
+def reverse_lists_tiled_supported(B, E, N):
+    """Does the tiled reverse-list build take B clouds of E entries into N destinations (N <= SUG_REV_TILED_MAX_DEST,
+    E <= SUG_REV_TILED_MAX_ENTRIES)?"""
+    return bool(lib().sug_reverse_lists_tiled_supported(B, E, N))
+
+
+def reverse_lists_tiled(idx, n_dest, tile=0, ent=None):
+    """The lists of reverse_lists for clouds of any size within reverse_lists_tiled_supported, by the build that streams
+    a cloud's entries through LDS in tiles of `tile` entries (0: the library's choice, else a multiple of 1024 up to
+    SUG_REV_TILED_MAX_TILE, taken as given): sug_reverse_lists_tiled.  `ent` as in reverse_lists."""
+    _need_gpu(idx)
+    idx = _i32(idx).contiguous()
+    B, E = idx.shape
+    off = torch.empty(B, n_dest + 1, dtype=torch.int32, device=idx.device)
+    if ent is None:
+        ent = torch.empty(B, E, dtype=torch.int32, device=idx.device)
+    assert ent.shape == (B, E) and ent.dtype == torch.int32 and ent.is_contiguous() and ent.device == idx.device
+    check(lib().sug_reverse_lists_tiled(_p(idx), B, E, n_dest, tile, _p(off), _p(ent), _st()), 'sug_reverse_lists_tiled')
+    return off, ent
+
+
 def fps(xyz, npoint, start):
     """xyz [B,N,3], start [B] (any int dtype/device) -> [B,npoint] int32."""
     _need_gpu(xyz)
@@ -1963,10 +1984,39 @@ class _EdgeConv2(torch.autograd.Function):
         return (dpq, None, dg1, db1, dw.view(wshape), db, dg2, db2) + (None,) * 6
 
 
+class _EdgeExpandLists(torch.autograd.Function):
+    """y1 = P[idx] + Q of the composed block for lists with more entries per cloud than the ordered scatter behind
+    gather_rows' backward takes (sug_scatter_rows_ordered_supported): the same forward; the backward over sug_knn_reverse's
+    lists (sug_edge_expand_bwd: one fixed order, the same bits run to run) where gather_rows would add with atomics."""
+
+    @staticmethod
+    def forward(ctx, pq, idx):
+        C1 = pq.shape[-1] // 2
+        idx = _i32(idx).contiguous()
+        ctx.save_for_backward(idx)
+        ctx.shape = (pq.shape[0], pq.shape[1], C1)
+        return gather_rows(pq[:, :, :C1], idx) + pq[:, :, C1:].unsqueeze(2)
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        B, N, C1 = ctx.shape
+        g = g.contiguous()
+        off, ent = knn_reverse(idx)
+        dpq = torch.empty(B, N, 2 * C1, dtype=torch.float32, device=g.device)
+        check(lib().sug_edge_expand_bwd(_p(g), _p(off), _p(ent), B, N, idx.shape[2], C1, _p(dpq), 2 * C1, _st()),
+              'sug_edge_expand_bwd')
+        return dpq, None
+
+
 def _edgeconv2_composed(pq, idx, bn1, slope1, weight, bias, bn2, slope2):
     """The block from the single-layer ops, every k-expanded tensor stored: y1 (gather + add), a1, y2, a2, then torch.max."""
-    C1 = pq.shape[-1] // 2
-    y1 = gather_rows(pq[:, :, :C1], idx) + pq[:, :, C1:].unsqueeze(2)        # [B,N,k,C1]
+    B, N, C1 = pq.shape[0], pq.shape[1], pq.shape[-1] // 2
+    k = idx.shape[2]
+    if SCATTER_ORDERED and C1 == 64 and k <= 32 and not lib().sug_scatter_rows_ordered_supported(B, N, N * k):
+        y1 = _EdgeExpandLists.apply(pq, idx)
+    else:
+        y1 = gather_rows(pq[:, :, :C1], idx) + pq[:, :, C1:].unsqueeze(2)    # [B,N,k,C1]
     a1 = bn_act_rows(y1, bn1, slope1)
     a2 = bn_act_rows(linear_rows(a1, weight.reshape(weight.shape[0], C1), bias), bn2, slope2)
     return a2.max(dim=2)[0]

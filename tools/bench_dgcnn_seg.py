@@ -8,6 +8,11 @@ with every round reported (the spread is max - min of the rounds).
   pn2_step  for context: one SegStep(Pointnet2PartSeg) on the same batch
 
     python tools/bench_dgcnn_seg.py [--iters 25] [--warmup 3] [--out profiles/dgcnn_seg_bench.json]
+    python tools/bench_dgcnn_seg.py --npoints 2048 --out profiles/dgcnn_seg_bench.json
+
+--npoints N (other than 1024) measures seg_step alone at B = 32 * 1024 / N clouds of N points, the same edge count, and adds
+it to the file as `seg_step_n<N>` beside the rows that are there.  At N = 2048 the backward's reverse lists (40 960 entries
+per cloud) come from the tiled build behind sug_knn_reverse.
 
 Launches are counted with torch.profiler over one call of each path (kernel events; null where the profiler is unavailable).
 Edge-sized traffic of the block, counted from the code (nobody measured it): one edge-sized tensor = B N k 64 floats =
@@ -24,8 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
-# 32 clouds of 1024 points: the edge count of 16 x 2048 (655 360 rows).  N = 2048 with k = 20 is 40 960 entries per cloud, past
-# what sug_knn_reverse builds in LDS (about 40 400 at N = 2048), and every EdgeConv backward in the tree takes its lists.
+# 32 clouds of 1024 points: the edge count of 16 x 2048 (655 360 rows), the size --npoints 2048 measures.
 B, N, K, C1 = 32, 1024, 20, 64
 PARTS, CATS = 50, 16
 ROUNDS = 5
@@ -106,7 +110,7 @@ def bench_block(a):
     return res
 
 
-def _batch():
+def _batch(B=B, N=N):
     import pn2_msg_fp_cases as PC
     pts = PC.clouds(0, N, batch=B).cuda()
     g = torch.Generator().manual_seed(2)
@@ -115,10 +119,10 @@ def _batch():
     return pts, cat, lab
 
 
-def bench_step(a):
+def bench_step(a, B=B, N=N):
     from sug_amd.model.dgcnn_seg import DGCNNPartSeg
     from sug_amd.seg_step import SegStep
-    pts, cat, lab = _batch()
+    pts, cat, lab = _batch(B, N)
     steps = []
     for _ in range(2):
         torch.manual_seed(0)
@@ -144,8 +148,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=25)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--npoints', type=int, default=N)
     ap.add_argument('--out')
     a = ap.parse_args()
+    if a.npoints != N:
+        if a.npoints < K or (B * N) % a.npoints:
+            ap.error('--npoints must divide %d and be at least k = %d' % (B * N, K))
+        res = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}
+        res['seg_step_n%d' % a.npoints] = bench_step(a, B * N // a.npoints, a.npoints)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            json.dump(res, open(a.out, 'w'), indent=1)
+        print(json.dumps(res['seg_step_n%d' % a.npoints]))
+        return
     res = {'workload': 'DGCNN part segmentation: two-layer EdgeConv block and SegStep, fused vs composed, same tree',
            'block': bench_block(a), 'seg_step': bench_step(a), 'pn2_step': bench_pn2(a)}
     if a.out:
