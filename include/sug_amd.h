@@ -44,8 +44,8 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
-#define SUG_ABI_VERSION 7
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added; 8: the KPConv entry points keep one row layout -- the eight sug_*_cap twins are gone, sug_grid_subsample takes C, level and the nullable record, sug_kpconv_fwd takes nq_valid, sug_seg_instnorm_fwd / _bwd take N). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+#define SUG_ABI_VERSION 8
 int sug_abi_version(void);
 
 /* ---- kNN graph ----------------------------------------------------------
@@ -1161,81 +1161,68 @@ int sug_part_iou_accumulate(const float* logits, const int64_t* label, const int
 
 
 /* ---- KPConv backbone (model/KPConv_model.py, model/KPConv_blocks.py; rigid kernel points, linear influence, sum) ----
- * Clouds are packed: level points [sum N_b, 3] with device offsets off[B+1] (int32).  A neighbour table [Nq, H] holds
- * global support indices, a missing slot the shadow index Ns.  No float atomics: every sum has one fixed order.
+ * Row layout: clouds are packed.  Level l owns a buffer of C_l rows; rows [0, off[B]) are valid -- the clouds back to back
+ * at the device offsets off[B+1] (int32) -- and rows [off[B], C_l) are dead.  A neighbour table [Cq, H] holds global
+ * support indices, a missing slot the shadow index Cs (the rows of the support buffer).  No float atomics: every sum has
+ * one fixed order.  Invariants:
+ *   1. every dead row of every level tensor is exactly zero (coordinates, activations, and the gradients of both);
+ *   2. a dead query's table row is all shadow;
+ *   3. a dead support's reverse list is empty;
+ *   4. every function reads the valid counts from device memory, never reads a dead input row, and writes zeros to the
+ *      dead rows of its outputs;
+ *   5. no buffer, grid or host branch depends on a value in device memory: a launch sequence is static (a graph-capturable
+ *      pyramid).
+ * Exact sizes are the case with no dead rows, C_l == off[B]: 1. to 4. hold trivially.  sug_kpconv_bwd,
+ * sug_seg_max_pool_fwd and sug_seg_max_pool_bwd need nothing beyond 2. and 3. (Nq / Ns = the row counts).
  *
  * sug_grid_subsample: per cloud, the voxels floor(p / dl) (fp32 true division) in order of their first point, each the
  * fp32 point-order sum of its points divided once by the count.  out_pad [B, cap, 3] and cnt [B] are scratch / counts,
- * out [<= sum N_b, 3] the packed result with offsets out_off [B+1].  cap >= every input cloud's length,
- * cap <= SUG_KPCONV_MAX_CLOUD. */
+ * out [C, 3] the packed result with offsets out_off [B+1], C <= B*cap.  cap >= every input cloud's length,
+ * cap <= SUG_KPCONV_MAX_CLOUD.  out_off is clamped to C (the rows past C are dropped) and the dead rows of out are zeroed.
+ * record (may be null; then level is not looked at): int32 [SUG_KPCONV_RECORD_INTS], zeroed by the caller once, into
+ * which the unclamped total is folded: record[level] = max(record[level], total), level in [0, 4); record[4] = forwards in
+ * which any level overflowed (counted once per forward; the level-0 call opens a forward), record[5] = scratch. */
 #define SUG_KPCONV_MAX_CLOUD 4096
-int sug_grid_subsample(const float* pts, const int32_t* off, int B, int cap, float dl, float* out_pad, int32_t* cnt,
-                       float* out, int32_t* out_off, void* stream);
+#define SUG_KPCONV_RECORD_INTS 8
+int sug_grid_subsample(const float* pts, const int32_t* off, int B, int cap, float dl, int C, int level, float* out_pad,
+                       int32_t* cnt, float* out, int32_t* out_off, int32_t* record, void* stream);
 /* out [Nq, limit]: per query the first `limit` supports of its cloud, in support order, with d^2 < radius^2
- * (d^2 = (s-q)_x^2 + (s-q)_y^2 + (s-q)_z^2 in fp32, left to right); the rest Ns.  limit <= 64. */
+ * (d^2 = (s-q)_x^2 + (s-q)_y^2 + (s-q)_z^2 in fp32, left to right); the rest, and a dead query's whole row, Ns.
+ * Nq / Ns: the rows of q / s.  limit <= 64. */
 int sug_radius_neighbors(const float* q, const int32_t* qoff, int Nq, const float* s, const int32_t* soff, int Ns, int B,
                          float radius, int limit, int32_t* out, void* stream);
 /* Reverse lists of a neighbour table: the entries e = q*H + h naming support s, ascending, are
- * rev_ent[rev_be[2s] .. rev_be[2s+1]); rev_ent [Nq*H] (cloud b's lists lie in [qoff[b]*H, qoff[b+1]*H)), rev_be [Ns, 2].
- * Shadow slots appear in no list.  cap >= every cloud's support count, <= SUG_KPCONV_MAX_CLOUD. */
+ * rev_ent[rev_be[2s] .. rev_be[2s+1]); rev_ent [Nq*H] (cloud b's lists lie in [qoff[b]*H, qoff[b+1]*H)), rev_be [Ns, 2]:
+ * (0, 0) for the dead supports [soff[B], Ns).  Shadow slots appear in no list.  cap >= every cloud's support count,
+ * <= SUG_KPCONV_MAX_CLOUD. */
 int sug_radius_reverse(const int32_t* nbr, const int32_t* qoff, const int32_t* soff, int B, int H, int Ns, int cap,
                        int32_t* rev_be, int32_t* rev_ent, void* stream);
 /* wf [Nq, K*Cin] = (sum_h w[q,k,h] x[s_h, :]) / cnt[q] with w = max(0, 1 - |(s_h - q) - kp_k| / extent) (shadow: 0) and
  * cnt = max(1, #{h : sum_c x[s_h, c] > 0}); the layer output is wf . W viewed as [K*Cin, Cout].  Also written for the
- * backward: w [Nq, H, K], cnt [Nq] (fp32).  H <= 64, K <= 16. */
-int sug_kpconv_fwd(const float* q, const float* s, const int32_t* nbr, int Nq, int H, int Ns, const float* kp, int K,
-                   float extent, const float* x, int Cin, float* wf, float* w, float* cnt, void* stream);
+ * backward: w [Nq, H, K], cnt [Nq] (fp32).  nq_valid: device pointer to the number of valid queries (qoff + B), never
+ * null; dead rows: wf = 0, w = 0, cnt = 1.  H <= 64, K <= 16. */
+int sug_kpconv_fwd(const float* q, const float* s, const int32_t* nbr, const int32_t* nq_valid, int Nq, int H, int Ns,
+                   const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w, float* cnt,
+                   void* stream);
 /* dx [Ns, Cin] = sum over the reverse entries (q, h) of s, ascending, of (sum_k w[q,h,k] dwf[q,k,:]) / cnt[q] */
 int sug_kpconv_bwd(const int32_t* rev_be, const int32_t* rev_ent, int H, int K, const float* w, const float* cnt,
                    const float* dwf, int Ns, int Cin, float* dx, void* stream);
-/* Per-cloud InstanceNorm1d (biased variance, no affine) over the rows of each cloud, x / y [N, C]; mode 0: plain,
- * 1: LeakyReLU(0.1) after it, 2: LeakyReLU(0.1)(norm + sc).  mean / rstd [B, C] are kept for the backward, which
- * writes dx and, in mode 2, dsc (the gradient of sc). */
-int sug_seg_instnorm_fwd(const float* x, const int32_t* off, int B, int C, float eps, int mode, const float* sc, float* y,
-                         float* mean, float* rstd, void* stream);
+/* Per-cloud InstanceNorm1d (biased variance, no affine) over the rows of each cloud, x / y / dx / dsc [N, C]; mode 0:
+ * plain, 1: LeakyReLU(0.1) after it, 2: LeakyReLU(0.1)(norm + sc).  mean / rstd [B, C] are kept for the backward, which
+ * writes dx and, in mode 2, dsc (the gradient of sc).  An empty cloud: mean = rstd = 0, nothing normalised. */
+int sug_seg_instnorm_fwd(const float* x, const int32_t* off, int B, int N, int C, float eps, int mode, const float* sc,
+                         float* y, float* mean, float* rstd, void* stream);
 int sug_seg_instnorm_bwd(const float* g, const float* y, const float* x, const float* mean, const float* rstd,
-                         const int32_t* off, int B, int C, int mode, float* dx, float* dsc, void* stream);
+                         const int32_t* off, int B, int N, int C, int mode, float* dx, float* dsc, void* stream);
 /* y [Nq, C] = max over the H slots of x[slot] (a shadow slot reads 0), arg = the first slot h holding it; the backward
  * routes g[q, c] to the support of slot arg[q, c] through the reverse lists (a shadow winner: nowhere). */
 int sug_seg_max_pool_fwd(const float* x, const int32_t* nbr, int Nq, int H, int Ns, int C, float* y, int32_t* arg,
                          void* stream);
 int sug_seg_max_pool_bwd(const float* g, const int32_t* arg, const int32_t* rev_be, const int32_t* rev_ent, int H, int Ns,
                          int C, float* dx, void* stream);
-/* y [B, C] = per-cloud mean of x [N, C]; dx [N, C] = g[b] / N_b */
+/* y [B, C] = per-cloud mean of x [N, C], an empty cloud's row 0; dx [N, C] = g[b] / N_b, rows >= off[B] = 0 */
 int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C, float* y, void* stream);
 int sug_seg_mean_bwd(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream);
-/* Capacity forms (a graph-capturable pyramid): level l owns a buffer of a static number of rows C_l; rows [0, off[B])
- * are valid, rows [off[B], C_l) are dead and exactly zero in every level tensor; the shadow index of a table is the
- * capacity of its support level; a dead query's table row is all shadow, a dead support's reverse list is empty.  Every
- * function reads the valid counts from device memory, never reads a dead input row, and writes zeros to the dead rows of
- * its outputs.  sug_kpconv_bwd, sug_seg_max_pool_fwd and sug_seg_max_pool_bwd serve this layout as they are (Nq / Ns =
- * the capacities).
- *
- * sug_grid_subsample_cap: sug_grid_subsample into out [C, 3], C <= B*cap.  out_off is clamped to C (the rows past C are
- * dropped), the dead rows of out are zeroed, and the unclamped total is folded into record (int32
- * [SUG_KPCONV_RECORD_INTS], zeroed by the caller once): record[level] = max(record[level], total), record[4] = forwards in
- * which any level overflowed (counted once per forward; the level-0 call opens a forward), record[5] = scratch. */
-#define SUG_KPCONV_RECORD_INTS 8
-int sug_grid_subsample_cap(const float* pts, const int32_t* off, int B, int cap, float dl, int C, int level, float* out_pad,
-                           int32_t* cnt, float* out, int32_t* out_off, int32_t* record, void* stream);
-/* out [Cq, limit]; a dead query (row >= qoff[B]) gets an all-shadow row, the shadow index is Cs */
-int sug_radius_neighbors_cap(const float* q, const int32_t* qoff, int Cq, const float* s, const int32_t* soff, int Cs, int B,
-                             float radius, int limit, int32_t* out, void* stream);
-/* rev_be [Cs, 2]: (0, 0) for the dead supports [soff[B], Cs); cap >= every cloud's support count (the level-0 cloud size) */
-int sug_radius_reverse_cap(const int32_t* nbr, const int32_t* qoff, const int32_t* soff, int B, int H, int Cs, int cap,
-                           int32_t* rev_be, int32_t* rev_ent, void* stream);
-/* nq_valid: device pointer to the number of valid queries (qoff + B); dead rows: wf = 0, w = 0, cnt = 1 */
-int sug_kpconv_fwd_cap(const float* q, const float* s, const int32_t* nbr, const int32_t* nq_valid, int Cq, int H, int Cs,
-                       const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w, float* cnt,
-                       void* stream);
-/* x / y / dx / dsc [N, C], N the capacity; an empty cloud: mean = rstd = 0, nothing normalised */
-int sug_seg_instnorm_fwd_cap(const float* x, const int32_t* off, int B, int N, int C, float eps, int mode, const float* sc,
-                             float* y, float* mean, float* rstd, void* stream);
-int sug_seg_instnorm_bwd_cap(const float* g, const float* y, const float* x, const float* mean, const float* rstd,
-                             const int32_t* off, int B, int N, int C, int mode, float* dx, float* dsc, void* stream);
-/* an empty cloud: y row = 0; dx rows >= off[B] = 0 */
-int sug_seg_mean_fwd_cap(const float* x, const int32_t* off, int B, int C, float* y, void* stream);
-int sug_seg_mean_bwd_cap(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream);
 /* sample_tensor_slices (model/KPConv_blocks.py:159-176) from device offsets: out [B, S, D], out[b, j] = x[off[b] + i],
  * i = j * (n / S) for n = off[b+1] - off[b] >= S, j mod n below that, zeros for n = 0.  Forward only. */
 int sug_kp_sample_rows(const float* x, const int32_t* off, int B, int S, int D, float* out, void* stream);

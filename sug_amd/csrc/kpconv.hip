@@ -2,14 +2,11 @@
 // neighbours and their reverse lists) and the rigid / linear-influence / sum-aggregation kernel point convolution with
 // the per-cloud instance norm, max pooling and global average around it.
 //
-// Clouds are PACKED: level-l points [sum N_b, 3] with device offsets off[B+1].  Neighbour tables [Nq, H] hold global
-// support indices; a missing slot holds the shadow index Ns (the number of supports), as the reference pads them.
-// Every reduction has one fixed order, no float atomics: the backward scatters go through the sorted reverse lists of
-// sug_radius_reverse, so the backbone is reproducible bit for bit from run to run.
-//
-// CAPACITY LAYOUT (the sug_*_cap entry points).  Level l owns a buffer of a static number of rows
-// C_l (C_0 = B*N, C_l = min(C_{l-1}, 64*ceil(B*caps[l-1]/64))); rows [0, off[B]) are valid, rows [off[B], C_l) are dead.
-// The shadow index of a table is the CAPACITY of its support level, a constant of the launch sequence.  Invariants:
+// ROW LAYOUT.  Clouds are PACKED: level l owns a buffer of C_l rows, of which rows [0, off[B]) are
+// valid -- the clouds back to back at the device offsets off[B+1] -- and rows [off[B], C_l) are dead.  Neighbour tables
+// [C_q, H] hold global support indices; a missing slot holds the shadow index, the row count C_s of the support buffer (as
+// the reference pads them).  Every reduction has one fixed order, no float atomics: the backward scatters go through the
+// sorted reverse lists of sug_radius_reverse, so the backbone is reproducible bit for bit from run to run.  Invariants:
 //   1. every dead row of every level tensor is exactly zero: coordinates, activations, and the gradients of both;
 //   2. every slot of a dead query's table row is the shadow index;
 //   3. the reverse list of a dead support is empty (lo == hi);
@@ -17,13 +14,15 @@
 //      forward and backward.  The library GEMMs run on all C_l rows; their weight gradients stay right because the
 //      dead rows of both operands are zero (a NaN in a dead row would poison dW);
 //   5. no buffer, no grid and no host branch depends on a value in device memory, and nothing is copied to the host.
-// The kernels take the valid count from device memory (off[B], by pointer) and the capacity by value; the kernel bodies
-// are shared with the exact-size path (template<bool CAPS>).  sug_kpconv_bwd, sug_seg_max_pool_fwd and
-// sug_seg_max_pool_bwd hold under 2. and 3. as they are (Ns / Nq = the capacities): a dead support's empty list sums
-// to 0, a dead query's all-shadow row reads only the zero shadow, so they have no capacity twin.
+// The kernels take the valid count from device memory (off[B], by pointer) and the row count by value.  EXACT SIZES are
+// the case C_l == off[B]: no dead rows, so 1. to 4. hold trivially and the dead-row branches below run over nothing (the
+// exact-size pyramid gives up 5.: it reads the level totals once to slice its buffers).  With level caps C_0 = B*N and
+// C_l = min(C_{l-1}, 64*ceil(B*caps[l-1]/64)) are constants of the launch sequence.  sug_kpconv_bwd,
+// sug_seg_max_pool_fwd and sug_seg_max_pool_bwd hold under 2. and 3. as they are: a dead support's empty list sums to 0,
+// a dead query's all-shadow row reads only the zero shadow.
 // Overflow (a level total above C_l): the pack step clamps the offsets to C_l and drops the rows past it -- the tail of
 // the last clouds, a cloud may become empty (an empty cloud normalises nothing; its mean row and pooled feature are 0).
-// The unclamped total is folded into a small device record (sug_grid_subsample_cap).
+// The unclamped total is folded into a small device record (sug_grid_subsample).
 #include "common.h"
 
 namespace {
@@ -126,32 +125,13 @@ __global__ void __launch_bounds__(SUB_BLOCK) grid_subsample_kernel(const float* 
   if (threadIdx.x == 0) cnt[b] = nv;
 }
 
-// padded [B, cap, 3] -> packed rows, offsets from the counts (out_off [B+1])
-__global__ void pack_kernel(const float* __restrict__ pad, int cap, const int32_t* __restrict__ cnt, int B,
-                            float* __restrict__ out, int32_t* __restrict__ out_off) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < B * cap) {
-    const int b = t / cap, i = t - b * cap;
-    if (i < cnt[b]) {
-      int o = 0;
-      for (int j = 0; j < b; ++j) o += cnt[j];
-      for (int a = 0; a < 3; ++a) out[(size_t)(o + i) * 3 + a] = pad[(size_t)t * 3 + a];
-    }
-  }
-  if (t == 0) {
-    int o = 0;
-    out_off[0] = 0;
-    for (int j = 0; j < B; ++j) out_off[j + 1] = (o += cnt[j]);
-  }
-}
-
-// Capacity form of pack_kernel: out has C rows.  Offsets are clamped to C (rows past C are dropped), the dead rows
-// [min(total, C), C) are zero-filled, and the unclamped total is folded into rec (int32 [SUG_KPCONV_RECORD_INTS]):
-// rec[level] = max(rec[level], total); rec[4] counts the forwards with an overflow at any level (rec[5] = this forward
-// has been counted; cleared by the level-0 call) -- one lane, plain stores.  Grid covers max(B*cap, C) threads.
-__global__ void pack_cap_kernel(const float* __restrict__ pad, int cap, const int32_t* __restrict__ cnt, int B, int C,
-                                float* __restrict__ out, int32_t* __restrict__ out_off, int32_t* __restrict__ rec,
-                                int level) {
+// padded [B, cap, 3] -> packed rows of out [C, 3], offsets from the counts (out_off [B+1]).  Offsets are clamped to C (rows
+// past C are dropped) and the dead rows [min(total, C), C) are zero-filled.  With a record rec (int32
+// [SUG_KPCONV_RECORD_INTS]; may be null) the unclamped total is folded into it: rec[level] = max(rec[level], total);
+// rec[4] counts the forwards with an overflow at any level (rec[5] = this forward has been counted; cleared by the
+// level-0 call) -- one lane, plain stores.  Grid covers B*cap >= C threads.
+__global__ void pack_kernel(const float* __restrict__ pad, int cap, const int32_t* __restrict__ cnt, int B, int C,
+                            float* __restrict__ out, int32_t* __restrict__ out_off, int32_t* __restrict__ rec, int level) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < B * cap) {
     const int b = t / cap, i = t - b * cap;
@@ -172,19 +152,20 @@ __global__ void pack_cap_kernel(const float* __restrict__ pad, int cap, const in
     int o = 0;
     out_off[0] = 0;
     for (int j = 0; j < B; ++j) out_off[j + 1] = min(o += cnt[j], C);
-    if (o > rec[level]) rec[level] = o;
-    int counted = level == 0 ? 0 : rec[5];
-    if (o > C && !counted) {
-      rec[4] += 1;
-      counted = 1;
+    if (rec) {
+      if (o > rec[level]) rec[level] = o;
+      int counted = level == 0 ? 0 : rec[5];
+      if (o > C && !counted) {
+        rec[4] += 1;
+        counted = 1;
+      }
+      rec[5] = counted;
     }
-    rec[5] = counted;
   }
 }
 
 // One query per thread: the first `limit` supports of its cloud, in support order, with d^2 < r^2; shadow-padded.
-// CAPS: Nq / Ns are capacities; a dead query (i >= qoff[B]) gets an all-shadow row and reads nothing.
-template <bool CAPS>
+// A dead query (i >= qoff[B]) gets an all-shadow row and reads nothing.
 __global__ void radius_kernel(const float* __restrict__ q, const int32_t* __restrict__ qoff, const float* __restrict__ s,
                               const int32_t* __restrict__ soff, int B, int Nq, int Ns, float r2, int limit,
                               int32_t* __restrict__ out) {
@@ -192,7 +173,7 @@ __global__ void radius_kernel(const float* __restrict__ q, const int32_t* __rest
   if (i >= Nq) return;
   int32_t* o = out + (size_t)i * limit;
   int m = 0;
-  if (CAPS && i >= qoff[B]) {
+  if (i >= qoff[B]) {
     for (; m < limit; ++m) o[m] = Ns;
     return;
   }
@@ -210,8 +191,7 @@ __global__ void radius_kernel(const float* __restrict__ q, const int32_t* __rest
 
 // One cloud per workgroup: the entries e = q*H + h of the cloud's queries that name support s, ascending, at
 // rev_ent[rev_be[s][0] .. rev_be[s][1]) (inside the cloud's own range [q0*H, q1*H) of rev_ent).
-// CAPS: one more workgroup (blockIdx.x == B) gives the dead supports [soff[B], Ns) their empty lists.
-template <bool CAPS>
+// One more workgroup (blockIdx.x == B) gives the dead supports [soff[B], Ns) their empty lists.
 __global__ void __launch_bounds__(SUB_BLOCK) radius_reverse_kernel(const int32_t* __restrict__ nbr,
                                                                    const int32_t* __restrict__ qoff,
                                                                    const int32_t* __restrict__ soff, int H, int Ns,
@@ -222,7 +202,7 @@ __global__ void __launch_bounds__(SUB_BLOCK) radius_reverse_kernel(const int32_t
   int* cur = cnt + cap;
   int* part = cur + cap;
   const int b = blockIdx.x;
-  if (CAPS && b == (int)gridDim.x - 1) {      // uniform: before the first barrier
+  if (b == (int)gridDim.x - 1) {      // uniform: before the first barrier
     for (int i = soff[b] + threadIdx.x; i < Ns; i += SUB_BLOCK) rev_be[(size_t)i * 2] = rev_be[(size_t)i * 2 + 1] = 0;
     return;
   }
@@ -269,8 +249,7 @@ __global__ void __launch_bounds__(SUB_BLOCK) radius_reverse_kernel(const int32_t
 // w[k,h] = max(0, 1 - |(s_h - q) - kp_k| / extent) into LDS and out to w_out [Nq, H, K]; the positive-sum flags of the
 // neighbour rows.  Phase 2 (threads over QB x Cin): wf[q, k, c] = sum_h w[k,h] x[s_h, c], divided by
 // max(1, #positive rows); written as [Nq, K*Cin] for the GEMM against W viewed as [K*Cin, Cout].
-// CAPS: Nq / Ns are capacities, *nq_valid the valid queries; dead queries get zero wf / w rows and cnt 1.
-template <bool CAPS>
+// *nq_valid: the valid queries of the Nq; dead queries get zero wf / w rows and cnt 1.
 __global__ void __launch_bounds__(256) kpconv_fwd_kernel(const float* __restrict__ q, const float* __restrict__ s,
                                                          const int32_t* __restrict__ nbr,
                                                          const int32_t* __restrict__ nq_valid, int Nq, int H, int Ns,
@@ -282,8 +261,8 @@ __global__ void __launch_bounds__(256) kpconv_fwd_kernel(const float* __restrict
   __shared__ int pos[KP_QB][KP_MAX_H];
   __shared__ float cnt[KP_QB];
   const int qb0 = blockIdx.x * KP_QB;
-  const int nv = CAPS ? min(*nq_valid, Nq) : Nq;
-  if (CAPS && qb0 >= nv) {      // a wholly dead tile (blockIdx and a uniform load only): zeros, before the first barrier
+  const int nv = min(*nq_valid, Nq);
+  if (qb0 >= nv) {      // a wholly dead tile (blockIdx and a uniform load only): zeros, before the first barrier
     const int rows = min(KP_QB, Nq - qb0);
     for (int t = threadIdx.x; t < rows * K * Cin; t += blockDim.x) wf[(size_t)qb0 * K * Cin + t] = 0.f;
     for (int t = threadIdx.x; t < rows * H * K; t += blockDim.x) w_out[(size_t)qb0 * H * K + t] = 0.f;
@@ -379,9 +358,8 @@ __device__ __forceinline__ double seg_combine(double v, double* red) {
   return r;
 }
 
-// CAPS (x / y have N rows, N a capacity): workgroup blockIdx.x == B zero-fills the dead rows [off[B], N) of y; an empty
-// cloud writes mean = rstd = 0 and normalises nothing.  Both leave before the first barrier, on uniform values only.
-template <bool CAPS>
+// x / y have N rows: workgroup blockIdx.x == B zero-fills the dead rows [off[B], N) of y; an empty cloud writes
+// mean = rstd = 0 and normalises nothing.  Both leave before the first barrier, on uniform values only.
 __global__ void __launch_bounds__(256) seg_instnorm_fwd_kernel(const float* __restrict__ x, const int32_t* __restrict__ off,
                                                                int N, int C, float eps, int mode,
                                                                const float* __restrict__ sc, float* __restrict__ y,
@@ -389,13 +367,13 @@ __global__ void __launch_bounds__(256) seg_instnorm_fwd_kernel(const float* __re
   __shared__ double red[256];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), l = threadIdx.x >> 6;
   const bool on = c < C;
-  if (CAPS && b == (int)gridDim.x - 1) {
+  if (b == (int)gridDim.x - 1) {
     if (on)
       for (int r = off[b] + l; r < N; r += 4) y[(size_t)r * C + c] = 0.f;
     return;
   }
   const int r0 = off[b], r1 = off[b + 1];
-  if (CAPS && r1 <= r0) {
+  if (r1 <= r0) {
     if (on && l == 0) mean_out[(size_t)b * C + c] = rstd_out[(size_t)b * C + c] = 0.f;
     return;
   }
@@ -427,7 +405,6 @@ __global__ void __launch_bounds__(256) seg_instnorm_fwd_kernel(const float* __re
 }
 
 // gp = g * act'(out); dsc = gp (mode 2); dx = rstd (gp - mean(gp) - xhat mean(gp xhat)), xhat = (x - mean) rstd
-template <bool CAPS>
 __global__ void __launch_bounds__(256) seg_instnorm_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y,
                                                                const float* __restrict__ x, const float* __restrict__ mean_in,
                                                                const float* __restrict__ rstd_in,
@@ -436,7 +413,7 @@ __global__ void __launch_bounds__(256) seg_instnorm_bwd_kernel(const float* __re
   __shared__ double red[256];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), l = threadIdx.x >> 6;
   const bool on = c < C;
-  if (CAPS && b == (int)gridDim.x - 1) {      // the dead rows of dx (and dsc): zeros
+  if (b == (int)gridDim.x - 1) {      // the dead rows of dx (and dsc): zeros
     if (on)
       for (int r = off[b] + l; r < N; r += 4) {
         dx[(size_t)r * C + c] = 0.f;
@@ -445,7 +422,7 @@ __global__ void __launch_bounds__(256) seg_instnorm_bwd_kernel(const float* __re
     return;
   }
   const int r0 = off[b], r1 = off[b + 1];
-  if (CAPS && r1 <= r0) return;               // an empty cloud has no rows to write
+  if (r1 <= r0) return;                       // an empty cloud has no rows to write
   const double n = (double)(r1 - r0);
   const float m = on ? mean_in[(size_t)b * C + c] : 0.f, rs = on ? rstd_in[(size_t)b * C + c] : 0.f;
   double s1 = 0.0, s2 = 0.0;
@@ -507,13 +484,12 @@ __global__ void max_pool_bwd_kernel(const float* __restrict__ g, const int32_t* 
   dx[t] = acc;
 }
 
-template <bool CAPS>
 __global__ void __launch_bounds__(256) seg_mean_fwd_kernel(const float* __restrict__ x, const int32_t* __restrict__ off,
                                                            int C, float* __restrict__ y) {
   __shared__ double red[256];
   const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), l = threadIdx.x >> 6;
   const int r0 = off[b], r1 = off[b + 1];
-  if (CAPS && r1 <= r0) {                     // an empty cloud's pooled row is 0 (uniform: before the barrier)
+  if (r1 <= r0) {                     // an empty cloud's pooled row is 0 (uniform: before the barrier)
     if (c < C && l == 0) y[(size_t)b * C + c] = 0.f;
     return;
   }
@@ -524,13 +500,12 @@ __global__ void __launch_bounds__(256) seg_mean_fwd_kernel(const float* __restri
   if (c < C && l == 0) y[(size_t)b * C + c] = (float)(s / (double)(r1 - r0));
 }
 
-template <bool CAPS>
 __global__ void seg_mean_bwd_kernel(const float* __restrict__ g, const int32_t* __restrict__ off, int B, int N, int C,
                                     float* __restrict__ dx) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (int64_t)N * C) return;
   const int r = (int)(t / C), c = (int)(t - (int64_t)r * C);
-  if (CAPS && r >= off[B]) {                  // a dead row
+  if (r >= off[B]) {                          // a dead row
     dx[t] = 0.f;
     return;
   }
@@ -556,11 +531,14 @@ __global__ void sample_rows_kernel(const float* __restrict__ x, const int32_t* _
 
 }  // namespace
 
-extern "C" int sug_grid_subsample(const float* pts, const int32_t* off, int B, int cap, float dl, float* out_pad,
-                                  int32_t* cnt, float* out, int32_t* out_off, void* stream) {
+extern "C" int sug_grid_subsample(const float* pts, const int32_t* off, int B, int cap, float dl, int C, int level,
+                                  float* out_pad, int32_t* cnt, float* out, int32_t* out_off, int32_t* record,
+                                  void* stream) {
   SUG_REQUIRE(pts && off && out_pad && cnt && out && out_off, "sug_grid_subsample: null pointer");
   SUG_REQUIRE(B > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD, "sug_grid_subsample: cap %d outside (0, %d]", cap,
               SUG_KPCONV_MAX_CLOUD);
+  SUG_REQUIRE(C > 0 && (int64_t)C <= (int64_t)B * cap && (!record || (level >= 0 && level < 4)),
+              "sug_grid_subsample: capacity %d outside (0, B*cap] or level %d outside [0, 4)", C, level);
   SUG_REQUIRE(dl > 0.f, "sug_grid_subsample: dl must be positive");
   hipStream_t st = (hipStream_t)stream;
   const int sh = (5 * cap + SUB_BLOCK) * (int)sizeof(int);
@@ -570,8 +548,8 @@ extern "C" int sug_grid_subsample(const float* pts, const int32_t* off, int B, i
     return rc;
   hipLaunchKernelGGL(grid_subsample_kernel, dim3(B), dim3(SUB_BLOCK), sh, st, pts, off, dl, cap, out_pad, cnt);
   SUG_LAUNCH_CHECK("sug_grid_subsample");
-  hipLaunchKernelGGL(pack_kernel, dim3(sug_divup((int64_t)B * cap, 256)), dim3(256), 0, st, out_pad, cap, cnt, B, out,
-                     out_off);
+  hipLaunchKernelGGL(pack_kernel, dim3(sug_divup((int64_t)B * cap, 256)), dim3(256), 0, st, out_pad, cap, cnt, B, C, out,
+                     out_off, record, level);
   SUG_LAUNCH_CHECK("sug_grid_subsample/pack");
   return SUG_OK;
 }
@@ -581,7 +559,7 @@ extern "C" int sug_radius_neighbors(const float* q, const int32_t* qoff, int Nq,
   SUG_REQUIRE(q && qoff && s && soff && out, "sug_radius_neighbors: null pointer");
   SUG_REQUIRE(B > 0 && Nq > 0 && Ns > 0 && limit > 0 && limit <= KP_MAX_H, "sug_radius_neighbors: bad shape");
   const float r2 = radius * radius;       // fp32(r) * fp32(r), rounded once
-  hipLaunchKernelGGL(radius_kernel<false>, dim3(sug_divup(Nq, 256)), dim3(256), 0, (hipStream_t)stream, q, qoff, s, soff, B, Nq,
+  hipLaunchKernelGGL(radius_kernel, dim3(sug_divup(Nq, 256)), dim3(256), 0, (hipStream_t)stream, q, qoff, s, soff, B, Nq,
                      Ns, r2, limit, out);
   SUG_LAUNCH_CHECK("sug_radius_neighbors");
   return SUG_OK;
@@ -593,20 +571,20 @@ extern "C" int sug_radius_reverse(const int32_t* nbr, const int32_t* qoff, const
   SUG_REQUIRE(B > 0 && H > 0 && Ns > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD,
               "sug_radius_reverse: bad shape (cap %d, at most %d supports per cloud)", cap, SUG_KPCONV_MAX_CLOUD);
   const int sh = (2 * cap + SUB_BLOCK) * (int)sizeof(int);
-  hipLaunchKernelGGL(radius_reverse_kernel<false>, dim3(B), dim3(SUB_BLOCK), sh, (hipStream_t)stream, nbr, qoff, soff, H, Ns,
+  hipLaunchKernelGGL(radius_reverse_kernel, dim3(B + 1), dim3(SUB_BLOCK), sh, (hipStream_t)stream, nbr, qoff, soff, H, Ns,
                      cap, rev_be, rev_ent);
   SUG_LAUNCH_CHECK("sug_radius_reverse");
   return SUG_OK;
 }
 
-extern "C" int sug_kpconv_fwd(const float* q, const float* s, const int32_t* nbr, int Nq, int H, int Ns,
-                              const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w,
+extern "C" int sug_kpconv_fwd(const float* q, const float* s, const int32_t* nbr, const int32_t* nq_valid, int Nq, int H,
+                              int Ns, const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w,
                               float* cnt, void* stream) {
-  SUG_REQUIRE(q && s && nbr && kp && x && wf && w && cnt, "sug_kpconv_fwd: null pointer");
+  SUG_REQUIRE(q && s && nbr && nq_valid && kp && x && wf && w && cnt, "sug_kpconv_fwd: null pointer");
   SUG_REQUIRE(Nq > 0 && Ns > 0 && Cin > 0 && H > 0 && H <= KP_MAX_H && K > 0 && K <= KP_MAX_K && extent > 0.f,
               "sug_kpconv_fwd: bad shape (H %d <= %d, K %d <= %d)", H, KP_MAX_H, K, KP_MAX_K);
-  hipLaunchKernelGGL(kpconv_fwd_kernel<false>, dim3(sug_divup(Nq, KP_QB)), dim3(256), 0, (hipStream_t)stream, q, s, nbr,
-                     (const int32_t*)nullptr, Nq, H, Ns, kp, K, extent, x, Cin, wf, w, cnt);
+  hipLaunchKernelGGL(kpconv_fwd_kernel, dim3(sug_divup(Nq, KP_QB)), dim3(256), 0, (hipStream_t)stream, q, s, nbr, nq_valid,
+                     Nq, H, Ns, kp, K, extent, x, Cin, wf, w, cnt);
   SUG_LAUNCH_CHECK("sug_kpconv_fwd");
   return SUG_OK;
 }
@@ -621,22 +599,23 @@ extern "C" int sug_kpconv_bwd(const int32_t* rev_be, const int32_t* rev_ent, int
   return SUG_OK;
 }
 
-extern "C" int sug_seg_instnorm_fwd(const float* x, const int32_t* off, int B, int C, float eps, int mode,
+extern "C" int sug_seg_instnorm_fwd(const float* x, const int32_t* off, int B, int N, int C, float eps, int mode,
                                     const float* sc, float* y, float* mean, float* rstd, void* stream) {
   SUG_REQUIRE(x && off && y && mean && rstd && (mode != 2 || sc), "sug_seg_instnorm_fwd: null pointer");
-  SUG_REQUIRE(B > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_fwd: bad shape / mode");
-  hipLaunchKernelGGL(seg_instnorm_fwd_kernel<false>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, 0,
+  SUG_REQUIRE(B > 0 && N > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_fwd: bad shape / mode");
+  hipLaunchKernelGGL(seg_instnorm_fwd_kernel, dim3(B + 1, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, N,
                      C, eps, mode, sc, y, mean, rstd);
   SUG_LAUNCH_CHECK("sug_seg_instnorm_fwd");
   return SUG_OK;
 }
 
 extern "C" int sug_seg_instnorm_bwd(const float* g, const float* y, const float* x, const float* mean, const float* rstd,
-                                    const int32_t* off, int B, int C, int mode, float* dx, float* dsc, void* stream) {
+                                    const int32_t* off, int B, int N, int C, int mode, float* dx, float* dsc,
+                                    void* stream) {
   SUG_REQUIRE(g && y && x && mean && rstd && off && dx && (mode != 2 || dsc), "sug_seg_instnorm_bwd: null pointer");
-  SUG_REQUIRE(B > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_bwd: bad shape / mode");
-  hipLaunchKernelGGL(seg_instnorm_bwd_kernel<false>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, g, y, x,
-                     mean, rstd, off, 0, C, mode, dx, dsc);
+  SUG_REQUIRE(B > 0 && N > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_bwd: bad shape / mode");
+  hipLaunchKernelGGL(seg_instnorm_bwd_kernel, dim3(B + 1, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, g, y, x,
+                     mean, rstd, off, N, C, mode, dx, dsc);
   SUG_LAUNCH_CHECK("sug_seg_instnorm_bwd");
   return SUG_OK;
 }
@@ -664,7 +643,7 @@ extern "C" int sug_seg_max_pool_bwd(const float* g, const int32_t* arg, const in
 extern "C" int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C, float* y, void* stream) {
   SUG_REQUIRE(x && off && y, "sug_seg_mean_fwd: null pointer");
   SUG_REQUIRE(B > 0 && C > 0, "sug_seg_mean_fwd: bad shape");
-  hipLaunchKernelGGL(seg_mean_fwd_kernel<false>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, y);
+  hipLaunchKernelGGL(seg_mean_fwd_kernel, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, y);
   SUG_LAUNCH_CHECK("sug_seg_mean_fwd");
   return SUG_OK;
 }
@@ -672,106 +651,9 @@ extern "C" int sug_seg_mean_fwd(const float* x, const int32_t* off, int B, int C
 extern "C" int sug_seg_mean_bwd(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream) {
   SUG_REQUIRE(g && off && dx, "sug_seg_mean_bwd: null pointer");
   SUG_REQUIRE(B > 0 && N > 0 && C > 0, "sug_seg_mean_bwd: bad shape");
-  hipLaunchKernelGGL(seg_mean_bwd_kernel<false>, dim3(sug_divup((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, g, off, B,
+  hipLaunchKernelGGL(seg_mean_bwd_kernel, dim3(sug_divup((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, g, off, B,
                      N, C, dx);
   SUG_LAUNCH_CHECK("sug_seg_mean_bwd");
-  return SUG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- capacity forms
-extern "C" int sug_grid_subsample_cap(const float* pts, const int32_t* off, int B, int cap, float dl, int C, int level,
-                                      float* out_pad, int32_t* cnt, float* out, int32_t* out_off, int32_t* record,
-                                      void* stream) {
-  SUG_REQUIRE(pts && off && out_pad && cnt && out && out_off && record, "sug_grid_subsample_cap: null pointer");
-  SUG_REQUIRE(B > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD, "sug_grid_subsample_cap: cap %d outside (0, %d]", cap,
-              SUG_KPCONV_MAX_CLOUD);
-  SUG_REQUIRE(C > 0 && (int64_t)C <= (int64_t)B * cap && level >= 0 && level < 4,
-              "sug_grid_subsample_cap: capacity %d outside (0, B*cap] or level %d outside [0, 4)", C, level);
-  SUG_REQUIRE(dl > 0.f, "sug_grid_subsample_cap: dl must be positive");
-  hipStream_t st = (hipStream_t)stream;
-  const int sh = (5 * cap + SUB_BLOCK) * (int)sizeof(int);
-  static SugLdsOptIn note;
-  if (int rc = sug_allow_dynamic_lds(note, &grid_subsample_kernel, (5 * SUG_KPCONV_MAX_CLOUD + SUB_BLOCK) * 4,
-                                     "sug_grid_subsample_cap"))
-    return rc;
-  hipLaunchKernelGGL(grid_subsample_kernel, dim3(B), dim3(SUB_BLOCK), sh, st, pts, off, dl, cap, out_pad, cnt);
-  SUG_LAUNCH_CHECK("sug_grid_subsample_cap");
-  hipLaunchKernelGGL(pack_cap_kernel, dim3(sug_divup((int64_t)B * cap, 256)), dim3(256), 0, st, out_pad, cap, cnt, B, C, out,
-                     out_off, record, level);
-  SUG_LAUNCH_CHECK("sug_grid_subsample_cap/pack");
-  return SUG_OK;
-}
-
-extern "C" int sug_radius_neighbors_cap(const float* q, const int32_t* qoff, int Cq, const float* s, const int32_t* soff,
-                                        int Cs, int B, float radius, int limit, int32_t* out, void* stream) {
-  SUG_REQUIRE(q && qoff && s && soff && out, "sug_radius_neighbors_cap: null pointer");
-  SUG_REQUIRE(B > 0 && Cq > 0 && Cs > 0 && limit > 0 && limit <= KP_MAX_H, "sug_radius_neighbors_cap: bad shape");
-  const float r2 = radius * radius;
-  hipLaunchKernelGGL(radius_kernel<true>, dim3(sug_divup(Cq, 256)), dim3(256), 0, (hipStream_t)stream, q, qoff, s, soff, B,
-                     Cq, Cs, r2, limit, out);
-  SUG_LAUNCH_CHECK("sug_radius_neighbors_cap");
-  return SUG_OK;
-}
-
-extern "C" int sug_radius_reverse_cap(const int32_t* nbr, const int32_t* qoff, const int32_t* soff, int B, int H, int Cs,
-                                      int cap, int32_t* rev_be, int32_t* rev_ent, void* stream) {
-  SUG_REQUIRE(nbr && qoff && soff && rev_be && rev_ent, "sug_radius_reverse_cap: null pointer");
-  SUG_REQUIRE(B > 0 && H > 0 && Cs > 0 && cap > 0 && cap <= SUG_KPCONV_MAX_CLOUD,
-              "sug_radius_reverse_cap: bad shape (cap %d, at most %d supports per cloud)", cap, SUG_KPCONV_MAX_CLOUD);
-  const int sh = (2 * cap + SUB_BLOCK) * (int)sizeof(int);
-  hipLaunchKernelGGL(radius_reverse_kernel<true>, dim3(B + 1), dim3(SUB_BLOCK), sh, (hipStream_t)stream, nbr, qoff, soff, H,
-                     Cs, cap, rev_be, rev_ent);
-  SUG_LAUNCH_CHECK("sug_radius_reverse_cap");
-  return SUG_OK;
-}
-
-extern "C" int sug_kpconv_fwd_cap(const float* q, const float* s, const int32_t* nbr, const int32_t* nq_valid, int Cq, int H,
-                                  int Cs, const float* kp, int K, float extent, const float* x, int Cin, float* wf, float* w,
-                                  float* cnt, void* stream) {
-  SUG_REQUIRE(q && s && nbr && nq_valid && kp && x && wf && w && cnt, "sug_kpconv_fwd_cap: null pointer");
-  SUG_REQUIRE(Cq > 0 && Cs > 0 && Cin > 0 && H > 0 && H <= KP_MAX_H && K > 0 && K <= KP_MAX_K && extent > 0.f,
-              "sug_kpconv_fwd_cap: bad shape (H %d <= %d, K %d <= %d)", H, KP_MAX_H, K, KP_MAX_K);
-  hipLaunchKernelGGL(kpconv_fwd_kernel<true>, dim3(sug_divup(Cq, KP_QB)), dim3(256), 0, (hipStream_t)stream, q, s, nbr,
-                     nq_valid, Cq, H, Cs, kp, K, extent, x, Cin, wf, w, cnt);
-  SUG_LAUNCH_CHECK("sug_kpconv_fwd_cap");
-  return SUG_OK;
-}
-
-extern "C" int sug_seg_instnorm_fwd_cap(const float* x, const int32_t* off, int B, int N, int C, float eps, int mode,
-                                        const float* sc, float* y, float* mean, float* rstd, void* stream) {
-  SUG_REQUIRE(x && off && y && mean && rstd && (mode != 2 || sc), "sug_seg_instnorm_fwd_cap: null pointer");
-  SUG_REQUIRE(B > 0 && N > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_fwd_cap: bad shape / mode");
-  hipLaunchKernelGGL(seg_instnorm_fwd_kernel<true>, dim3(B + 1, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off,
-                     N, C, eps, mode, sc, y, mean, rstd);
-  SUG_LAUNCH_CHECK("sug_seg_instnorm_fwd_cap");
-  return SUG_OK;
-}
-
-extern "C" int sug_seg_instnorm_bwd_cap(const float* g, const float* y, const float* x, const float* mean,
-                                        const float* rstd, const int32_t* off, int B, int N, int C, int mode, float* dx,
-                                        float* dsc, void* stream) {
-  SUG_REQUIRE(g && y && x && mean && rstd && off && dx && (mode != 2 || dsc), "sug_seg_instnorm_bwd_cap: null pointer");
-  SUG_REQUIRE(B > 0 && N > 0 && C > 0 && mode >= 0 && mode <= 2, "sug_seg_instnorm_bwd_cap: bad shape / mode");
-  hipLaunchKernelGGL(seg_instnorm_bwd_kernel<true>, dim3(B + 1, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, g, y, x,
-                     mean, rstd, off, N, C, mode, dx, dsc);
-  SUG_LAUNCH_CHECK("sug_seg_instnorm_bwd_cap");
-  return SUG_OK;
-}
-
-extern "C" int sug_seg_mean_fwd_cap(const float* x, const int32_t* off, int B, int C, float* y, void* stream) {
-  SUG_REQUIRE(x && off && y, "sug_seg_mean_fwd_cap: null pointer");
-  SUG_REQUIRE(B > 0 && C > 0, "sug_seg_mean_fwd_cap: bad shape");
-  hipLaunchKernelGGL(seg_mean_fwd_kernel<true>, dim3(B, sug_divup(C, 64)), dim3(256), 0, (hipStream_t)stream, x, off, C, y);
-  SUG_LAUNCH_CHECK("sug_seg_mean_fwd_cap");
-  return SUG_OK;
-}
-
-extern "C" int sug_seg_mean_bwd_cap(const float* g, const int32_t* off, int B, int N, int C, float* dx, void* stream) {
-  SUG_REQUIRE(g && off && dx, "sug_seg_mean_bwd_cap: null pointer");
-  SUG_REQUIRE(B > 0 && N > 0 && C > 0, "sug_seg_mean_bwd_cap: bad shape");
-  hipLaunchKernelGGL(seg_mean_bwd_kernel<true>, dim3(sug_divup((int64_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream, g, off,
-                     B, N, C, dx);
-  SUG_LAUNCH_CHECK("sug_seg_mean_bwd_cap");
   return SUG_OK;
 }
 

@@ -8,9 +8,8 @@ Where the reference passes `stack_lengths` (per-cloud row counts) this build pas
 [B+1] (the `offsets` entry of the preprocessing dict): the kernels take the segments from device memory, without a host
 synchronisation.  Only the rigid / linear / sum path is built; the other options raise NotImplementedError.
 
-A preprocessing dict with `capacity: True` (PreprocessorGPU with level caps) holds every level at a static number of rows;
-the blocks then call the capacity forms of the ops (ops.kpconv_cap, seg_instnorm_cap, seg_mean_cap), which read the valid
-row counts from the offsets on the device and keep the dead rows exactly zero.
+A level tensor may have more rows than its offsets name (PreprocessorGPU with level caps holds every level at a static
+number of rows): the ops read the valid row counts from the offsets on the device and keep the dead rows exactly zero.
 """
 import functools
 import math
@@ -72,13 +71,14 @@ def load_kernels(radius, num_kpoints, dimension, fixed, lloyd=False):
 
 # ----------------------------------------------------------------------------------------------- helpers
 def _rev_single(neighb_inds, Nq, Ns):
-    """Reverse lists of a neighbour table treated as one cloud (a KPConv called outside the preprocessed batch)."""
+    """(reverse lists, query offsets) of a neighbour table treated as one cloud (a KPConv called outside the preprocessed
+    batch)."""
     if Ns > ops.KPCONV_MAX_CLOUD:
         raise NotImplementedError('KPConv outside a preprocessed batch: at most %d supports (got %d)' % (ops.KPCONV_MAX_CLOUD, Ns))
     dev = neighb_inds.device
     qoff = torch.tensor([0, Nq], dtype=torch.int32, device=dev)
     soff = torch.tensor([0, Ns], dtype=torch.int32, device=dev)
-    return ops.radius_reverse(neighb_inds, qoff, soff, Ns, max(Ns, 1))
+    return ops.radius_reverse(neighb_inds, qoff, soff, Ns, max(Ns, 1)), qoff
 
 
 def _i32(t):
@@ -89,14 +89,13 @@ def max_pool(x, inds, rev=None):
     """[n2, d]: max over each row's pooling slots of x (shadow slot = 0 row), model/KPConv_blocks.py:127-142."""
     inds = _i32(inds)
     if rev is None:
-        rev = _rev_single(inds, inds.shape[0], x.shape[0])
+        rev, _ = _rev_single(inds, inds.shape[0], x.shape[0])
     return ops.seg_max_pool(x, inds, rev)
 
 
-def global_average(x, batch_offsets, capacity=False):
-    """[B, d]: per-cloud mean of the rows of x (model/KPConv_blocks.py:179-197); batch_offsets [B+1] int32 (device).
-    capacity: x is at capacity (an empty cloud's row is zero)."""
-    return (ops.seg_mean_cap if capacity else ops.seg_mean)(x, batch_offsets)
+def global_average(x, batch_offsets):
+    """[B, d]: per-cloud mean of the rows of x (model/KPConv_blocks.py:179-197); batch_offsets [B+1] int32 (device)."""
+    return ops.seg_mean(x, batch_offsets)
 
 
 def sample_index(lengths, sampled_len=64):
@@ -166,16 +165,13 @@ class KPConv(nn.Module):
         return Parameter(torch.tensor(K_points_numpy, dtype=torch.float32), requires_grad=False)
 
     def forward(self, q_pts, s_pts, neighb_inds, x, rev=None, qoff=None):
-        """[Nq, out_channels]; rev: the sorted reverse lists of neighb_inds (ops.radius_reverse), built here if absent.
-        qoff (the capacity layout): the query level's device offsets; rev is then required."""
+        """[Nq, out_channels]; rev: the sorted reverse lists of neighb_inds (ops.radius_reverse), qoff: the query level's
+        device offsets.  Without the two (the reference's call) the tables are one cloud's and both are built here."""
         neighb_inds = _i32(neighb_inds)
-        if qoff is not None:
-            return ops.kpconv_cap(x, q_pts.contiguous(), s_pts.contiguous(), neighb_inds, rev, self.kernel_points,
-                                  self.weights, self.KP_extent, qoff)
         if rev is None:
-            rev = _rev_single(neighb_inds, q_pts.shape[0], s_pts.shape[0])
+            rev, qoff = _rev_single(neighb_inds, q_pts.shape[0], s_pts.shape[0])
         return ops.kpconv(x, q_pts.contiguous(), s_pts.contiguous(), neighb_inds, rev, self.kernel_points, self.weights,
-                          self.KP_extent)
+                          self.KP_extent, qoff)
 
     def __repr__(self):
         return 'KPConv(radius: {:.2f}, extent: {:.2f}, in_feat: {:d}, out_feat: {:d})'.format(
@@ -210,10 +206,10 @@ class BatchNormBlock(nn.Module):
         self.in_dim = in_dim
         self.norm = nn.InstanceNorm1d(in_dim, momentum=bn_momentum)
 
-    def forward(self, x, stack_lengths, act=False, shortcut=None, capacity=False):
+    def forward(self, x, stack_lengths, act=False, shortcut=None):
         """stack_lengths: the level's device offsets [B+1] (int32).  act: LeakyReLU(0.1) after the norm;
-        shortcut: LeakyReLU(0.1)(norm + shortcut) (the end of the bottleneck block).  capacity: x is at capacity."""
-        return (ops.seg_instnorm_cap if capacity else ops.seg_instnorm)(x, stack_lengths, act=act, shortcut=shortcut)
+        shortcut: LeakyReLU(0.1)(norm + shortcut) (the end of the bottleneck block)."""
+        return ops.seg_instnorm(x, stack_lengths, act=act, shortcut=shortcut)
 
     def __repr__(self):
         return 'BatchNormBlock(in_feat: {:d}, momentum: {:.3f}, only_bias: {:s})'.format(
@@ -234,10 +230,10 @@ class UnaryBlock(nn.Module):
         if not no_relu:
             self.leaky_relu = nn.LeakyReLU(0.1)
 
-    def forward(self, x, stack_lengths=None, shortcut=None, capacity=False):
+    def forward(self, x, stack_lengths=None, shortcut=None):
         """shortcut (no_relu blocks only): LeakyReLU(0.1)(block(x) + shortcut) in the norm's epilogue."""
         y = ops.linear_rows(x, self.mlp.weight)
-        return self.batch_norm(y, stack_lengths, act=not self.no_relu, shortcut=shortcut, capacity=capacity)
+        return self.batch_norm(y, stack_lengths, act=not self.no_relu, shortcut=shortcut)
 
     def __repr__(self):
         return 'UnaryBlock(in_feat: {:d}, out_feat: {:d}, BN: {:s}, ReLU: {:s})'.format(
@@ -273,9 +269,8 @@ class SimpleBlock(nn.Module):
 
     def forward(self, x, batch):
         q_pts, s_pts, nbr, rev, off = _level(batch, self.layer_ind, 'strided' in self.block_name)
-        cap = bool(batch.get('capacity', False))
-        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev, qoff=off if cap else None)
-        return self.batch_norm(x, off, act=True, capacity=cap)
+        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev, qoff=off)
+        return self.batch_norm(x, off, act=True)
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -310,12 +305,11 @@ class ResnetBottleneckBlock(nn.Module):
         strided = 'strided' in self.block_name
         off_pre = batch['offsets'][self.layer_ind]
         q_pts, s_pts, nbr, rev, off_post = _level(batch, self.layer_ind, strided)
-        cap = bool(batch.get('capacity', False))
-        x = self.unary1(features, off_pre, capacity=cap) if isinstance(self.unary1, UnaryBlock) else features
-        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev, qoff=off_post if cap else None)
-        x = self.batch_norm_conv(x, off_post, act=True, capacity=cap)
+        x = self.unary1(features, off_pre) if isinstance(self.unary1, UnaryBlock) else features
+        x = self.KPConv(q_pts, s_pts, nbr, x, rev=rev, qoff=off_post)
+        x = self.batch_norm_conv(x, off_post, act=True)
         shortcut = max_pool(features, nbr, rev) if strided else features
         if isinstance(self.unary_shortcut, UnaryBlock):
-            shortcut = self.unary_shortcut(shortcut, off_post, capacity=cap)
+            shortcut = self.unary_shortcut(shortcut, off_post)
         # unary2 (Linear + norm, no ReLU), the residual sum and the LeakyReLU in one epilogue
-        return self.unary2(x, off_post, shortcut=shortcut, capacity=cap)
+        return self.unary2(x, off_post, shortcut=shortcut)

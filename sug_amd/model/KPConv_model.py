@@ -10,8 +10,9 @@ are restated under documented assumptions:
   * grid subsample: key = floor(fp32(p) / fp32(dl)) per axis (true division), voxels per cloud in order of their first
     point (MinkowskiEngine's own order is a hash order), the voxel point = fp32 sum in point order / count.
 
-With level caps (`set_level_caps` of KPConv_g / KPFCls) the pyramid takes the CAPACITY form instead: level l owns a buffer
-of a static number of rows (`level_capacity`), the kernels read the valid counts from the device offsets, and nothing is
+Every op takes level buffers of at least off[B] rows and reads the valid counts from the device offsets (kpconv.hip,
+"ROW LAYOUT"); the exact-size pyramid slices its buffers to exactly off[B] rows.  With level caps (`set_level_caps` of
+KPConv_g / KPFCls) level l instead keeps a buffer of a static number of rows (`level_capacity`), and nothing is
 copied to the host -- a forward and its backward are one static launch sequence, which a hipGraph can replay.  A level
 that needs more rows than its capacity is truncated (the tail of the last clouds) and noted in a small device record that
 `capacity_report` reads; `calibrate_level_caps` measures caps on sample batches with the exact-size path.
@@ -182,34 +183,58 @@ class PreprocessorGPU(nn.Module):
                    'cap_needed': int(math.ceil(rec[l] / float(B)))} for l in range(len(self.level_caps))]
         return {'levels': levels, 'overflows': rec[4]}
 
-    def _forward_capacity(self, points, B, N):
-        """The pyramid at capacity: every tensor has a static size, every count stays on the device."""
+    def forward(self, pts: List[torch.Tensor]):
+        """pts: list of point clouds XYZ [Ni, 3] (fp32, HIP device)."""
+        return self.forward_packed(torch.cat([p.float() for p in pts], 0).contiguous(), [int(p.shape[0]) for p in pts])
+
+    def forward_packed(self, points, lengths):
+        """points [sum Ni, 3] packed on the device, lengths: host ints.  One builder for both forms: with level caps every
+        level buffer has its static capacity and every count stays on the device; without, the buffers are sliced to their
+        totals after the one synchronisation of the forward."""
+        ops._need_gpu(points)
         config = self.cfg
         plan = _layer_plan(config)
         limits = config.neighborhood_limits
         dev = points.device
-        if N > ops.KPCONV_MAX_CLOUD:
-            raise NotImplementedError('KPConv preprocessing: clouds of at most %d points (got %d)' % (ops.KPCONV_MAX_CLOUD, N))
-        C = level_capacity(B, N, self.level_caps)
-        rec = self._record_on(dev)
-        self._shape = (B, N)
-        bufs, offs = [points], [torch.arange(0, (B + 1) * N, N, dtype=torch.int32, device=dev)]
+        B, cap = len(lengths), int(max(lengths))
+        if cap > ops.KPCONV_MAX_CLOUD:
+            raise NotImplementedError('KPConv preprocessing: clouds of at most %d points (got %d)' % (ops.KPCONV_MAX_CLOUD, cap))
+        if self.level_caps is not None:
+            if len(set(lengths)) != 1:
+                raise NotImplementedError('KPConv preprocessing with level caps: clouds of one length (got %r)' % (lengths,))
+            C = level_capacity(B, cap, self.level_caps)
+            rec = self._record_on(dev)
+            self._shape = (B, cap)
+            off0 = torch.arange(0, (B + 1) * cap, cap, dtype=torch.int32, device=dev)
+        else:
+            C = rec = None
+            off0 = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int32).to(dev, non_blocking=True)
+        bufs, offs = [points], [off0]
         for li, (r, pooled) in enumerate(plan):
             if not pooled:
                 break
-            p, o = ops.kp_grid_subsample_cap(bufs[-1], offs[-1], B, N, 2 * r / config.conv_radius, C[li + 1], rec, li)
+            p, o = ops.kp_grid_subsample(bufs[-1], offs[-1], B, cap, 2 * r / config.conv_radius,
+                                         rows=C[li + 1] if C else None, record=rec, level=li)
             bufs.append(p)
             offs.append(o)
+        stack = torch.stack(offs)
+        lens = None
+        if C is None:
+            # the one synchronisation of the forward: every level's offsets
+            off_host = stack.cpu().numpy().astype(np.int64)
+            lens = [list(map(int, np.diff(o))) for o in off_host]
+            bufs = [b[:int(o[-1])] for b, o in zip(bufs, off_host)]
         neighbors, pools, upsamples, rev_n, rev_p = [], [], [], [], []
         for li, (r, pooled) in enumerate(plan):
-            nb = ops.radius_neighbors_cap(bufs[li], offs[li], bufs[li], offs[li], r, limits[li])
+            Ns = bufs[li].shape[0]
+            nb = ops.radius_neighbors(bufs[li], offs[li], bufs[li], offs[li], r, limits[li])
             neighbors.append(nb)
-            rev_n.append(ops.radius_reverse_cap(nb, offs[li], offs[li], C[li], N))
+            rev_n.append(ops.radius_reverse(nb, offs[li], offs[li], Ns, cap))
             if pooled:
-                pl = ops.radius_neighbors_cap(bufs[li + 1], offs[li + 1], bufs[li], offs[li], r, limits[li])
+                pl = ops.radius_neighbors(bufs[li + 1], offs[li + 1], bufs[li], offs[li], r, limits[li])
                 pools.append(pl)
-                rev_p.append(ops.radius_reverse_cap(pl, offs[li + 1], offs[li], C[li], N))
-                upsamples.append(ops.radius_neighbors_cap(bufs[li], offs[li], bufs[li + 1], offs[li + 1], 2 * r, limits[li]))
+                rev_p.append(ops.radius_reverse(pl, offs[li + 1], offs[li], Ns, cap))
+                upsamples.append(ops.radius_neighbors(bufs[li], offs[li], bufs[li + 1], offs[li + 1], 2 * r, limits[li]))
             else:
                 empty = torch.zeros((0, 1), dtype=torch.int32, device=dev)
                 pools.append(empty)
@@ -220,75 +245,14 @@ class PreprocessorGPU(nn.Module):
             'neighbors': neighbors,
             'pools': pools,
             'upsamples': upsamples,
-            'stack_lengths': [(o[1:] - o[:-1]).to(torch.int64) for o in offs],
+            'stack_lengths': list((stack[:, 1:] - stack[:, :-1]).to(torch.int64).unbind(0)),
+            # this build's additions: device offsets, reverse lists, host lengths (exact sizes only: with level caps
+            # nothing may need them), the level capacities (with level caps only)
             'offsets': offs,
             'rev_neighbors': rev_n,
             'rev_pools': rev_p,
-            'lengths': None,            # nothing may need host lengths
-            'capacity': True,
+            'lengths': lens,
             'capacities': C,
-        }
-
-    def forward(self, pts: List[torch.Tensor]):
-        """pts: list of point clouds XYZ [Ni, 3] (fp32, HIP device)."""
-        return self.forward_packed(torch.cat([p.float() for p in pts], 0).contiguous(), [int(p.shape[0]) for p in pts])
-
-    def forward_packed(self, points, lengths):
-        """points [sum Ni, 3] packed on the device, lengths: host ints."""
-        ops._need_gpu(points)
-        if self.level_caps is not None:
-            if len(set(lengths)) != 1:
-                raise NotImplementedError('KPConv preprocessing with level caps: clouds of one length (got %r)' % (lengths,))
-            return self._forward_capacity(points, len(lengths), int(lengths[0]))
-        config = self.cfg
-        plan = _layer_plan(config)
-        limits = config.neighborhood_limits
-        dev = points.device
-        B = len(lengths)
-        cap = max(lengths)
-        if cap > ops.KPCONV_MAX_CLOUD:
-            raise NotImplementedError('KPConv preprocessing: clouds of at most %d points (got %d)' % (ops.KPCONV_MAX_CLOUD, cap))
-        off0 = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int32).to(dev, non_blocking=True)
-        bufs, offs = [points], [off0]
-        for li, (r, pooled) in enumerate(plan):
-            if not pooled:
-                break
-            dl = 2 * r / config.conv_radius
-            p, o = ops.kp_grid_subsample(bufs[-1], offs[-1], B, cap, dl)
-            bufs.append(p)
-            offs.append(o)
-        # the one synchronisation of the forward: every level's offsets
-        off_host = torch.stack(offs).cpu().numpy().astype(np.int64)
-        lens = [np.diff(o) for o in off_host]
-        pts = [b[:int(o[-1])] for b, o in zip(bufs, off_host)]
-        neighbors, pools, upsamples, rev_n, rev_p = [], [], [], [], []
-        for li, (r, pooled) in enumerate(plan):
-            Ns, capl = pts[li].shape[0], int(lens[li].max())
-            nb = ops.radius_neighbors(pts[li], offs[li], pts[li], offs[li], r, limits[li])
-            neighbors.append(nb)
-            rev_n.append(ops.radius_reverse(nb, offs[li], offs[li], Ns, capl))
-            if pooled:
-                pl = ops.radius_neighbors(pts[li + 1], offs[li + 1], pts[li], offs[li], r, limits[li])
-                pools.append(pl)
-                rev_p.append(ops.radius_reverse(pl, offs[li + 1], offs[li], Ns, capl))
-                upsamples.append(ops.radius_neighbors(pts[li], offs[li], pts[li + 1], offs[li + 1], 2 * r, limits[li]))
-            else:
-                empty = torch.zeros((0, 1), dtype=torch.int32, device=dev)
-                pools.append(empty)
-                upsamples.append(empty)
-                rev_p.append(None)
-        stack = torch.tensor(np.stack(lens), dtype=torch.int64).to(dev, non_blocking=True)
-        return {
-            'points': pts,
-            'neighbors': neighbors,
-            'pools': pools,
-            'upsamples': upsamples,
-            'stack_lengths': list(stack.unbind(0)),
-            # this build's additions: device offsets, reverse lists, host lengths
-            'offsets': offs,
-            'rev_neighbors': rev_n,
-            'rev_pools': rev_p,
-            'lengths': [list(map(int, x)) for x in lens],
         }
 
 
@@ -340,9 +304,9 @@ class GlobalAverageBlock(nn.Module):
     def __init__(self):
         super(GlobalAverageBlock, self).__init__()
 
-    def forward(self, x, len, capacity=False):
+    def forward(self, x, len):
         """len: the last level's device offsets [B+1] (int32) in this build (the reference: stack lengths)."""
-        return global_average(x, len, capacity)
+        return global_average(x, len)
 
 
 def _split_clouds(x):
@@ -373,7 +337,7 @@ class KPFCls(LevelCaps, nn.Module):
         kpconv_meta = self.preprocessor.forward_packed(pts, lengths)
         feats0 = kpconv_meta["points"][0][:, 0:1]
         feats = self.encoder(feats0, kpconv_meta)
-        feats_avg = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1], kpconv_meta.get('capacity', False))
+        feats_avg = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1])
         return self.fc(feats_avg)
 
 

@@ -565,9 +565,7 @@ class KPConv_g(nn.Module):
     def __init__(self, config=None):
         super(KPConv_g, self).__init__()
         from .KPConv_model import KPFEncoder, PreprocessorGPU, GlobalAverageBlock, KPConvConfig
-        from .KPConv_blocks import sample_tensor_slices
         self.config = KPConvConfig if config is None else config
-        self.sample_tensor_slices = sample_tensor_slices
         self.preprocessor = PreprocessorGPU(self.config)
         self.encoder = KPFEncoder(self.config)
         self.global_avg_pooling = GlobalAverageBlock()
@@ -590,11 +588,8 @@ class KPConv_g(nn.Module):
         kpconv_meta = self.preprocessor.forward_packed(pts, lengths)
         feats0 = kpconv_meta["points"][0][:, 0:1]
         feats = self.encoder(feats0, kpconv_meta)
-        if kpconv_meta.get('capacity', False):
-            nodes = ops.kp_sample_rows(feats[2], kpconv_meta["offsets"][1])
-        else:
-            nodes = self.sample_tensor_slices(feats[2], kpconv_meta["lengths"][1])
-        feats = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1], kpconv_meta.get('capacity', False))
+        nodes = ops.kp_sample_rows(feats[2], kpconv_meta["offsets"][1])
+        feats = self.global_avg_pooling(feats[0], kpconv_meta["offsets"][-1])
         if node:
             return feats, nodes, None
         return feats, nodes

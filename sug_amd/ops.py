@@ -4051,27 +4051,34 @@ def chamfer_nn(a, b):
 
 
 # ----------------------------------------------------------------------------- KPConv backbone
-# Packed clouds (rows of all clouds of a level back to back) with int32 device offsets off [B+1]; neighbour tables
-# [Nq, H] int32 whose missing slots hold the shadow index Ns (sug_amd/csrc/kpconv.hip).
+# Packed clouds (sug_amd/csrc/kpconv.hip, "ROW LAYOUT"): a level tensor has rows >= off[B] rows, of which the first off[B]
+# are valid -- the clouds back to back at the int32 device offsets off [B+1] -- and the rest exactly zero, in and out;
+# neighbour tables [Nq, H] int32 whose missing slots hold the shadow index Ns, the rows of the support tensor.  The valid
+# counts are read on the device, so nothing here waits for the host.  Exact sizes are tensors of off[B] rows.
 KPCONV_MAX_CLOUD = _H['SUG_KPCONV_MAX_CLOUD']          # the largest `cap` sug_grid_subsample / sug_radius_reverse take
+KPCONV_RECORD_INTS = _H['SUG_KPCONV_RECORD_INTS']
 
 
-def kp_grid_subsample(pts, off, B, cap, dl):
+def kp_grid_subsample(pts, off, B, cap, dl, rows=None, record=None, level=0):
     """Grid subsample of packed clouds pts [N,3] (offsets off, every cloud <= cap points) -> (packed voxel points
-    [N,3] of which the first sum-of-counts rows are valid, their offsets [B+1]); nothing is synchronised."""
-    _need_gpu(pts, off)
+    [rows,3] (rows: N if None) of which the first sum-of-counts rows are valid and the others zero, their offsets [B+1]
+    clamped to rows); with a `record` (int32 [KPCONV_RECORD_INTS]) the unclamped total goes into it at `level` (0 = the
+    first pooled level).  Nothing is synchronised."""
+    _need_gpu(pts, off, record)
     pts = pts.detach().contiguous()
+    rows = pts.shape[0] if rows is None else rows
     pad = torch.empty(B, cap, 3, dtype=torch.float32, device=pts.device)
     cnt = torch.empty(B, dtype=torch.int32, device=pts.device)
-    out = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=pts.device)
+    out = torch.empty(rows, 3, dtype=torch.float32, device=pts.device)
     out_off = torch.empty(B + 1, dtype=torch.int32, device=pts.device)
-    check(lib().sug_grid_subsample(_p(pts), _p(off), B, cap, float(dl), _p(pad), _p(cnt), _p(out), _p(out_off), _st()),
-          'sug_grid_subsample')
+    check(lib().sug_grid_subsample(_p(pts), _p(off), B, cap, float(dl), rows, level, _p(pad), _p(cnt), _p(out), _p(out_off),
+                                   _p(record), _st()), 'sug_grid_subsample')
     return out, out_off
 
 
 def radius_neighbors(q, qoff, s, soff, radius, limit):
-    """[Nq, limit] int32: per query the first `limit` supports of its cloud (support order) with d^2 < r^2, shadow Ns."""
+    """[Nq, limit] int32: per query the first `limit` supports of its cloud (support order) with d^2 < r^2, the shadow
+    Ns = s.shape[0]; a dead query's row is all shadow."""
     _need_gpu(q, qoff, s, soff)
     q, s = q.detach().contiguous(), s.detach().contiguous()
     out = torch.empty(q.shape[0], limit, dtype=torch.int32, device=q.device)
@@ -4081,7 +4088,8 @@ def radius_neighbors(q, qoff, s, soff, radius, limit):
 
 
 def radius_reverse(nbr, qoff, soff, Ns, cap):
-    """Sorted reverse lists of a neighbour table: (rev_be [Ns,2], rev_ent [Nq*H])."""
+    """Sorted reverse lists of a neighbour table: (rev_be [Ns,2] with empty lists for the dead supports, rev_ent
+    [Nq*H]); cap: no cloud has more supports (the level-0 cloud size will do: no cloud grows)."""
     _need_gpu(nbr, qoff, soff)
     Nq, H = nbr.shape
     be = torch.empty(Ns, 2, dtype=torch.int32, device=nbr.device)
@@ -4093,11 +4101,12 @@ def radius_reverse(nbr, qoff, soff, Ns, cap):
 
 class _KPConvAgg(torch.autograd.Function):
     """wf [Nq, K*Cin]: the influence-weighted neighbour features of every kernel point, divided by the positive-row count
-    (sug_kpconv_fwd); backward dx through the support's reverse lists (sug_kpconv_bwd)."""
+    (sug_kpconv_fwd); backward dx through the support's reverse lists (sug_kpconv_bwd).  qoff's last entry is the number
+    of valid queries (read on the device)."""
 
     @staticmethod
-    def forward(ctx, x, q, s, nbr, kp, extent, rev):
-        _need_gpu(x, q, s, nbr, kp)
+    def forward(ctx, x, q, s, nbr, kp, extent, rev, qoff):
+        _need_gpu(x, q, s, nbr, kp, qoff)
         x = x.contiguous()
         Nq, H = nbr.shape
         K, Cin = kp.shape[0], x.shape[1]
@@ -4105,9 +4114,9 @@ class _KPConvAgg(torch.autograd.Function):
         w = torch.empty(Nq, H, K, dtype=torch.float32, device=x.device)
         cnt = torch.empty(Nq, dtype=torch.float32, device=x.device)
         check(_timed('kpconv_fwd', {'Nq': Nq, 'Cin': Cin},
-                     lambda: lib().sug_kpconv_fwd(_p(q), _p(s), _p(nbr), Nq, H, s.shape[0], _p(kp.detach().contiguous()),
-                                                  K, float(extent), _p(x), Cin, _p(wf), _p(w), _p(cnt), _st())),
-              'sug_kpconv_fwd')
+                     lambda: lib().sug_kpconv_fwd(_p(q), _p(s), _p(nbr), _p(qoff[-1:]), Nq, H, s.shape[0],
+                                                  _p(kp.detach().contiguous()), K, float(extent), _p(x), Cin, _p(wf),
+                                                  _p(w), _p(cnt), _st())), 'sug_kpconv_fwd')
         ctx.save_for_backward(w, cnt)
         ctx.rev, ctx.dims = rev, (H, K, s.shape[0], Cin)
         return wf
@@ -4122,15 +4131,16 @@ class _KPConvAgg(torch.autograd.Function):
         check(_timed('kpconv_bwd', {'Ns': Ns, 'Cin': Cin},
                      lambda: lib().sug_kpconv_bwd(_p(be), _p(ent), H, K, _p(w), _p(cnt), _p(g), Ns, Cin, _p(dx), _st())),
               'sug_kpconv_bwd')
-        return dx, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None
 
 
-def kpconv(x, q, s, nbr, rev, kernel_points, weights, extent):
+def kpconv(x, q, s, nbr, rev, kernel_points, weights, extent, qoff):
     """KPConv (rigid, linear influence, sum): [Nq, Cout] = (wf / count) . W with W [K, Cin, Cout] viewed as [K*Cin, Cout];
-    rev = radius_reverse(nbr, ...)."""
+    rev = radius_reverse(nbr, ...), qoff the query level's offsets.  The GEMM runs on all Nq rows, the dead ones being
+    zero."""
     _need_gpu(x, q, s, nbr, kernel_points, weights)
     K, Cin, Cout = weights.shape
-    wf = _KPConvAgg.apply(x, q, s, nbr, kernel_points, extent, rev)
+    wf = _KPConvAgg.apply(x, q, s, nbr, kernel_points, extent, rev, qoff)
     return linear_rows(wf, weights.view(K * Cin, Cout).t())
 
 
@@ -4139,12 +4149,12 @@ class _SegInstNorm(torch.autograd.Function):
     def forward(ctx, x, off, mode, sc):
         _need_gpu(x, off, sc)
         x = x.contiguous()
-        B, C = off.numel() - 1, x.shape[1]
+        B, (N, C) = off.numel() - 1, x.shape
         y = torch.empty_like(x)
         mean = torch.empty(B, C, dtype=torch.float32, device=x.device)
         rstd = torch.empty(B, C, dtype=torch.float32, device=x.device)
         scc = sc.contiguous() if sc is not None else None
-        check(lib().sug_seg_instnorm_fwd(_p(x), _p(off), B, C, 1e-5, mode, _p(scc), _p(y), _p(mean), _p(rstd), _st()),
+        check(lib().sug_seg_instnorm_fwd(_p(x), _p(off), B, N, C, 1e-5, mode, _p(scc), _p(y), _p(mean), _p(rstd), _st()),
               'sug_seg_instnorm_fwd')
         ctx.save_for_backward(x, y, mean, rstd, off)
         ctx.mode = mode
@@ -4156,14 +4166,15 @@ class _SegInstNorm(torch.autograd.Function):
         g = g.contiguous()
         dx = torch.empty_like(x)
         dsc = torch.empty_like(x) if ctx.mode == 2 else None
-        check(lib().sug_seg_instnorm_bwd(_p(g), _p(y), _p(x), _p(mean), _p(rstd), _p(off), off.numel() - 1, x.shape[1],
-                                         ctx.mode, _p(dx), _p(dsc), _st()), 'sug_seg_instnorm_bwd')
+        check(lib().sug_seg_instnorm_bwd(_p(g), _p(y), _p(x), _p(mean), _p(rstd), _p(off), off.numel() - 1, x.shape[0],
+                                         x.shape[1], ctx.mode, _p(dx), _p(dsc), _st()), 'sug_seg_instnorm_bwd')
         return dx, None, None, dsc
 
 
 def seg_instnorm(x, off, act=False, shortcut=None):
     """Per-cloud InstanceNorm1d of rows x [N, C] (clouds at offsets off), then LeakyReLU(0.1) if act; with a shortcut
-    [N, C]: LeakyReLU(0.1)(norm(x) + shortcut)."""
+    [N, C]: LeakyReLU(0.1)(norm(x) + shortcut).  The dead rows [off[B], N) of the result and of the gradients are zero.
+    An empty cloud normalises nothing (it used to divide by zero where x had exactly off[B] rows)."""
     mode = 2 if shortcut is not None else (1 if act else 0)
     return _SegInstNorm.apply(x, off, mode, shortcut)
 
@@ -4221,143 +4232,9 @@ class _SegMean(torch.autograd.Function):
 
 
 def seg_mean(x, off):
-    """[B, C]: per-cloud mean of the rows x [N, C] (model/KPConv_model.py global_average)."""
+    """[B, C]: per-cloud mean of the rows x [N, C] (model/KPConv_model.py global_average).  An empty cloud's row is zero,
+    with a zero gradient (it used to be NaN where x had exactly off[B] rows)."""
     return _SegMean.apply(x, off)
-
-
-# Capacity forms (kpconv.hip, "CAPACITY LAYOUT"): every level tensor has a static number of rows, of which the first
-# off[B] are valid and the rest exactly zero; the valid counts are read on the device, so nothing here waits for the host
-# and the launch sequence of a forward + backward is static.  sug_kpconv_bwd / sug_seg_max_pool_* serve both layouts.
-KPCONV_RECORD_INTS = _H['SUG_KPCONV_RECORD_INTS']
-
-
-def kp_grid_subsample_cap(pts, off, B, cap, dl, C, record, level):
-    """kp_grid_subsample into a buffer of C rows: (points [C,3] with zero dead rows, offsets [B+1] clamped to C); the
-    unclamped total goes into `record` (int32 [KPCONV_RECORD_INTS]) at `level` (0 = the first pooled level)."""
-    _need_gpu(pts, off, record)
-    pts = pts.detach().contiguous()
-    pad = torch.empty(B, cap, 3, dtype=torch.float32, device=pts.device)
-    cnt = torch.empty(B, dtype=torch.int32, device=pts.device)
-    out = torch.empty(C, 3, dtype=torch.float32, device=pts.device)
-    out_off = torch.empty(B + 1, dtype=torch.int32, device=pts.device)
-    check(lib().sug_grid_subsample_cap(_p(pts), _p(off), B, cap, float(dl), C, level, _p(pad), _p(cnt), _p(out), _p(out_off),
-                                       _p(record), _st()), 'sug_grid_subsample_cap')
-    return out, out_off
-
-
-def radius_neighbors_cap(q, qoff, s, soff, radius, limit):
-    """[Cq, limit] int32 at capacity: the shadow index is Cs = s.shape[0]; a dead query's row is all shadow."""
-    _need_gpu(q, qoff, s, soff)
-    q, s = q.detach().contiguous(), s.detach().contiguous()
-    out = torch.empty(q.shape[0], limit, dtype=torch.int32, device=q.device)
-    check(lib().sug_radius_neighbors_cap(_p(q), _p(qoff), q.shape[0], _p(s), _p(soff), s.shape[0], qoff.numel() - 1,
-                                         float(radius), limit, _p(out), _st()), 'sug_radius_neighbors_cap')
-    return out
-
-
-def radius_reverse_cap(nbr, qoff, soff, Cs, cap):
-    """Sorted reverse lists at capacity: (rev_be [Cs,2] with empty lists for the dead supports, rev_ent [Cq*H]); cap: the
-    level-0 cloud size (no cloud grows)."""
-    _need_gpu(nbr, qoff, soff)
-    Cq, H = nbr.shape
-    be = torch.empty(Cs, 2, dtype=torch.int32, device=nbr.device)
-    ent = torch.empty(max(1, Cq * H), dtype=torch.int32, device=nbr.device)
-    check(lib().sug_radius_reverse_cap(_p(nbr), _p(qoff), _p(soff), qoff.numel() - 1, H, Cs, cap, _p(be), _p(ent), _st()),
-          'sug_radius_reverse_cap')
-    return be, ent
-
-
-class _KPConvAggCap(torch.autograd.Function):
-    """_KPConvAgg at capacity: qoff's last entry is the number of valid queries (read on the device)."""
-
-    @staticmethod
-    def forward(ctx, x, q, s, nbr, kp, extent, rev, qoff):
-        _need_gpu(x, q, s, nbr, kp, qoff)
-        x = x.contiguous()
-        Cq, H = nbr.shape
-        K, Cin = kp.shape[0], x.shape[1]
-        wf = torch.empty(Cq, K * Cin, dtype=torch.float32, device=x.device)
-        w = torch.empty(Cq, H, K, dtype=torch.float32, device=x.device)
-        cnt = torch.empty(Cq, dtype=torch.float32, device=x.device)
-        check(_timed('kpconv_fwd', {'Nq': Cq, 'Cin': Cin},
-                     lambda: lib().sug_kpconv_fwd_cap(_p(q), _p(s), _p(nbr), _p(qoff[-1:]), Cq, H, s.shape[0],
-                                                      _p(kp.detach().contiguous()), K, float(extent), _p(x), Cin, _p(wf),
-                                                      _p(w), _p(cnt), _st())), 'sug_kpconv_fwd_cap')
-        ctx.save_for_backward(w, cnt)
-        ctx.rev, ctx.dims = rev, (H, K, s.shape[0], Cin)
-        return wf
-
-    @staticmethod
-    def backward(ctx, g):
-        return _KPConvAgg.backward(ctx, g) + (None,)
-
-
-def kpconv_cap(x, q, s, nbr, rev, kernel_points, weights, extent, qoff):
-    """kpconv at capacity (q / nbr [Cq, ...], x / s [Cs, ...]); the GEMM runs on all Cq rows, the dead ones being zero."""
-    _need_gpu(x, q, s, nbr, kernel_points, weights)
-    K, Cin, Cout = weights.shape
-    wf = _KPConvAggCap.apply(x, q, s, nbr, kernel_points, extent, rev, qoff)
-    return linear_rows(wf, weights.view(K * Cin, Cout).t())
-
-
-class _SegInstNormCap(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, off, mode, sc):
-        _need_gpu(x, off, sc)
-        x = x.contiguous()
-        B, (N, C) = off.numel() - 1, x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        scc = sc.contiguous() if sc is not None else None
-        check(lib().sug_seg_instnorm_fwd_cap(_p(x), _p(off), B, N, C, 1e-5, mode, _p(scc), _p(y), _p(mean), _p(rstd), _st()),
-              'sug_seg_instnorm_fwd_cap')
-        ctx.save_for_backward(x, y, mean, rstd, off)
-        ctx.mode = mode
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y, mean, rstd, off = ctx.saved_tensors
-        g = g.contiguous()
-        dx = torch.empty_like(x)
-        dsc = torch.empty_like(x) if ctx.mode == 2 else None
-        check(lib().sug_seg_instnorm_bwd_cap(_p(g), _p(y), _p(x), _p(mean), _p(rstd), _p(off), off.numel() - 1, x.shape[0],
-                                             x.shape[1], ctx.mode, _p(dx), _p(dsc), _st()), 'sug_seg_instnorm_bwd_cap')
-        return dx, None, None, dsc
-
-
-def seg_instnorm_cap(x, off, act=False, shortcut=None):
-    """seg_instnorm at capacity: x [C_l, C] with valid rows [0, off[B]); the dead rows of the result are zero."""
-    mode = 2 if shortcut is not None else (1 if act else 0)
-    return _SegInstNormCap.apply(x, off, mode, shortcut)
-
-
-class _SegMeanCap(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, off):
-        _need_gpu(x, off)
-        x = x.contiguous()
-        B, C = off.numel() - 1, x.shape[1]
-        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        check(lib().sug_seg_mean_fwd_cap(_p(x), _p(off), B, C, _p(y), _st()), 'sug_seg_mean_fwd_cap')
-        ctx.save_for_backward(off)
-        ctx.N = x.shape[0]
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        (off,) = ctx.saved_tensors
-        g = g.contiguous()
-        B, C = g.shape
-        dx = torch.empty(ctx.N, C, dtype=torch.float32, device=g.device)
-        check(lib().sug_seg_mean_bwd_cap(_p(g), _p(off), B, ctx.N, C, _p(dx), _st()), 'sug_seg_mean_bwd_cap')
-        return dx, None
-
-
-def seg_mean_cap(x, off):
-    """seg_mean at capacity; an empty cloud's row is zero, with a zero gradient."""
-    return _SegMeanCap.apply(x, off)
 
 
 def kp_sample_rows(x, off, sampled_len=64):

@@ -124,7 +124,7 @@ def test_python_constants_are_the_headers():
     """The Python names that mirror a #define are read from the header (the literals below restate it on purpose)."""
     from sug_amd import _lib, ops, optim
     H = _lib.CONSTANTS
-    assert H['SUG_ABI_VERSION'] == 7 and H['SUG_ERR_ARG'] == -1 and H['SUG_PREP_DRAW_NOISE'] == 0x20000000
+    assert H['SUG_ABI_VERSION'] == 8 and H['SUG_ERR_ARG'] == -1 and H['SUG_PREP_DRAW_NOISE'] == 0x20000000
     assert _lib.STATS_BLOCKS == H['SUG_STATS_BLOCKS'] == 1024
     assert (optim.CHAIN_SLOTS, optim.CHAIN_BUCKETS) == (2, 8)
     assert (ops.EVAL_MAX_ROWS, ops.EVAL_MAX_CLASSES, ops.EVAL_BATCH_COUNT, ops.EVAL_DATA_TOTAL, ops.EVAL_CORRECT_TOTAL,

@@ -176,7 +176,7 @@ def test_header_constants_equal_ops():
     assert (H['SUG_PREP_DRAW_ANGLE'], H['SUG_PREP_DRAW_SUBSET'], H['SUG_PREP_DRAW_NOISE']) == (C.DRAW_ANGLE, C.DRAW_SUBSET, C.DRAW_NOISE)
     assert ops.PREP_AUG_PARAMS == H['SUG_PREP_AUG_PARAMS'] == 5
     assert sorted(H['SUG_PREP_AUG_' + n] for n in ('SCALE_LOW', 'SCALE_HIGH', 'SHIFT_RANGE', 'ANGLE_SIGMA', 'ANGLE_CLIP')) == list(range(5))
-    assert H['SUG_ABI_VERSION'] == 7                                                # additive: the version does not move
+    assert H['SUG_ABI_VERSION'] == 8                                                # additive: the version does not move
     P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     assert _lib.DECLARATIONS['sug_prepare_batch_aug'] == (ctypes.c_int, [P, I, I, P, I, I, I] + [P] * 7 + [ctypes.c_uint64, P, F, F, P]
                                                           + [P] * 8)

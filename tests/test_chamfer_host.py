@@ -94,7 +94,7 @@ def test_new_symbols_are_bound_with_their_types():
     P, I = ctypes.c_void_p, ctypes.c_int
     assert _lib.SIGNATURES['sug_chamfer_nn'] == [P, P, I, I, I, P, P, P, P, P]
     assert _lib.SIGNATURES['sug_chamfer_nn_bwd'] == [P, P, P, P, P, P, I, I, I, P, P, P]
-    assert _lib.CONSTANTS['SUG_CHAMFER_MAX_POINTS'] == 5000 and _lib.CONSTANTS['SUG_ABI_VERSION'] == 7
+    assert _lib.CONSTANTS['SUG_CHAMFER_MAX_POINTS'] == 5000 and _lib.CONSTANTS['SUG_ABI_VERSION'] == 8
     L = _lib.lib()
     assert hasattr(L, 'sug_chamfer_nn') and hasattr(L, 'sug_chamfer_nn_bwd')
 

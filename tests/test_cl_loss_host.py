@@ -146,12 +146,12 @@ def test_header_ctypes_table_and_python_limits_agree():
     H = _lib.CONSTANTS
     assert (ops.CL_LOSS_MAX_ROWS, ops.CL_LOSS_MAX_D, ops.CL_LOSS_MAX_TERMS) == \
         (H['SUG_CL_LOSS_MAX_ROWS'], H['SUG_CL_LOSS_MAX_D'], H['SUG_CL_LOSS_MAX_TERMS']) == (1024, 1 << 20, 4)
-    assert (H['SUG_CL_LOSS_SUM_FIELDS'], H['SUG_CL_LOSS_ROW_FIELDS'], H['SUG_ABI_VERSION']) == (3, 4, 7)
+    assert (H['SUG_CL_LOSS_SUM_FIELDS'], H['SUG_CL_LOSS_ROW_FIELDS'], H['SUG_ABI_VERSION']) == (3, 4, 8)
     vp, i32 = ctypes.c_void_p, ctypes.c_int
     want = {'sug_cl_loss_fwd': [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
             'sug_cl_loss_bwd': [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]}
     L = _lib.lib()
-    assert L.sug_abi_version() == 7
+    assert L.sug_abi_version() == 8
     for name, args in want.items():
         assert _lib.SIGNATURES[name] == args, name
         assert getattr(L, name).argtypes == args

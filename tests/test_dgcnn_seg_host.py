@@ -18,9 +18,9 @@ def test_header_declares_the_entry_points_and_keeps_the_abi_version():
     from sug_amd import _lib
     for name in ENTRY_POINTS:
         assert name in _lib.DECLARATIONS, name
-    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 7
+    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 8
     text = open(os.path.join(ROOT, 'include', 'sug_amd.h')).read()
-    assert re.search(r'#define\s+SUG_ABI_VERSION\s+7\b', text)
+    assert re.search(r'#define\s+SUG_ABI_VERSION\s+8\b', text)
     # the short-segment layer takes the arguments of its long-segment sibling
     assert _lib.DECLARATIONS['sug_edgemlp_max_layer_fwd_xf'] == _lib.DECLARATIONS['sug_pointmlp_max_layer_fwd_xf']
     src = open(os.path.join(ROOT, 'sug_amd', 'csrc', 'edgemlp.hip')).read()

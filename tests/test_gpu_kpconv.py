@@ -136,7 +136,7 @@ def test_kpconv_op_against_fp64(Cin):
     n32 = nbr.to(torch.int32).to(DEV)
     rev = ops.radius_reverse(n32, o, o, pts.shape[0], max(lens))
     xg, Wg = x.to(DEV).requires_grad_(True), W.to(DEV).requires_grad_(True)
-    y = ops.kpconv(xg, q, q, n32, rev, kp.to(DEV), Wg, extent)
+    y = ops.kpconv(xg, q, q, n32, rev, kp.to(DEV), Wg, extent, o)
     y.backward(gy.to(DEV))
     scale = outd.abs().max().item()
     assert (y.detach().cpu().double() - outd.detach()).abs().max().item() <= 2e-6 * max(1.0, scale)

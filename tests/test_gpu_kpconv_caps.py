@@ -1,6 +1,6 @@
-"""GPU: the KPConv capacity layout (sug_amd/csrc/kpconv.hip "CAPACITY LAYOUT") -- the pyramid at
-capacity against the reference's pyramid, every capacity op against its exact-size twin on NaN-padded buffers, the models
-with level caps against the goldens, one hipGraph over preprocessing + forward + backward replayed on a batch of other
+"""GPU: the KPConv row layout with dead rows (sug_amd/csrc/kpconv.hip "ROW LAYOUT") -- the pyramid at
+capacity against the reference's pyramid, every op on a NaN-padded buffer against itself on a tight one, the reference's
+KPConv call, the models with level caps against the goldens, one hipGraph over preprocessing + forward + backward replayed on a batch of other
 level sizes, SourceStep / SUGStep / eval_graphs replay against eager launches, and the overflow contract (last)."""
 import hashlib
 import os
@@ -141,13 +141,14 @@ def _rand(g, *shape):
 
 
 def _tables(pts, off, n, r, H):
-    """(exact table, exact reverse lists, capacity table, capacity reverse lists) of one level against itself."""
+    """(tight table, tight reverse lists, padded table, padded reverse lists) of one level against itself: the n rows
+    alone, and in a buffer of CAP rows whose dead rows are NaN."""
     from sug_amd import ops
     nbr = ops.radius_neighbors(pts, off, pts, off, r, H)
     rev = ops.radius_reverse(nbr, off, off, n, max(LENS))
     pc = _pad(pts)
-    nbc = ops.radius_neighbors_cap(pc, off, pc, off, r, H)
-    revc = ops.radius_reverse_cap(nbc, off, off, CAP, max(LENS))
+    nbc = ops.radius_neighbors(pc, off, pc, off, r, H)
+    revc = ops.radius_reverse(nbc, off, off, CAP, max(LENS))
     return nbr, rev, nbc, revc
 
 
@@ -159,7 +160,7 @@ def test_tables_and_reverse_lists_on_uneven_clouds():
     assert bool((nbc[n:] == CAP).all())                     # dead queries: all shadow
     assert not bool(((v >= n) & (v < CAP)).any())
     v[v == CAP] = n
-    assert torch.equal(v, nbr)
+    assert torch.equal(v, nbr) and int(nbr.max()) <= n      # (the tight table's shadow is n)
     assert torch.equal(bec[:n], be)                         # the same lists at the same places
     assert bool((bec[n:, 0] == bec[n:, 1]).all())           # dead supports: empty
     be_h, ent_h, entc_h = be.cpu(), ent.cpu(), entc.cpu()
@@ -180,11 +181,17 @@ def test_kpconv_cap_on_uneven_clouds(Cin):
     extent = r * 1.2 / 2.5
     # the aggregation kernels: bit-equal valid rows, zero dead rows, NaN in every dead input row (x, q, s, dwf)
     xe = x.clone().requires_grad_(True)
-    wf = ops._KPConvAgg.apply(xe, pts, pts, nbr, kp, extent, rev)
+    wf = ops._KPConvAgg.apply(xe, pts, pts, nbr, kp, extent, rev, off)
+    w, cnt = wf.grad_fn.saved_tensors
     wf.backward(gw)
     xc = _pad(x).requires_grad_(True)
     pc = _pad(pts)
-    wfc = ops._KPConvAggCap.apply(xc, pc, pc, nbc, kp, extent, revc, off)
+    wfc = ops._KPConvAgg.apply(xc, pc, pc, nbc, kp, extent, revc, off)
+    wc, cntc = wfc.grad_fn.saved_tensors
+    # rows 96..103 are one tile of the kernel: three live queries, five dead ones (the dead queries of a LIVE tile)
+    assert n == 99 and torch.equal(wc[:n], w) and torch.equal(cntc[:n], cnt)
+    assert bool((cntc[n:104] == 1).all()) and not bool(wc[n:104].any())
+    assert bool((cntc[104:] == 1).all()) and not bool(wc[104:].any())       # the wholly dead tiles
     wfc.backward(_pad(gw))
     assert torch.equal(wfc[:n].detach(), wf.detach()) and not bool(wfc[n:].detach().any())
     assert torch.equal(xc.grad[:n], xe.grad) and not bool(xc.grad[n:].any())
@@ -196,11 +203,11 @@ def test_kpconv_cap_on_uneven_clouds(Cin):
     gy = _rand(g, n, Cout)
     We = W.clone().requires_grad_(True)
     xe = x.clone().requires_grad_(True)
-    y = ops.kpconv(xe, pts, pts, nbr, rev, kp, We, extent)
+    y = ops.kpconv(xe, pts, pts, nbr, rev, kp, We, extent, off)
     y.backward(gy)
     Wc = W.clone().requires_grad_(True)
     xc = _pad(x, fill=0.0).requires_grad_(True)             # invariant 1 holds for what the GEMM reads
-    yc = ops.kpconv_cap(xc, pc, pc, nbc, revc, kp, Wc, extent, off)
+    yc = ops.kpconv(xc, pc, pc, nbc, revc, kp, Wc, extent, off)
     yc.backward(_pad(gy, fill=0.0))
     assert not bool(yc[n:].detach().any()) and not bool(xc.grad[n:].any())
     for a, b in ((yc[:n].detach(), y.detach()), (xc.grad[:n], xe.grad), (Wc.grad, We.grad)):
@@ -219,7 +226,7 @@ def test_seg_instnorm_cap_on_uneven_clouds(mode):
     y.backward(gy)
     xc = _pad(x).requires_grad_(True)
     scc = _pad(sc).requires_grad_(True) if mode == 2 else None
-    yc = ops.seg_instnorm_cap(xc, off, act=mode == 1, shortcut=scc)
+    yc = ops.seg_instnorm(xc, off, act=mode == 1, shortcut=scc)
     yc.backward(_pad(gy))
     assert torch.equal(yc[:n].detach(), y.detach()) and not bool(yc[n:].detach().any())
     assert torch.equal(xc.grad[:n], xe.grad) and not bool(xc.grad[n:].any())
@@ -247,7 +254,7 @@ def test_max_pool_mean_and_node_sampling_on_uneven_clouds():
     m = ops.seg_mean(xe, off)
     m.backward(gm)
     xc = _pad(x).requires_grad_(True)
-    mc = ops.seg_mean_cap(xc, off)
+    mc = ops.seg_mean(xc, off)
     mc.backward(gm)
     assert torch.equal(mc.detach(), m.detach())
     assert torch.equal(xc.grad[:n], xe.grad) and not bool(xc.grad[n:].any())
@@ -256,7 +263,7 @@ def test_max_pool_mean_and_node_sampling_on_uneven_clouds():
 
 def test_empty_cloud_and_long_clouds():
     """Clouds [130, 0, 64] in 256 rows: the empty cloud normalises nothing, its mean row and node rows are zero; the other
-    clouds equal the exact-size ops on [130, 64]; node sampling takes the stride rule for n >= 64."""
+    clouds equal the ops on the tight clouds [130, 64]; node sampling takes the stride rule for n >= 64."""
     from sug_amd import ops
     from sug_amd.model.KPConv_blocks import sample_tensor_slices
     g = torch.Generator().manual_seed(9)
@@ -268,7 +275,7 @@ def test_empty_cloud_and_long_clouds():
     y = ops.seg_instnorm(xe, off2, act=True)
     y.backward(gy)
     xc = _pad(x, 256).requires_grad_(True)
-    yc = ops.seg_instnorm_cap(xc, off, act=True)
+    yc = ops.seg_instnorm(xc, off, act=True)
     yc.backward(_pad(gy, 256))
     assert torch.equal(yc[:n].detach(), y.detach()) and not bool(yc[n:].detach().any())
     assert torch.equal(xc.grad[:n], xe.grad) and not bool(xc.grad[n:].any())
@@ -276,12 +283,53 @@ def test_empty_cloud_and_long_clouds():
     m = ops.seg_mean(xe, off2)
     m.backward(gm[[0, 2]])
     xc = _pad(x, 256).requires_grad_(True)
-    mc = ops.seg_mean_cap(xc, off)
+    mc = ops.seg_mean(xc, off)
     mc.backward(gm)
     assert torch.equal(mc[[0, 2]].detach(), m.detach()) and not bool(mc[1].detach().any())
     assert torch.equal(xc.grad[:n], xe.grad) and not bool(xc.grad[n:].any())
     s = ops.kp_sample_rows(_pad(x, 256), off)
     assert torch.equal(s[[0, 2]], sample_tensor_slices(x, [130, 64])) and not bool(s[1].any())
+
+
+def test_grid_subsample_tight_against_capacity_buffer():
+    """One subsample, twice: into a buffer of as many rows as went in, without a record, and into one of CAP rows with a
+    record.  The same offsets and valid rows, zero rows past the total in both, the total in the record."""
+    from sug_amd import ops
+    pts, off, n, _ = _case(2)
+    B, dl = len(LENS), 0.08
+    pt, ot = ops.kp_grid_subsample(pts, off, B, max(LENS), dl)
+    rec = torch.zeros(ops.KPCONV_RECORD_INTS, dtype=torch.int32, device=DEV)
+    pc, oc = ops.kp_grid_subsample(pts, off, B, max(LENS), dl, rows=CAP, record=rec, level=0)
+    cnt = np.diff(ot.cpu().numpy())
+    total = int(cnt.sum())
+    assert all(0 < c < l for c, l in zip(cnt[[0, 2]], (LENS[0], LENS[2]))) and 0 < cnt[1] <= LENS[1] and total < n   # they shrink
+    assert torch.equal(ot, oc)
+    assert pt.shape == (n, 3) and pc.shape == (CAP, 3)
+    assert torch.equal(pt[:total], pc[:total]) and bool(pt[:total].any())
+    assert not bool(pt[total:].any()) and not bool(pc[total:].any())
+    r = rec.tolist()
+    assert r[0] == total and r[4] == 0
+
+
+def test_reference_style_kpconv_call():
+    """KPConv.forward(q, s, nbr, x) as the reference calls it -- no reverse lists, no offsets: one cloud's tables.  Value
+    and input gradient equal ops.kpconv with the one-cloud offsets and lists spelled out."""
+    from sug_amd import ops
+    from sug_amd.model.KPConv_blocks import KPConv
+    n, H, Cin, Cout, r = 60, 12, 16, 24, 0.08
+    pts, off, _, g = _case(3, lens=[n])
+    nbr = ops.radius_neighbors(pts, off, pts, off, r, H)
+    torch.manual_seed(0)
+    conv = KPConv(15, 3, Cin, Cout, r * 1.2 / 2.5, r).to(DEV)
+    x, gy = _rand(g, n, Cin), _rand(g, n, Cout)
+    xa = x.clone().requires_grad_(True)
+    ya = conv(pts, pts, nbr.long(), xa)                     # (the reference's tables are int64)
+    ya.backward(gy)
+    xb = x.clone().requires_grad_(True)
+    rev = ops.radius_reverse(nbr, off, off, n, n)
+    yb = ops.kpconv(xb, pts, pts, nbr, rev, conv.kernel_points, conv.weights, conv.KP_extent, off)
+    yb.backward(gy)
+    assert bool(ya.detach().any()) and torch.equal(ya.detach(), yb.detach()) and torch.equal(xa.grad, xb.grad)
 
 
 # ----------------------------------------------------------------------------------------------- 3. model parity

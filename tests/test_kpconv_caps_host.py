@@ -1,12 +1,13 @@
 """CPU: the host side of the KPConv capacity layout -- the capacity formula, the validation of set_level_caps, the
-graph_capturable flag following the caps, the refusals that stay, and the declared / exported capacity symbols."""
+graph_capturable flag following the caps, the refusals that stay, and the declared / exported symbols of the one row
+layout (the capacity signatures under the unsuffixed names)."""
 import ctypes
 
 import pytest
 import torch
 
-CAP_SYMBOLS = ('sug_grid_subsample_cap', 'sug_radius_neighbors_cap', 'sug_radius_reverse_cap', 'sug_kpconv_fwd_cap',
-               'sug_seg_instnorm_fwd_cap', 'sug_seg_instnorm_bwd_cap', 'sug_seg_mean_fwd_cap', 'sug_seg_mean_bwd_cap',
+CAP_SYMBOLS = ('sug_grid_subsample', 'sug_radius_neighbors', 'sug_radius_reverse', 'sug_kpconv_fwd',
+               'sug_seg_instnorm_fwd', 'sug_seg_instnorm_bwd', 'sug_seg_mean_fwd', 'sug_seg_mean_bwd',
                'sug_kp_sample_rows')
 
 
@@ -99,16 +100,24 @@ def test_capacity_symbols_declared_and_exported():
     for name in CAP_SYMBOLS:
         assert name in _lib.SIGNATURES, name
     assert _lib.CONSTANTS['SUG_KPCONV_RECORD_INTS'] == 8
-    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 7           # additive: the version stays
+    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 8           # signatures changed, the *_cap twins are gone
     L = ctypes.CDLL(_lib.LIB_PATH)
     for name in CAP_SYMBOLS:
         assert hasattr(L, name), name
+        if name != 'sug_kp_sample_rows':
+            assert name + '_cap' not in _lib.SIGNATURES and not hasattr(L, name + '_cap'), name
     # bad arguments are refused on the host, before any launch
     p = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(64)))
     B = _lib.lib()
-    assert B.sug_grid_subsample_cap(p, p, 2, 8, 0.1, 17, 0, p, p, p, p, p, None) != 0      # capacity above B*cap
-    assert B.sug_grid_subsample_cap(p, p, 2, 8, 0.1, 16, 4, p, p, p, p, p, None) != 0      # level outside the record
-    assert B.sug_kpconv_fwd_cap(p, p, p, None, 8, 4, 8, p, 15, 0.1, p, 4, p, p, p, None) != 0   # no valid-count pointer
+    assert B.sug_grid_subsample(p, p, 2, 8, 0.1, 17, 0, p, p, p, p, p, None) != 0      # capacity above B*cap
+    assert B.sug_grid_subsample(p, p, 2, 8, 0.1, 16, 4, p, p, p, p, p, None) != 0      # level outside the record
+    assert b'level 4 outside' in B.sug_last_error()
+    assert B.sug_kpconv_fwd(p, p, p, None, 8, 4, 8, p, 15, 0.1, p, 4, p, p, p, None) != 0   # no valid-count pointer
+    # a null record with any level passes the argument check: the refusal is the NEXT check's (dl, which nothing launches)
+    assert B.sug_grid_subsample(p, p, 2, 8, 0.0, 16, 7, p, p, p, p, None, None) == _lib.CONSTANTS['SUG_ERR_ARG']
+    assert b'dl must be positive' in B.sug_last_error()
+    assert B.sug_grid_subsample(p, p, 2, 8, 0.0, 16, 7, p, p, p, p, p, None) != 0
+    assert b'level 7 outside' in B.sug_last_error()
 
 
 def test_capacity_ops_refuse_cpu_tensors():
@@ -119,16 +128,16 @@ def test_capacity_ops_refuse_cpu_tensors():
     nbr = torch.zeros(8, 4, dtype=torch.int32)
     rec = torch.zeros(8, dtype=torch.int32)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.kp_grid_subsample_cap(p, off, 1, 8, 0.1, 8, rec, 0)
+        ops.kp_grid_subsample(p, off, 1, 8, 0.1, 8, rec, 0)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.radius_neighbors_cap(p, off, p, off, 0.1, 4)
+        ops.radius_neighbors(p, off, p, off, 0.1, 4)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.radius_reverse_cap(nbr, off, off, 8, 8)
+        ops.radius_reverse(nbr, off, off, 8, 8)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.kpconv_cap(x, p, p, nbr, None, torch.zeros(15, 3), torch.zeros(15, 4, 4), 0.02, off)
+        ops.kpconv(x, p, p, nbr, None, torch.zeros(15, 3), torch.zeros(15, 4, 4), 0.02, off)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.seg_instnorm_cap(x, off, act=True)
+        ops.seg_instnorm(x, off, act=True)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.seg_mean_cap(x, off)
+        ops.seg_mean(x, off)
     with pytest.raises(RuntimeError, match='HIP device'):
         ops.kp_sample_rows(x, off)

@@ -90,7 +90,7 @@ def test_kpconv_ops_refuse_cpu_tensors():
     with pytest.raises(RuntimeError, match='HIP device'):
         ops.radius_reverse(nbr, off, off, 8, 8)
     with pytest.raises(RuntimeError, match='HIP device'):
-        ops.kpconv(x, p, p, nbr, None, torch.zeros(15, 3), torch.zeros(15, 4, 4), 0.02)
+        ops.kpconv(x, p, p, nbr, None, torch.zeros(15, 3), torch.zeros(15, 4, 4), 0.02, off)
     with pytest.raises(RuntimeError, match='HIP device'):
         ops.seg_instnorm(x, off, act=True)
     with pytest.raises(RuntimeError, match='HIP device'):

@@ -42,7 +42,7 @@ def test_header_ctypes_table_and_python_limits_agree():
     assert (ops.MMD_EST_MAX_ROWS, ops.MMD_EST_MAX_D, ops.MMD_EST_MAX_SIGMAS, ops.MMD_POLY_MAX_DEGREE) == \
         (H['SUG_MMD_EST_MAX_ROWS'], H['SUG_MMD_EST_MAX_D'], H['SUG_MMD_EST_MAX_SIGMAS'], H['SUG_MMD_POLY_MAX_DEGREE']) == \
         (1024, 1 << 20, 8, 8)
-    assert (H['SUG_MMD_RATIO_ROW_FIELDS'], H['SUG_MMD_RATIO_STATS'], H['SUG_ABI_VERSION']) == (9, 16, 7)
+    assert (H['SUG_MMD_RATIO_ROW_FIELDS'], H['SUG_MMD_RATIO_STATS'], H['SUG_ABI_VERSION']) == (9, 16, 8)
     vp, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
     want = {
         'sug_mmd_ratio_fwd': [vp, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],

@@ -91,7 +91,7 @@ def test_header_constants_and_bindings():
     assert 'int sug_pfh_descriptors(const float* pts, int M, int N, double rad, int nneighbors, int div,' in header
     assert 'int sug_pfh_hist_distance(const double* histS, const int32_t* cntS, int64_t src_batch_stride,' in header
     H = _lib.CONSTANTS
-    assert (H['SUG_PFH_MAX_POINTS'], H['SUG_PFH_MAX_NEIGHBORS'], H['SUG_ABI_VERSION']) == (1024, 16, 7)
+    assert (H['SUG_PFH_MAX_POINTS'], H['SUG_PFH_MAX_NEIGHBORS'], H['SUG_ABI_VERSION']) == (1024, 16, 8)
     assert (ops.PFH_MAX_POINTS, ops.PFH_MAX_NEIGHBORS) == (1024, 16)
     P, I, L, Dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
     assert _lib.DECLARATIONS['sug_pfh_descriptors'] == (I, [P, I, I, Dbl, I, I, P, P, P, P, P, P])

@@ -61,7 +61,7 @@ def test_new_entry_points_are_declared():
     for n in NEW_SYMBOLS:
         assert n in _lib.DECLARATIONS and _lib.DECLARATIONS[n][0] is ctypes.c_int, n + ' is not declared in include/sug_amd.h'
         assert n in _lib.SIGNATURES, n + ' is not in _lib.SIGNATURES'
-    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 7
+    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 8
 
 
 def test_classes_refuse_cpu_tensors():

@@ -17,7 +17,7 @@ def test_header_declares_the_entry_points_and_the_limits():
     assert _lib.CONSTANTS['SUG_REV_TILED_MAX_DEST'] >= 32768
     assert _lib.CONSTANTS['SUG_REV_TILED_MAX_ENTRIES'] >= 2 ** 21
     assert _lib.CONSTANTS['SUG_REV_TILED_MAX_TILE'] % 1024 == 0 and _lib.CONSTANTS['SUG_REV_TILED_MAX_TILE'] >= 2048
-    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 7 == _lib.lib().sug_abi_version()
+    assert _lib.CONSTANTS['SUG_ABI_VERSION'] == 8 == _lib.lib().sug_abi_version()
     for name in ('sug_reverse_lists_tiled_supported', 'sug_reverse_lists_tiled'):
         assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name)
 

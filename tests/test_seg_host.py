@@ -99,7 +99,7 @@ def test_reference_runs_agree_on_every_index_list():
 def test_header_constants_and_abi_version():
     from sug_amd import _lib, ops
     H = _lib.CONSTANTS
-    assert H['SUG_ABI_VERSION'] == 7
+    assert H['SUG_ABI_VERSION'] == 8
     assert H['SUG_POINT_CE_MAX_ROWS'] >= 1 << 22 and H['SUG_POINT_CE_MAX_CLASSES'] == 64
     assert H['SUG_POINT_CE_BLOCK_ROWS'] == ops.POINT_CE_BLOCK_ROWS >= 64
     assert H['SUG_SEG_MAX_PARTS'] == 64 and H['SUG_SEG_MAX_CATEGORIES'] == 64

@@ -16,7 +16,7 @@ def test_header_declares_the_entry_point_and_constants():
     from sug_amd import _lib, ops
     from sug_amd._lib import SIGNATURES, DECLARATIONS, _vp, _i32, _f32
     H = _lib.CONSTANTS
-    assert H['SUG_ABI_VERSION'] == 7
+    assert H['SUG_ABI_VERSION'] == 8
     assert (H['SUG_PREP_NORMALS'], H['SUG_PREP_DRAW_FILL'], H['SUG_PREP_SEG_MAX_EXTRA']) == (128, 0x60000000, 8)
     assert (ops.PREP_NORMALS, ops.PREP_SEG_MAX_EXTRA) == (128, 8)
     old = [H['SUG_PREP_' + n] for n in ('NORMALIZE', 'ROTATE_Z', 'JITTER', 'SHUFFLE', 'SCALE', 'PERTURB', 'SHIFT')]
