@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added; 8: the KPConv entry points keep one row layout -- the eight sug_*_cap twins are gone, sug_grid_subsample takes C, level and the nullable record, sug_kpconv_fwd takes nq_valid, sug_seg_instnorm_fwd / _bwd take N). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added; 8: the KPConv entry points keep one row layout -- the eight sug_*_cap twins are gone, sug_grid_subsample takes C, level and the nullable record, sug_kpconv_fwd takes nq_valid, sug_seg_instnorm_fwd / _bwd take N; still 8 after sug_edgeconv_path was added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 8
 int sug_abi_version(void);
 
@@ -527,6 +527,14 @@ int sug_edgeconv_layer_fwd(const float* pq, int64_t ldpq, const int32_t* idx, co
                            float eps, float momentum, float slope, float* running_mean,
                            float* running_var, float* z, uint8_t* arg, float* s1, float* coef,
                            float* out, int64_t ldo, double* stats, float* ws, void* stream);
+/* Which kernel the layer above (backward = 0: the gather / reduce of sug_edgeconv_fwd, _fwd_bn and the layer forward,
+ * B = the clouds of the call, i.e. of one group where the layer runs group by group) or sug_edgeconv_layer_bwd's
+ * scatter (backward = 1) takes for a shape: 1 = the LDS-resident kernel (k == 20, Co % 16 == 0 and the cloud's slice
+ * within the LDS budget: N <= 2272 forward, N <= 1094 backward; the backward not with SUG_EDGECONV_BWD_LEGACY in the
+ * environment), 0 = the generic one.  The shape part of the dispatch's own condition -- the dispatch calls the same
+ * function; with pointers that are not 16-byte aligned it takes the generic kernel whatever this says.  Launches
+ * nothing; 0 for a shape with a non-positive extent. */
+int sug_edgeconv_path(int backward, int B, int N, int k, int Co);
 /* The same layer with the 1x1 convolution inside the gather kernel (edgeconv_fused.hip): x [B*N, Cin] rows (row
  * stride ldx; Cin in {3, 64, 128}), wcat [2Co, Cin] = [W1 ; W2-W1] of the layer's weight W = [W1 | W2] [Co, 2Cin]
  * (sug_edge_weight_split), qbias [Co] = the conv bias or NULL.  A workgroup = (cloud, 16-channel slice) forms its

@@ -997,6 +997,33 @@ int sug_stats_finalize(const float* ws, int nblk, int C, const float* gamma, con
   return SUG_OK;
 }
 
+// The shape part of the choice between the LDS-resident kernels and the generic ones, in one place each: the dispatch
+// below and sug_edgeconv_path ask these (the pointer-alignment terms stay with the calls that hold the pointers).
+//   forward: k = 20, whole 16-channel slices, the [N][16] P image + the reduction scratch within 150 KB of LDS
+//   (N <= 2272), one partial row per (cloud, part) within the statistics workspace
+static bool fwd_lds_shape(int B, int N, int k, int Co) {
+#ifdef SUG_EDGECONV_NO_LDS
+  return false;
+#else
+  return k == 20 && Co % 16 == 0 && (size_t)N * 16 * 4 + 64 * 32 * 4 <= 150 * 1024 && B <= SUG_STATS_BLOCKS / 4;
+#endif
+}
+//   backward: k = 20, whole slices, the a | Q | arg images, the histogram and the visiting order within 158 KB
+//   (N <= 1094); SUG_EDGECONV_BWD_LEGACY in the environment (read at every call) selects the generic scatter
+static size_t bwd_lds_bytes(int N) { return (size_t)N * 16 * 9 + 512 * sizeof(int) + (size_t)N * sizeof(uint16_t); }
+static bool bwd_lds_shape(int N, int k, int Co) {
+#ifdef SUG_EDGECONV_NO_LDS
+  return false;
+#else
+  return k == 20 && Co % 16 == 0 && N <= 65535 && bwd_lds_bytes(N) <= 158 * 1024 && !getenv("SUG_EDGECONV_BWD_LEGACY");
+#endif
+}
+
+extern "C" int sug_edgeconv_path(int backward, int B, int N, int k, int Co) {
+  if (B <= 0 || N <= 0 || k <= 0 || Co <= 0) return 0;
+  return backward ? bwd_lds_shape(N, k, Co) : fwd_lds_shape(B, N, k, Co);
+}
+
 // producer only: per-workgroup partial rows in ws, their number in *nblk
 // Bg > 0: sums about the pivot of each domain group of Bg clouds (LDS-resident kernel only; the caller folds with
 // sug_edgeconv_bn_act, which reads the pivot rows); Bg = 0: plain sums
@@ -1011,10 +1038,8 @@ static int edgeconv_fwd_partials(const float* pq, int64_t ldpq, const int32_t* i
                   (!s1 || ((uintptr_t)s1 % 16) == 0) && ((uintptr_t)arg % 4) == 0,
               "sug_edgeconv_fwd: pointers must be 16-byte aligned");
   hipStream_t st_ = (hipStream_t)stream;
-#ifndef SUG_EDGECONV_NO_LDS
-  // LDS-resident gathers when a 16-channel slice of one cloud's P matrix fits (N <= 2048)
-  if (k == 20 && Co % 16 == 0 && (size_t)N * 16 * 4 + 64 * 32 * 4 <= 150 * 1024 && B <= SUG_STATS_BLOCKS / 4 &&
-      ((uintptr_t)idx % 16) == 0) {
+  // LDS-resident gathers when a 16-channel slice of one cloud's P matrix fits
+  if (fwd_lds_shape(B, N, k, Co) && ((uintptr_t)idx % 16) == 0) {
     const int nslice = Co / 16;
     int psplit = 512 / (B * nslice);
     psplit = psplit < 1 ? 1 : (psplit > 4 ? 4 : psplit);
@@ -1028,7 +1053,6 @@ static int edgeconv_fwd_partials(const float* pq, int64_t ldpq, const int32_t* i
     *nblk = B * psplit;
     return SUG_OK;
   }
-#endif
   const int lpp = lanes_per_point(Co);
   const int nch = sug_divup(Co >> 2, lpp);
   const int64_t BN = (int64_t)B * N;
@@ -1099,14 +1123,9 @@ int sug_edgeconv_fwd_bn_act_groups(const float* pq, int64_t ldpq, const int32_t*
   hipStream_t st = (hipStream_t)stream;
   const int Bg = B / groups;
   const int64_t rows = (int64_t)Bg * N;
-  const bool lds = k == 20 && Co % 16 == 0 && (size_t)N * 16 * 4 + 64 * 32 * 4 <= 150 * 1024 && B <= SUG_STATS_BLOCKS / 4 &&
-                   ((uintptr_t)idx % 16) == 0;
+  const bool lds = fwd_lds_shape(B, N, k, Co) && ((uintptr_t)idx % 16) == 0;
   const bool vec = (ldo % 4 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)coef % 16 == 0) && ((uintptr_t)z % 16 == 0);
-#ifdef SUG_EDGECONV_NO_LDS
-  const bool one = false;
-#else
   const bool one = lds && vec;
-#endif
   if (one) {
     // two launches: gather / reduce with per-(cloud, part) partial rows, then statistics fold + BatchNorm + activation
     // (edgeconv_fused.hip: every workgroup of the second launch folds its group's partial rows itself)
@@ -1348,10 +1367,9 @@ static int edgeconv_bwd_scatter_groups(const float* a, const uint8_t* arg, const
   const int64_t BN = (int64_t)Bg * N;                 // rows behind one set of BatchNorm statistics
   const float invM = (float)(1.0 / ((double)BN * k));
   hipStream_t st = (hipStream_t)stream;
-#ifndef SUG_EDGECONV_NO_LDS
-  // LDS-resident gathers when a 16-channel slice of one cloud's a, Q and arg fits (N <= 1024)
-  const size_t sh_lds = (size_t)N * 16 * 9 + 512 * sizeof(int) + (size_t)N * sizeof(uint16_t);
-  if (k == 20 && Co % 16 == 0 && N <= 65535 && sh_lds <= 158 * 1024 && !getenv("SUG_EDGECONV_BWD_LEGACY") &&
+  // LDS-resident gathers when a 16-channel slice of one cloud's a, Q and arg fits
+  const size_t sh_lds = bwd_lds_bytes(N);
+  if (bwd_lds_shape(N, k, Co) &&
       ((uintptr_t)a % 16) == 0 && ((uintptr_t)pq % 16) == 0 && ((uintptr_t)arg % 4) == 0 && ((uintptr_t)dpq % 16) == 0 &&
       ((uintptr_t)s1 % 16) == 0 && ((uintptr_t)coef % 16) == 0) {
     const int nslice = Co / 16;
@@ -1364,7 +1382,6 @@ static int edgeconv_bwd_scatter_groups(const float* a, const uint8_t* arg, const
     SUG_LAUNCH_CHECK("sug_edgeconv_bwd_scatter(lds)");
     return SUG_OK;
   }
-#endif
   // generic path: one launch per BatchNorm group
   const int lpp = lanes_per_point(Co);
   const int nch = sug_divup(Co >> 2, lpp);

@@ -1609,6 +1609,13 @@ def edgeconv_bn_act_max(pq, idx, gamma, beta, running_mean, running_var, trainin
                            None if out is None else [out], torch.is_grad_enabled())
 
 
+def edgeconv_path(backward, B, N, k, Co):
+    """True where the LDS-resident kernel takes the shape, False where the generic one does: the forward gather / reduce
+    of edgeconv_bn_act_max over B clouds (those of one group where the layer runs group by group), or with `backward` the
+    scatter of the backward of either EdgeConv layer.  The dispatch's own condition (sug_edgeconv_path), alignment aside."""
+    return bool(lib().sug_edgeconv_path(int(bool(backward)), B, N, k, Co))
+
+
 # The 1x1 convolution inside the gather kernel (edgeconv_fused.hip): default; SUG_EDGECONV_FUSED=0 selects the
 # library GEMM + edgeconv_bn_act_max path (A/B measurements).
 EDGECONV_FUSED = _os.environ.get('SUG_EDGECONV_FUSED', '1') == '1'

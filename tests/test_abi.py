@@ -20,6 +20,7 @@ EXPECTED = {
     'sug_linear_dw_workspace': (ctypes.c_int64, 'lii'),                           # int64_t return
     'sug_adam_chunk': (ctypes.c_int, ''),                                         # int f(void)
     'sug_bn_replay_multi': (ctypes.c_int, 'i' 'ppp' 'p' 'pp' 'p'),                 # const void* const*, void* const*
+    'sug_edgeconv_path': (ctypes.c_int, 'iiiii'),                                 # a query: ints only, no stream
 }
 
 
@@ -28,7 +29,7 @@ def test_library_built_and_exports_header_symbols():
     assert os.path.exists(_lib.LIB_PATH), 'build with make -C sug_amd/csrc'
     L = ctypes.CDLL(_lib.LIB_PATH)
     names = sorted(_lib.DECLARATIONS)
-    assert len(names) >= 142
+    assert len(names) >= 177
     for n in names:
         assert hasattr(L, n), 'missing export %s' % n
 
