@@ -7,6 +7,7 @@
 //                 w_t = (1/max(d_t,1e-10)) / sum   (upsample_inter, model/point_utils.py:156-162)
 // All tensors are tiny (B*64 nodes, B*N points x 64 channels): latency-bound, one launch each.
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -592,9 +593,6 @@ extern "C" int sug_interp3_cat_bwd(const float* g, int64_t ldg, int C1, const fl
   SUG_LAUNCH_CHECK("sug_interp3_cat_bwd");
   return SUG_OK;
 }
-
-// knn.hip: LDS bytes of sug_reverse_lists for this shape (declared here as in group.hip, not in common.h)
-size_t sug_reverse_lists_lds_bytes(int B, int E, int N, int* ranges);
 
 // Do the reverse lists of idx3 (3N entries per cloud into S nodes) fit the LDS-resident build that
 // sug_interp3_cat_bwd_lists needs?  0: the caller zero-fills dnode / dnloc and takes sug_interp3_cat_bwd.

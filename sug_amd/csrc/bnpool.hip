@@ -1,96 +1,14 @@
-// Train-mode BatchNorm (+LeakyReLU/ReLU) on point-major rows, its exact backward, and the fused
-// DGCNN tail  BatchNorm1d -> LeakyReLU(0.2) -> [max over points | mean over points]
-// (model/Model.py:112-116).  Statistics come from col_reduce_kernel (edgeconv.hip) through
-// sug_col_stats; this file adds the elementwise / pooling halves.  All HBM-bound:
-//   bn_bwd_apply      reads a, y (8 B/elem) writes dy (4 B/elem)
+// The fused DGCNN tail  BatchNorm1d -> LeakyReLU(0.2) -> [max over points | mean over points]
+// (model/Model.py:112-116) and its backward, LayerNorm + activation of the FC heads, the gate layers and column sums.
+// The tail's statistics come from bn_rows.hip (sug_col_stats_bn and its grouped forms), which also holds the
+// BatchNorm layer without pooling; this file adds the pooling halves.  All HBM-bound:
 //   bn_act_pool_fwd   reads y once (4 B/elem), writes 3 x [B,C]
 //   pool_bwd_reduce   reads y once; pool_bwd_apply reads y once, writes dy once.
 #include "common.h"
+#include "internal.h"
 #include <hip/hip_fp16.h>
 
 namespace {
-
-// float4 variant of bn_bwd_apply_kernel (C % 4 == 0, aligned rows)
-__global__ __launch_bounds__(256) void bn_bwd_apply_vec4_kernel(const float* __restrict__ a,
-                                                                const float* __restrict__ y, int64_t ldy,
-                                                                const float* __restrict__ coef,
-                                                                const double* __restrict__ red,
-                                                                int64_t rows, int C, float invM,
-                                                                float* __restrict__ dy, int64_t lddy) {
-  const int C4 = C >> 2;
-  const int64_t total = rows * C4;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C4) * 4;
-    const int64_t r = e / C4;
-    const float4 av = *reinterpret_cast<const float4*>(a + r * C + c);
-    const float4 yv = *reinterpret_cast<const float4*>(y + r * ldy + c);
-    const float4 sc = *reinterpret_cast<const float4*>(coef + c);
-    const float4 mean = *reinterpret_cast<const float4*>(coef + 2 * C + c);
-    const float4 rstd = *reinterpret_cast<const float4*>(coef + 3 * C + c);
-    float4 o;
-    o.x = av.x - sc.x * invM * ((float)red[c + 0] + (yv.x - mean.x) * rstd.x * (float)red[C + c + 0]);
-    o.y = av.y - sc.y * invM * ((float)red[c + 1] + (yv.y - mean.y) * rstd.y * (float)red[C + c + 1]);
-    o.z = av.z - sc.z * invM * ((float)red[c + 2] + (yv.z - mean.z) * rstd.z * (float)red[C + c + 2]);
-    o.w = av.w - sc.w * invM * ((float)red[c + 3] + (yv.w - mean.w) * rstd.w * (float)red[C + c + 3]);
-    *reinterpret_cast<float4*>(dy + r * lddy + c) = o;
-  }
-}
-
-// bn_bwd_apply_vec4_kernel over `rows` rows in domain groups of rows_g: coefficient set and sums of each row's group.
-// FROM_G: `a` is the upstream gradient (row stride lda) and a = scale * g * act'(scale*y + shift) is formed here
-// (the reduce kernel then writes no [rows, C] tensor: 5 passes over the layer instead of 6).
-template <bool FROM_G>
-__global__ __launch_bounds__(256) void bn_bwd_apply_vec4_groups_kernel(const float* __restrict__ a, int64_t lda,
-                                                                       const float* __restrict__ y, int64_t ldy,
-                                                                       const float* __restrict__ coef,
-                                                                       const double* __restrict__ red, int64_t rows,
-                                                                       int64_t rows_g, int C, float invM, float slope,
-                                                                       float* __restrict__ dy, int64_t lddy) {
-  const int C4 = C >> 2;
-  const int64_t total = rows * C4;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C4) * 4;
-    const int64_t r = e / C4;
-    const int64_t g = r / rows_g;
-    const float* cg = coef + g * 5 * C;
-    const double* rg = red + g * 2 * C;
-    float4 av = *reinterpret_cast<const float4*>(a + r * lda + c);
-    const float4 yv = *reinterpret_cast<const float4*>(y + r * ldy + c);
-    const float4 sc = *reinterpret_cast<const float4*>(cg + c);
-    const float4 mean = *reinterpret_cast<const float4*>(cg + 2 * C + c);
-    const float4 rstd = *reinterpret_cast<const float4*>(cg + 3 * C + c);
-    if (FROM_G) {
-      const float4 sh = *reinterpret_cast<const float4*>(cg + C + c);
-      av.x = sc.x * (av.x * (fmaf(sc.x, yv.x, sh.x) > 0.f ? 1.f : slope));
-      av.y = sc.y * (av.y * (fmaf(sc.y, yv.y, sh.y) > 0.f ? 1.f : slope));
-      av.z = sc.z * (av.z * (fmaf(sc.z, yv.z, sh.z) > 0.f ? 1.f : slope));
-      av.w = sc.w * (av.w * (fmaf(sc.w, yv.w, sh.w) > 0.f ? 1.f : slope));
-    }
-    float4 o;
-    o.x = av.x - sc.x * invM * ((float)rg[c + 0] + (yv.x - mean.x) * rstd.x * (float)rg[C + c + 0]);
-    o.y = av.y - sc.y * invM * ((float)rg[c + 1] + (yv.y - mean.y) * rstd.y * (float)rg[C + c + 1]);
-    o.z = av.z - sc.z * invM * ((float)rg[c + 2] + (yv.z - mean.z) * rstd.z * (float)rg[C + c + 2]);
-    o.w = av.w - sc.w * invM * ((float)rg[c + 3] + (yv.w - mean.w) * rstd.w * (float)rg[C + c + 3]);
-    *reinterpret_cast<float4*>(dy + r * lddy + c) = o;
-  }
-}
-
-// dy = a - (scale/M) * (dbeta + xhat * dgamma),  a = scale * G  (exact BN gradient)
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ a,
-                                                           const float* __restrict__ y, int64_t ldy,
-                                                           const float* __restrict__ coef,
-                                                           const double* __restrict__ red, int64_t rows,
-                                                           int C, float invM, float* __restrict__ dy,
-                                                           int64_t lddy) {
-  const int64_t total = rows * C;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    const int64_t r = e / C;
-    const float f = coef[c] * invM;
-    const float xhat = (y[r * ldy + c] - coef[2 * C + c]) * coef[3 * C + c];
-    dy[r * lddy + c] = a[r * C + c] - f * ((float)red[c] + xhat * (float)red[C + c]);
-  }
-}
 
 constexpr int NS = 4;      // row chunks per cloud (more workgroups -> more loads in flight)
 
@@ -343,7 +261,7 @@ __global__ __launch_bounds__(256) void pool_bwd_apply_rows_kernel(const float* _
 }
 
 // out[i] = sum over rows (ascending, 16 strided partials) of ws[row][i] in fp64 (same scheme as
-// edgeconv.hip's reduce_partials_kernel).
+// bn_rows.hip's reduce_partials_kernel).
 __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restrict__ ws, int nrow, int W,
                                                           double* __restrict__ out) {
   __shared__ double s_p[16][17];
@@ -362,49 +280,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
   }
 }
 
-inline int ew_grid(int64_t total) {
-  int64_t g = (total + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
-
-extern "C" int sug_bn_bwd_apply(const float* a, const float* y, int64_t ldy, const float* coef,
-                                const double* red, int64_t rows, int C, float* dy, int64_t lddy,
-                                void* stream) {
-  SUG_REQUIRE(a && y && coef && red && dy, "sug_bn_bwd_apply: null pointer");
-  SUG_REQUIRE(rows > 0 && C > 0 && ldy >= C && lddy >= C, "sug_bn_bwd_apply: bad shape");
-  const bool vec = (C % 4 == 0) && (ldy % 4 == 0) && (lddy % 4 == 0) && ((uintptr_t)a % 16 == 0) &&
-                   ((uintptr_t)y % 16 == 0) && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)coef % 16 == 0);
-  if (vec)
-    hipLaunchKernelGGL(bn_bwd_apply_vec4_kernel, dim3(ew_grid(rows * C / 4)), dim3(256), 0, (hipStream_t)stream, a,
-                       y, ldy, coef, red, rows, C, (float)(1.0 / (double)rows), dy, lddy);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(rows * C)), dim3(256), 0, (hipStream_t)stream, a, y,
-                       ldy, coef, red, rows, C, (float)(1.0 / (double)rows), dy, lddy);
-  SUG_LAUNCH_CHECK("sug_bn_bwd_apply");
-  return SUG_OK;
-}
-
-// all domain groups (rows_g rows each) in one launch; 1 = layout does not allow it.  from_g: `a` is the upstream
-// gradient gout (row stride lda) instead of the precomputed a = scale*G
-int sug_bn_bwd_apply_groups(const float* a, int64_t lda, int from_g, float slope, const float* y, int64_t ldy,
-                            const float* coef, const double* red, int64_t rows_g, int groups, int C, float* dy,
-                            int64_t lddy, hipStream_t st) {
-  const bool vec = (C % 4 == 0) && (ldy % 4 == 0) && (lddy % 4 == 0) && (lda % 4 == 0) && ((uintptr_t)a % 16 == 0) &&
-                   ((uintptr_t)y % 16 == 0) && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)coef % 16 == 0);
-  if (!vec) return 1;
-  const int64_t rows = rows_g * groups;
-  const float invM = (float)(1.0 / (double)rows_g);
-  if (from_g)
-    hipLaunchKernelGGL((bn_bwd_apply_vec4_groups_kernel<true>), dim3(ew_grid(rows * C / 4)), dim3(256), 0, st, a, lda, y, ldy,
-                       coef, red, rows, rows_g, C, invM, slope, dy, lddy);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_vec4_groups_kernel<false>), dim3(ew_grid(rows * C / 4)), dim3(256), 0, st, a, lda, y, ldy,
-                       coef, red, rows, rows_g, C, invM, slope, dy, lddy);
-  SUG_LAUNCH_CHECK("sug_bn_bwd_apply");
-  return SUG_OK;
-}
 
 // ---- LayerNorm + (Leaky)ReLU of the FC heads (fc_layer, model/model_utils.py:35-57): rows <= a few hundred,
 // C <= 1024.  Forward: one wave per row (mean, biased variance like nn.LayerNorm, two-pass over registers).
@@ -558,10 +434,10 @@ extern "C" int sug_bn_act_pool_bwd(const float* y, int64_t ldy, const float* coe
     hipLaunchKernelGGL(pool_bwd_apply_rows_kernel, dim3(sug_divup(N, rpb), B), dim3(256), 0, st, y, ldy, coef, red, gmax,
                        gmean, ld_pool, arg, B, N, C, rpb, slope, invM, dy, lddy, 0);
   } else if (vec)
-    hipLaunchKernelGGL((pool_bwd_apply_kernel<4>), dim3(ew_grid((int64_t)B * N * C / 4)), dim3(256), 0, st, y, ldy,
+    hipLaunchKernelGGL((pool_bwd_apply_kernel<4>), dim3(sug_ew_grid((int64_t)B * N * C / 4)), dim3(256), 0, st, y, ldy,
                        coef, red, gmax, gmean, ld_pool, arg, B, N, C, slope, invM, dy, lddy);
   else
-    hipLaunchKernelGGL((pool_bwd_apply_kernel<1>), dim3(ew_grid((int64_t)B * N * C)), dim3(256), 0, st, y, ldy, coef,
+    hipLaunchKernelGGL((pool_bwd_apply_kernel<1>), dim3(sug_ew_grid((int64_t)B * N * C)), dim3(256), 0, st, y, ldy, coef,
                        red, gmax, gmean, ld_pool, arg, B, N, C, slope, invM, dy, lddy);
   SUG_LAUNCH_CHECK("sug_bn_act_pool_bwd(apply)");
   return SUG_OK;

@@ -18,6 +18,7 @@
 // fp32 on the matrix pipe (v_mfma_f32_32x32x2_f32: lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31];
 // register r of the result holds D[8 (r >> 2) + (r & 3) + 4 (l >> 5)][l & 31]); every sum has a fixed order, no atomics.
 #include "common.h"
+#include "device_helpers.h"
 
 namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -27,8 +28,6 @@ constexpr int NW = NT / 64;
 constexpr int TS = 36;           // floats per staging-tile row (32 + pad)
 constexpr int HD = 512;          // hidden width of the attention MLP (channel / reduction = 4096 / 8)
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // ---------------------------------------------------------------------------------------------------- forward GEMMs
 struct GemmArgs {

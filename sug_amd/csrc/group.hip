@@ -2,6 +2,7 @@
 // Reference: model/point_utils.py:60-83, model/pointnet2_utils.py:41-57,
 // model/model_utils.py:122-123.  All HBM-bound: one read + one write per element.
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -208,10 +209,6 @@ extern "C" int sug_scatter_add_rows(const float* g, int64_t ldg, const int32_t* 
 }
 
 extern "C" int64_t sug_scatter_rows_workspace(int B, int N, int S) { return (int64_t)B * (N + 1) + (int64_t)B * S; }
-
-// knn.hip: LDS bytes of sug_reverse_lists for this shape (declared here, not in common.h: the kNN / fused-EdgeConv PMC traffic
-// files under profiles/ are keyed by a hash of the sources that include common.h)
-size_t sug_reverse_lists_lds_bytes(int B, int E, int N, int* ranges);
 
 extern "C" int sug_scatter_rows_ordered_supported(int B, int N, int S) {
   return (B > 0 && N > 0 && S > 0 && sug_reverse_lists_lds_bytes(B, S, N, nullptr) <= 160 * 1024) ? 1 : 0;

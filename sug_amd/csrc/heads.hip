@@ -15,6 +15,7 @@
 // register r of the result holds D[i = 8 (r >> 2) + (r & 3) + 4 (l >> 5)][j = l & 31].  Which two k's a step multiplies
 // is free as long as A and B agree.
 #include "common.h"
+#include "device_helpers.h"
 
 namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -22,8 +23,6 @@ constexpr int HMAX = 2;          // heads per launch
 constexpr int NT = 512;          // threads per workgroup (8 waves)
 constexpr int NW = NT / 64;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // ---------------------------------------------------------------------------------------------------- forward
 struct FwdHead {

@@ -9,6 +9,8 @@
 // Roofline: algorithmic bytes 4*C*N + 4*N*k per cloud, FLOPs N^2*(2C+3): compute
 // bound for every C; the [B,N,N] matrix of the reference never exists.
 #include "common.h"
+#include "internal.h"
+#include "device_helpers.h"
 
 namespace {
 
@@ -224,25 +226,6 @@ int dispatch_knn_c(const float* x, int64_t ldx, int B, int N, int C, int k, int3
 constexpr int REV_BLOCK = 1024;
 constexpr int REV_NW = REV_BLOCK / 64;
 static_assert(REV_NW == 16, "4 bins x 16 waves: the 64 totals a wave scans, 8 bytes a wave in the 32 scratch ints");
-
-// inclusive prefix sums over the lanes through the DPP paths (no LDS-crossbar shuffles): lanes without a source add 0
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned rev_dpp0(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ unsigned rev_row_scan(unsigned x) {          // over each row of 16 lanes
-  x += rev_dpp0<0x111, 0xf>(x);                                         // row_shr:1
-  x += rev_dpp0<0x112, 0xf>(x);                                         // row_shr:2
-  x += rev_dpp0<0x114, 0xf>(x);                                         // row_shr:4
-  x += rev_dpp0<0x118, 0xf>(x);                                         // row_shr:8
-  return x;
-}
-__device__ __forceinline__ unsigned rev_wave_scan(unsigned x) {         // over the 64 lanes
-  x = rev_row_scan(x);
-  x += rev_dpp0<0x142, 0xa>(x);                                         // row_bcast:15 into rows 1, 3
-  x += rev_dpp0<0x143, 0xc>(x);                                         // row_bcast:31 into rows 2, 3
-  return x;
-}
 
 template <int UMAX>
 __global__ __launch_bounds__(REV_BLOCK) void reverse_lists_kernel(const int32_t* __restrict__ idx, int N, int E, int RS,

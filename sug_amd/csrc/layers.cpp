@@ -3,42 +3,8 @@
 // separate forward calls) and chaining the kernels of the finer-grained entry points.  Nothing
 // new is computed here; the point is one host call (and no tensor slicing in the binding) per
 // layer instead of 4-8.  Host-only translation unit.
-#include <stdint.h>
-#include "../../include/sug_amd.h"
+#include "internal.h"
 
-void sug_set_error(const char* fmt, ...);
-// edgeconv.hip: sug_edgeconv_bwd_scatter over `groups` BatchNorm groups in one launch (group g reads
-// coef + g*coef_stride, red + g*red_stride)
-// grouped forms of the rows-layer kernels (edgeconv.hip, bnpool.hip): 0 = done, 1 = layout not vectorisable (go group
-// by group), < 0 = error
-struct ihipStream_t;
-int sug_col_stats_bn_groups(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
-                            const float* beta, float eps, float momentum, float* running_mean, float* running_var,
-                            float* coef, float* ws, ihipStream_t* st);
-int sug_affine_act_groups(const float* z, int64_t ldz, const float* coef, int64_t rows, int groups, int C, float slope,
-                          float* out, int64_t ldo, ihipStream_t* st);
-int sug_bwd_reduce_groups(const float* gout, int64_t ldg, const float* z, const float* coef, int64_t rows, int Co,
-                          int groups, float slope, float* a, double* red, float* ws, ihipStream_t* st, float* dgb);
-int sug_bn_bwd_apply_groups(const float* a, int64_t lda, int from_g, float slope, const float* y, int64_t ldy,
-                            const float* coef, const double* red, int64_t rows_g, int groups, int C, float* dy,
-                            int64_t lddy, ihipStream_t* st);
-int sug_col_stats_bn_own_ws(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
-                            const float* beta, float eps, float momentum, float* running_mean, float* running_var,
-                            float* coef, float* ws, ihipStream_t* st);
-int sug_bn_act_pool_fwd_groups(const float* y, int64_t ldy, const float* coef, int B, int groups, int N, int C, float slope,
-                               float* out_max, float* out_mean, int64_t ld_pool, int32_t* arg, float* ws, ihipStream_t* st);
-int sug_bn_act_pool_bwd_groups(const float* y, int64_t ldy, const float* coef, const float* gmax, const float* gmean,
-                               int64_t ld_pool, const int32_t* arg, int B, int groups, int N, int C, float slope, double* red,
-                               float* ws, float* dy, int64_t lddy, float* dgb, ihipStream_t* st);
-int sug_edgeconv_fwd_bn_act_groups(const float* pq, int64_t ldpq, const int32_t* idx, const float* gamma,
-                                   const float* beta, int B, int N, int k, int Co, int groups, float eps, float momentum,
-                                   float slope, float* running_mean, float* running_var, float* z, uint8_t* arg,
-                                   float* s1, float* coef, float* out, int64_t ldo, float* ws, void* stream);
-int sug_edgeconv_bwd_scatter_groups(const float* a, const uint8_t* arg, const float* s1, const float* pq, int64_t ldpq,
-                                    const int32_t* rev_off, const int32_t* rev_ent, const float* coef, const double* red,
-                                    int B, int N, int k, int Co, int groups, int64_t coef_stride, int64_t red_stride,
-                                    float* dpq, int64_t lddpq, void* stream);
-#define LAYER_REQUIRE(cond, ...) do { if (!(cond)) { sug_set_error(__VA_ARGS__); return SUG_ERR_ARG; } } while (0)
 #define LAYER_TRY(call) do { const int rc_ = (call); if (rc_ != SUG_OK) return rc_; } while (0)
 
 extern "C" int sug_edgeconv_layer_fwd(const float* pq, int64_t ldpq, const int32_t* idx, const float* gamma,
@@ -46,8 +12,8 @@ extern "C" int sug_edgeconv_layer_fwd(const float* pq, int64_t ldpq, const int32
                                       float eps, float momentum, float slope, float* running_mean,
                                       float* running_var, float* z, uint8_t* arg, float* s1, float* coef,
                                       float* out, int64_t ldo, double* stats, float* ws, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_edgeconv_layer_fwd: B=%d does not split into %d groups", B, groups);
-  LAYER_REQUIRE(coef && out && z && arg && stats, "sug_edgeconv_layer_fwd: null pointer");
+  SUG_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_edgeconv_layer_fwd: B=%d does not split into %d groups", B, groups);
+  SUG_REQUIRE(coef && out && z && arg && stats, "sug_edgeconv_layer_fwd: null pointer");
   const int Bg = B / groups;
   const int64_t rows = (int64_t)Bg * N;
   if (training)      // all groups in three launches when the LDS-resident kernel applies (edgeconv.hip)
@@ -68,14 +34,14 @@ extern "C" int sug_edgeconv_layer_bwd(const float* gout, int64_t ldg, const floa
                                       const float* coef, int B, int N, int k, int Co, int groups, int training,
                                       float slope, float* a, double* red, int32_t* rev_off, int32_t* rev_ent,
                                       float* dpq, int64_t lddpq, float* ws, float* dgb, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_edgeconv_layer_bwd: B=%d does not split into %d groups", B, groups);
-  LAYER_REQUIRE(red && a && rev_off && rev_ent, "sug_edgeconv_layer_bwd: null pointer");
+  SUG_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_edgeconv_layer_bwd: B=%d does not split into %d groups", B, groups);
+  SUG_REQUIRE(red && a && rev_off && rev_ent, "sug_edgeconv_layer_bwd: null pointer");
   const int Bg = B / groups;
   const int64_t rows = (int64_t)Bg * N;
   LAYER_TRY(sug_knn_reverse(idx, B, N, k, rev_off, rev_ent, stream));
   int grouped = 1;
   if (groups > 1) {      // (the grouped reduce also writes dgb: no fold launch afterwards)
-    grouped = sug_bwd_reduce_groups(gout, ldg, z, coef, rows, Co, groups, slope, a, red, ws, (ihipStream_t*)stream, dgb);
+    grouped = sug_bwd_reduce_groups(gout, ldg, z, coef, rows, Co, groups, slope, a, red, ws, (hipStream_t)stream, dgb);
     if (grouped < 0) return grouped;
   }
   for (int g = 0; grouped != 0 && g < groups; ++g) {
@@ -97,11 +63,11 @@ extern "C" int sug_bn_act_rows_fwd(const float* y, int64_t ldy, int64_t rows, in
                                    const float* gamma, const float* beta, int training, float eps, float momentum,
                                    float slope, float* running_mean, float* running_var, float* coef, float* out,
                                    int64_t ldo, double* stats, float* ws, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_bn_act_rows_fwd: %lld rows do not split into %d groups",
-                (long long)rows, groups);
-  LAYER_REQUIRE(coef && out, "sug_bn_act_rows_fwd: null pointer");
+  SUG_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_bn_act_rows_fwd: %lld rows do not split into %d groups",
+              (long long)rows, groups);
+  SUG_REQUIRE(coef && out, "sug_bn_act_rows_fwd: null pointer");
   const int64_t rg = rows / groups;
-  ihipStream_t* st = (ihipStream_t*)stream;
+  hipStream_t st = (hipStream_t)stream;
   if (groups > 1 && ldy == C) {                  // all groups per launch (3 launches instead of 3 per group)
     int rc = training ? sug_col_stats_bn_groups(y, ldy, rg, C, groups, gamma, beta, eps, momentum, running_mean, running_var,
                                                 coef, ws, st)
@@ -129,13 +95,13 @@ extern "C" int sug_bn_act_rows_fwd(const float* y, int64_t ldy, int64_t rows, in
 extern "C" int sug_col_stats_bn_grouped(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
                                         const float* beta, float eps, float momentum, float* running_mean,
                                         float* running_var, float* coef, float* ws, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_col_stats_bn_grouped: %lld rows do not split into %d groups",
-                (long long)rows, groups);
-  LAYER_REQUIRE(y && gamma && beta && coef && ws, "sug_col_stats_bn_grouped: null pointer");
+  SUG_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_col_stats_bn_grouped: %lld rows do not split into %d groups",
+              (long long)rows, groups);
+  SUG_REQUIRE(y && gamma && beta && coef && ws, "sug_col_stats_bn_grouped: null pointer");
   const int64_t rg = rows / groups;
   if (groups > 1 && ldy == C) {                  // every group's statistics in one launch pair
     const int rc = sug_col_stats_bn_groups(y, ldy, rg, C, groups, gamma, beta, eps, momentum, running_mean, running_var, coef, ws,
-                                           (ihipStream_t*)stream);
+                                           (hipStream_t)stream);
     if (rc <= 0) return rc;
   }
   for (int g = 0; g < groups; ++g)
@@ -147,11 +113,11 @@ extern "C" int sug_col_stats_bn_grouped(const float* y, int64_t ldy, int64_t row
 extern "C" int sug_bn_act_rows_bwd(const float* gout, int64_t ldg, const float* y, int64_t ldy, const float* coef,
                                    int64_t rows, int C, int groups, int training, float slope, float* a,
                                    double* red, float* dy, float* ws, float* dgb, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_bn_act_rows_bwd: %lld rows do not split into %d groups",
-                (long long)rows, groups);
-  LAYER_REQUIRE(ldy == C, "sug_bn_act_rows_bwd: y must be dense");
+  SUG_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_bn_act_rows_bwd: %lld rows do not split into %d groups",
+              (long long)rows, groups);
+  SUG_REQUIRE(ldy == C, "sug_bn_act_rows_bwd: y must be dense");
   const int64_t rg = rows / groups;
-  ihipStream_t* st = (ihipStream_t*)stream;
+  hipStream_t st = (hipStream_t)stream;
   // train mode, vectorisable layout: sums without the [rows, C] intermediate a = scale*G, the apply kernel forms it
   // from gout and y (5 passes over the layer instead of 6), all groups per launch
   if (training && ldg % 4 == 0 && C % 4 == 0 && ((uintptr_t)gout % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
@@ -194,7 +160,7 @@ extern "C" int sug_bn_act_pool_layer_fwd(const float* y, int64_t ldy, int B, int
                                          float momentum, float slope, float* running_mean, float* running_var,
                                          float* coef, float* out_max, float* out_mean, int64_t ld_pool, int32_t* arg, double* stats,
                                          float* ws_stats, float* ws_pool, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_layer_fwd: B=%d does not split into %d groups", B, groups);
+  SUG_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_layer_fwd: B=%d does not split into %d groups", B, groups);
   const int Bg = B / groups;
   const int64_t rg = (int64_t)Bg * N;
   for (int g = 0; g < groups; ++g) {
@@ -213,7 +179,7 @@ extern "C" int sug_bn_act_pool_layer_bwd(const float* y, int64_t ldy, const floa
                                          const float* gmean, int64_t ld_pool, const int32_t* arg, int B, int N, int C, int groups,
                                          float slope, int training, double* red, float* ws, float* dy, int64_t lddy,
                                          float* dgb, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_layer_bwd: B=%d does not split into %d groups", B, groups);
+  SUG_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_layer_bwd: B=%d does not split into %d groups", B, groups);
   const int Bg = B / groups;
   const int64_t rg = (int64_t)Bg * N;
   for (int g = 0; g < groups; ++g)
@@ -231,14 +197,14 @@ extern "C" int sug_bn_act_pool_layer_bwd(const float* y, int64_t ldy, const floa
 extern "C" int sug_col_stats_bn_groups_exact(const float* y, int64_t ldy, int64_t rows, int C, int groups, const float* gamma,
                                              const float* beta, float eps, float momentum, float* running_mean,
                                              float* running_var, float* coef, float* ws, void* stream) {
-  LAYER_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_col_stats_bn_groups_exact: %lld rows do not split into %d groups",
-                (long long)rows, groups);
-  LAYER_REQUIRE(y && gamma && beta && coef && ws, "sug_col_stats_bn_groups_exact: null pointer");
-  LAYER_REQUIRE(C > 0 && C <= 4096 && ldy >= C, "sug_col_stats_bn_groups_exact: bad shape");
+  SUG_REQUIRE(groups >= 1 && rows > 0 && rows % groups == 0, "sug_col_stats_bn_groups_exact: %lld rows do not split into %d groups",
+              (long long)rows, groups);
+  SUG_REQUIRE(y && gamma && beta && coef && ws, "sug_col_stats_bn_groups_exact: null pointer");
+  SUG_REQUIRE(C > 0 && C <= 4096 && ldy >= C, "sug_col_stats_bn_groups_exact: bad shape");
   const int64_t rg = rows / groups;
   if (groups > 1 && groups <= 16) {
     const int rc = sug_col_stats_bn_own_ws(y, ldy, rg, C, groups, gamma, beta, eps, momentum, running_mean, running_var, coef, ws,
-                                           (ihipStream_t*)stream);
+                                           (hipStream_t)stream);
     if (rc <= 0) return rc;
   }
   for (int g = 0; g < groups; ++g)
@@ -252,12 +218,12 @@ extern "C" int sug_bn_act_pool_groups_fwd(const float* y, int64_t ldy, int B, in
                                           float* running_mean, float* running_var, float* coef, float* out_max, float* out_mean,
                                           int64_t ld_pool, int32_t* arg, double* stats, float* ws_stats, float* ws_pool,
                                           void* stream) {
-  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_groups_fwd: B=%d does not split into %d groups", B, groups);
+  SUG_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_groups_fwd: B=%d does not split into %d groups", B, groups);
   if (training && groups > 1 && groups <= 16) {
-    LAYER_REQUIRE(y && gamma && beta && coef && out_max && out_mean && arg && ws_stats && ws_pool,
-                  "sug_bn_act_pool_groups_fwd: null pointer");
-    LAYER_REQUIRE(N > 0 && C > 0 && C <= 4096 && ldy >= C && ld_pool >= C, "sug_bn_act_pool_groups_fwd: bad shape");
-    ihipStream_t* st = (ihipStream_t*)stream;
+    SUG_REQUIRE(y && gamma && beta && coef && out_max && out_mean && arg && ws_stats && ws_pool,
+                "sug_bn_act_pool_groups_fwd: null pointer");
+    SUG_REQUIRE(N > 0 && C > 0 && C <= 4096 && ldy >= C && ld_pool >= C, "sug_bn_act_pool_groups_fwd: bad shape");
+    hipStream_t st = (hipStream_t)stream;
     const int Bg = B / groups;
     const int64_t rg = (int64_t)Bg * N;
     int rc = sug_col_stats_bn_own_ws(y, ldy, rg, C, groups, gamma, beta, eps, momentum, running_mean, running_var, coef, ws_stats, st);
@@ -280,12 +246,12 @@ extern "C" int sug_bn_act_pool_groups_bwd(const float* y, int64_t ldy, const flo
                                           int64_t ld_pool, const int32_t* arg, int B, int N, int C, int groups, float slope,
                                           int training, double* red, float* ws, float* dy, int64_t lddy, float* dgb,
                                           void* stream) {
-  LAYER_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_groups_bwd: B=%d does not split into %d groups", B, groups);
+  SUG_REQUIRE(groups >= 1 && B > 0 && B % groups == 0, "sug_bn_act_pool_groups_bwd: B=%d does not split into %d groups", B, groups);
   if (training && groups > 1 && groups <= 16) {
-    LAYER_REQUIRE(y && coef && gmax && gmean && arg && red && ws && dy, "sug_bn_act_pool_groups_bwd: null pointer");
-    LAYER_REQUIRE(N > 0 && C > 0 && ldy >= C && lddy >= C && ld_pool >= C, "sug_bn_act_pool_groups_bwd: bad shape");
+    SUG_REQUIRE(y && coef && gmax && gmean && arg && red && ws && dy, "sug_bn_act_pool_groups_bwd: null pointer");
+    SUG_REQUIRE(N > 0 && C > 0 && ldy >= C && lddy >= C && ld_pool >= C, "sug_bn_act_pool_groups_bwd: bad shape");
     const int rc = sug_bn_act_pool_bwd_groups(y, ldy, coef, gmax, gmean, ld_pool, arg, B, groups, N, C, slope, red, ws, dy, lddy,
-                                              dgb, (ihipStream_t*)stream);
+                                              dgb, (hipStream_t)stream);
     if (rc <= 0) return rc;
   }
   return sug_bn_act_pool_layer_bwd(y, ldy, coef, gmax, gmean, ld_pool, arg, B, N, C, groups, slope, training, red, ws, dy, lddy,

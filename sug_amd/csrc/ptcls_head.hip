@@ -15,6 +15,7 @@
 // register r of the result holds D[4 (l >> 4) + r][l & 15].  Which four k's a step multiplies is free as long as A and B
 // agree: the row-major operands are read as float4 at k = 16 u + 4 q (q = l >> 4), element e of the float4 feeding step e.
 #include "common.h"
+#include "device_helpers.h"
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -23,7 +24,6 @@ constexpr int RB = 16;           // rows per workgroup / tile
 constexpr int N2F = 64;          // width of the second hidden layer (4 waves x 16 columns in ptcls_fwd2 / ptcls_bwd1)
 constexpr int SP = N2F + 4;      // LDS row stride of an [RB][N2F] tile
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ f32x4 zero4() { f32x4 z; z[0] = z[1] = z[2] = z[3] = 0.f; return z; }
 __device__ __forceinline__ f32x4 mma4(float4 a, float4 b, f32x4 acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);

@@ -2,31 +2,13 @@
 // counting placement with the cloud streamed through LDS in tiles.  sug_knn_reverse (knn.hip) hands over the shapes its
 // own build refuses; sug_reverse_lists_tiled takes any shape within SUG_REV_TILED_MAX_DEST / _MAX_ENTRIES.
 #include "common.h"
+#include "device_helpers.h"
 
 namespace {
 
 constexpr int REV_BLOCK = 1024;
 constexpr int REV_NW = REV_BLOCK / 64;
 static_assert(REV_NW == 16, "4 bins x 16 waves: the 64 totals a wave scans, 8 bytes a wave in the 32 scratch ints");
-
-// inclusive prefix sums over the lanes through the DPP paths, as in knn.hip: lanes without a source add 0
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned rev_dpp0(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ unsigned rev_row_scan(unsigned x) {          // over each row of 16 lanes
-  x += rev_dpp0<0x111, 0xf>(x);                                         // row_shr:1
-  x += rev_dpp0<0x112, 0xf>(x);                                         // row_shr:2
-  x += rev_dpp0<0x114, 0xf>(x);                                         // row_shr:4
-  x += rev_dpp0<0x118, 0xf>(x);                                         // row_shr:8
-  return x;
-}
-__device__ __forceinline__ unsigned rev_wave_scan(unsigned x) {         // over the 64 lanes
-  x = rev_row_scan(x);
-  x += rev_dpp0<0x142, 0xa>(x);                                         // row_bcast:15 into rows 1, 3
-  x += rev_dpp0<0x143, 0xc>(x);                                         // row_bcast:31 into rows 2, 3
-  return x;
-}
 
 // ---- tiled reverse lists ---------------------------------------------------
 // The same placement for clouds of any size: reverse_lists_kernel is its one-tile case.  A workgroup owns the destinations

@@ -20,7 +20,7 @@ def compile_variant(tag, defs):
     initialises the GPU in every child, and hipcc execs clang / lld: the forbidden exec from a GPU-initialised process).
     The --pmc flow is two commands: `--build-only "<defs>"` un-profiled, then EF_ONLY under the profiler (load only)."""
     out = lib_path(tag)
-    files = [os.path.join(SRC, f) for f in ('edgeconv_fused.hip', 'edgeconv.hip', 'capi.cpp')]
+    files = [os.path.join(SRC, f) for f in ('edgeconv_fused.hip', 'edgeconv.hip', 'bn_rows.hip', 'capi.cpp')]
     subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + defs + files + ['-o', out], check=True)
     return out
 
