@@ -44,7 +44,7 @@ extern "C" {
 
 const char* sug_last_error(void);
 /* ABI version of the loaded library (bumped when a signature changes; 3: sug_adam_step_capturable gained lr_dev,
- * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added; 8: the KPConv entry points keep one row layout -- the eight sug_*_cap twins are gone, sug_grid_subsample takes C, level and the nullable record, sug_kpconv_fwd takes nq_valid, sug_seg_instnorm_fwd / _bwd take N; still 8 after sug_edgeconv_path was added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
+ * round-3 entry points; 4: sug_chamfer / sug_node_offset_bwd became reproducible -- sug_chamfer takes a workspace; 5: sug_ce_pair_* take ignore_index, lse has 2M + 1 entries; sug_pointmlp_max_layer_fwd_xf and sug_col_stats_bn_grouped added; 6: sug_ptran_fused_fwd / sug_ptran_fused_supported added, sug_group_max_bwd fails instead of changing its summation order when the LDS opt-in is refused; 7: sug_adam_chain_step, sug_edge_weight_split_multi, sug_soft_mmd_multi_fwd / _bwd, sug_sda_prob_weights_multi, sug_chamfer_weights and sug_bn_replay_multi added, sug_bn_act_pool_* take the row stride ld_pool of the pooled outputs / their gradients; still 7 after sug_eval_accumulate, the KPConv entry points (sug_grid_subsample .. sug_seg_mean_bwd), sug_ptcls_head_supported / _fwd / _bwd and the multi-scale grouping / feature propagation entry points (sug_ball_query_multi, sug_three_nn_direct, sug_fp_interp_fwd / _bwd) and sug_grad_scale16 were added: purely additive entry points, no signature changed; still 7 after the shape limits SUG_CE_PAIR_MAX_* / SUG_CE_MAX_* / SUG_MCD_MAX_ROWS / SUG_CLASS_MMD_MAX_* / SUG_PREP_MAX_POINTS / SUG_ICP_MAX_POINTS became defines of this header: the values the kernels already had; still 7 after sug_cl_loss_fwd / _bwd and their SUG_CL_LOSS_* limits were added; still 7 after sug_point_ce_workspace / _fwd / _bwd and sug_part_iou_accumulate were added; still 7 after sug_reverse_lists_build was added; still 7 after sug_edgemlp_supported, sug_edge_expand_fwd / _bwd and sug_edgemlp_max_layer_fwd_xf were added; still 7 after sug_reverse_lists_tiled / _supported and their SUG_REV_TILED_* limits were added; 8: the KPConv entry points keep one row layout -- the eight sug_*_cap twins are gone, sug_grid_subsample takes C, level and the nullable record, sug_kpconv_fwd takes nq_valid, sug_seg_instnorm_fwd / _bwd take N; still 8 after sug_edgeconv_path and sug_bn_rows_plan were added). A binding checks sug_abi_version() == SUG_ABI_VERSION of the header it was written against. */
 #define SUG_ABI_VERSION 8
 int sug_abi_version(void);
 
@@ -277,6 +277,16 @@ int sug_affine_act(const float* z, int64_t ldz, const float* coef, int64_t rows,
  * (model/model_utils.py:8-32 on [B,C,N,1]).  ws: SUG_STATS_BLOCKS*2*C floats. */
 int sug_col_stats(const float* y, int64_t ldy, int64_t rows, int C, double* stats, float* ws,
                   void* stream);
+/* How the column reduction behind every BatchNorm entry point of this header (the statistics of sug_col_stats,
+ * sug_col_stats_bn and its grouped forms: mode 0; the backward sums of sug_edgeconv_bwd_reduce / sug_bn_act_rows_bwd:
+ * mode 1 with the [rows, C] intermediate a = scale*G, mode 2 without) would be launched over `groups` blocks of `rows`
+ * rows each, row stride ld; own_ws: a workspace block per group (sug_col_stats_bn_groups_exact); aligned: every pointer
+ * the mode reads or writes is 16-byte aligned.  plan (HOST, 4 ints) = float4 kernel (1) or scalar (0) | its lanes
+ * along the channels (LX resp. CW) | rows per workgroup | workgroups per group, -1 where the launch is refused (more
+ * than 16 groups, more partial rows than the workspace holds, a scalar layout with groups > 1 or in mode 2) and the
+ * caller goes group by group.  The launch itself is computed by the same function.  Launches nothing, touches no
+ * device memory. */
+int sug_bn_rows_plan(int64_t rows, int C, int64_t ld, int groups, int own_ws, int mode, int aligned, int32_t* plan);
 
 /* EdgeConv backward, step 1: G = gout * act'(scale*z+shift);
  * a[b,n,c] = scale[c]*G;  red[0:Co] = sum G, red[Co:2Co] = sum G*(z-mean)*rstd (fp64).

@@ -425,10 +425,12 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict
     s_red[(size_t)ry * 2 * C + C + c] = q;
   }
   __syncthreads();
+  // the row-lanes' partials are folded in fp64, in lane order: with few channels there are up to 256 of them, and a serial
+  // fp32 fold of that length cost a sum whose terms cancel 12 ulp (C = 1, 300 rows: dgamma off by 7e-7 of itself)
   for (int i = threadIdx.x; i < 2 * C; i += 256) {
-    float acc = 0.f;
-    for (int r = 0; r < RY; ++r) acc += s_red[(size_t)r * 2 * C + i];
-    ws[(size_t)blockIdx.x * 2 * C + i] = acc;
+    double acc = 0.0;
+    for (int r = 0; r < RY; ++r) acc += (double)s_red[(size_t)r * 2 * C + i];
+    ws[(size_t)blockIdx.x * 2 * C + i] = (float)acc;
   }
 }
 
@@ -693,13 +695,18 @@ static int col_rows_per_block(int64_t rows, int cw) {
 // [group][block]; returns the number of partial rows PER GROUP.  own_ws: ws holds one SUG_STATS_BLOCKS * 2C block per
 // group (partial rows + that group's pivot row) and every group is cut into workgroups exactly as a single-group call
 // over its rows would cut it: the partial sums, and with them the statistics, equal those of `groups` separate calls
-template <int MODE>
-static int launch_col_reduce(const float* y, int64_t ldy, const float* z, const float* coef, int64_t rows,
-                             int C, float slope, float* a, float* ws, hipStream_t st, int groups = 1, int pivoted = 0,
-                             int own_ws = 0) {
-  const bool vec = (C % 4 == 0) && (ldy % 4 == 0) && ((uintptr_t)y % 16 == 0) &&
-                   (MODE == 0 || (((uintptr_t)z % 16 == 0) && (MODE == 2 || (uintptr_t)a % 16 == 0) && ((uintptr_t)coef % 16 == 0)));
-  if (vec) {
+//
+// col_reduce_plan is the whole decision, from numbers alone: launch_col_reduce launches what it says and
+// sug_bn_rows_plan hands the same answer to a caller (tests assert the path a shape takes from it).  `aligned`: every
+// pointer the mode reads or writes sixteen bytes at a time (y; from MODE 1 on z and coef; in MODE 1 also a) is 16-byte
+// aligned.  lanes = LX of the float4 kernel resp. CW of the scalar one; grid = -1: refused, nothing is launched.
+struct ColReducePlan {
+  int vec, lanes, rpb, grid;
+};
+static ColReducePlan col_reduce_plan(int64_t rows, int C, int64_t ldy, int groups, int own_ws, int mode, bool aligned) {
+  ColReducePlan p;
+  p.vec = (C % 4 == 0) && (ldy % 4 == 0) && aligned;
+  if (p.vec) {
     int lx = 1;
     while (lx < (C >> 2) && lx < 256) lx <<= 1;
     const int ly = 256 / lx;
@@ -707,18 +714,46 @@ static int launch_col_reduce(const float* y, int64_t ldy, const float* z, const 
     if (rpb < 4 * ly) rpb = 4 * ly;
     rpb = (rpb + ly - 1) / ly * ly;
     const int grid = sug_divup(rows, rpb);
-    if ((int64_t)grid * (own_ws ? 1 : groups) > SUG_STATS_ROWS || groups > 16) return -1;
-    hipLaunchKernelGGL((col_reduce_vec4_kernel<MODE>), dim3(grid, groups), dim3(256), (size_t)ly * 2 * C * sizeof(float),
-                       st, y, ldy, z, coef, rows, C, slope, a, ws, lx, (int)rpb, pivoted, own_ws);
-    return grid;
+    p.lanes = lx;
+    p.rpb = (int)rpb;
+    p.grid = ((int64_t)grid * (own_ws ? 1 : groups) > SUG_STATS_ROWS || groups > 16) ? -1 : grid;
+    return p;
   }
-  if (groups > 1 || MODE == 2) return -1;
-  const int cw = col_width(C);
-  const int rpb = col_rows_per_block(rows, cw);
-  const int grid = sug_divup(rows, rpb);
-  hipLaunchKernelGGL((col_reduce_kernel<MODE>), dim3(grid), dim3(256), (size_t)(256 / cw) * 2 * C * sizeof(float),
-                     st, y, ldy, z, coef, rows, C, slope, a, ws, cw, rpb, pivoted);
-  return grid;
+  p.lanes = col_width(C);
+  p.rpb = col_rows_per_block(rows, p.lanes);
+  p.grid = (groups > 1 || mode == 2) ? -1 : sug_divup(rows, p.rpb);
+  return p;
+}
+
+template <int MODE>
+static int launch_col_reduce(const float* y, int64_t ldy, const float* z, const float* coef, int64_t rows,
+                             int C, float slope, float* a, float* ws, hipStream_t st, int groups = 1, int pivoted = 0,
+                             int own_ws = 0) {
+  const bool aligned = ((uintptr_t)y % 16 == 0) &&
+                       (MODE == 0 || (((uintptr_t)z % 16 == 0) && (MODE == 2 || (uintptr_t)a % 16 == 0) && ((uintptr_t)coef % 16 == 0)));
+  const ColReducePlan p = col_reduce_plan(rows, C, ldy, groups, own_ws, MODE, aligned);
+  if (p.grid < 0) return -1;
+  if (p.vec)
+    hipLaunchKernelGGL((col_reduce_vec4_kernel<MODE>), dim3(p.grid, groups), dim3(256),
+                       (size_t)(256 / p.lanes) * 2 * C * sizeof(float), st, y, ldy, z, coef, rows, C, slope, a, ws, p.lanes,
+                       p.rpb, pivoted, own_ws);
+  else
+    hipLaunchKernelGGL((col_reduce_kernel<MODE>), dim3(p.grid), dim3(256), (size_t)(256 / p.lanes) * 2 * C * sizeof(float),
+                       st, y, ldy, z, coef, rows, C, slope, a, ws, p.lanes, p.rpb, pivoted);
+  return p.grid;
+}
+
+extern "C" int sug_bn_rows_plan(int64_t rows, int C, int64_t ld, int groups, int own_ws, int mode, int aligned,
+                                int32_t* plan) {
+  SUG_REQUIRE(plan, "sug_bn_rows_plan: null pointer");
+  SUG_REQUIRE(rows > 0 && C > 0 && C <= 4096 && ld >= C && groups >= 1 && mode >= 0 && mode <= 2,
+              "sug_bn_rows_plan: bad shape");
+  const ColReducePlan p = col_reduce_plan(rows, C, ld, groups, own_ws, mode, aligned != 0);
+  plan[0] = p.vec;
+  plan[1] = p.lanes;
+  plan[2] = p.rpb;
+  plan[3] = p.grid;
+  return SUG_OK;
 }
 
 extern "C" int sug_col_stats(const float* y, int64_t ldy, int64_t rows, int C, double* stats,

@@ -871,6 +871,16 @@ def col_stats(y2, ws=None):
     return stats
 
 
+def bn_rows_plan(rows, C, ld=None, groups=1, own_ws=False, mode=0, aligned=True):
+    """(vec, lanes, rpb, grid) of the column reduction over `groups` blocks of `rows` rows each (sug_bn_rows_plan: the
+    function the launch itself is computed from; host-side, no launch).  mode 0: statistics, 1 / 2: the backward sums with /
+    without the [rows, C] intermediate; grid -1: the grouped launch is refused and the caller goes group by group."""
+    plan = (ctypes.c_int32 * 4)()
+    check(lib().sug_bn_rows_plan(rows, C, C if ld is None else ld, groups, int(bool(own_ws)), mode, int(bool(aligned)), plan),
+          'sug_bn_rows_plan')
+    return bool(plan[0]), plan[1], plan[2], plan[3]
+
+
 class _BNActRows(torch.autograd.Function):
     """act(BatchNorm(y)) over the rows of y [rows, C]; act = LeakyReLU(slope) (0: ReLU, 1: none).
     Train mode uses batch statistics and updates the running ones like nn.BatchNorm."""
